@@ -4,7 +4,7 @@
 Metric (BASELINE.json): sim-sec / wall-sec of the simulator step loop (``n_steps*dt / wall(sim.run)``,
 build excluded - reference ``experiments/run_pathint.py:160-165``, ``experiments/run_slam.py:230-235``).
 
-    python bench.py --gpus N --steps K --warmup W [--workload pathint|slam]
+    python bench.py --gpus N --steps K --warmup W [--workload pathint|slam] [--dump-outputs DIR] [--full]
 
 ``--workload pathint`` (default; BASELINE configs[1], the configuration the metric is quoted on): ``PathIntegration`` 2-D,
 ``ssp_dim=1015``, ``pi_n_neurons=10000`` per VCO (508 VCO ensembles, 5.08 M LIF neurons), synthetic band-limited random
@@ -22,7 +22,12 @@ model is sharded (strong scaling): the path integrator's VCO ensembles over the 
 decoded oscillator states (RCCL) and the linear read-out on rank 0; the SLAMNetwork's ensemble arrays by ensemble and its
 dense populations by neuron with ONE all-reduce per timestep, the whole run enqueued on one stream (ssn_phase_async).
 
-Extra legs on rank 0 at N = 1 (all outside the timed region):
+A plain run sets up, warms up, times the K steps and prints the line (``metric``, ``value``, ``unit``, ``ms_per_step``, ...).
+``--dump-outputs DIR`` then writes what the timed path computed in its last step - the probed output a caller of the
+simulator receives, ``sim.data[probe]`` over the last block - as ``DIR/<workload>_output.npy`` (float64); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+Extra legs behind ``--full``, on rank 0 at N = 1 (all outside the timed region):
   * roofline: every launch of the dominant kernel in the timed region is bracketed with HIP events on the simulator's
     stream.  The whole-block kernel (k_ens_block) keeps neuron parameters and state in registers / LDS for a block of
     timesteps, so it is bound by vector-ALU issue, not HBM: ``bound = "valu"``.  Peak = the time loop's own instruction
@@ -96,6 +101,11 @@ def parse():
                          "its collectives (what a one-GPU box can exercise of the RCCL path)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo: rehearsal of the multi-rank path with several ranks sharing one GPU (RCCL needs one GPU per rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the probed output of the last step as DIR/<workload>_output.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: roofline, end to end, cpu_baseline / parity, the SLAM leg "
+                         "(pathint), per-kernel times (slam)")
     return ap.parse_args()
 
 
@@ -261,6 +271,24 @@ def slam_roofline(us_per_timestep, n_neurons):
                     "spiking / active neurons; achieved = measured bytes / time of a timestep in this run"}
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs DIR: {name: array} -> DIR/<name>.npy as float64.  An array larger than its share of DUMP_BYTES is cut
+    to a fixed, seeded sample of its rows (in order); ``<name>_rows.npy`` then holds their indices."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // max(1, a[0].nbytes)), replace=False))
+            np.save(os.path.join(args.dump_outputs, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
+
 def emit(args, out):
     """The bench line: stdout (the descriptor saved by init_dist where a rank's stdout was redirected)."""
     f = getattr(args, "_json_out", None) or sys.stdout
@@ -332,8 +360,10 @@ def slam_parity_and_baseline(args, H, sm, model, sim, OracleSimulator, dt, out):
     out["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
 
 
-def slam_leg(args, H, build, Simulator, OracleSimulator, dt, timed_steps, warm_steps=64, device=0):
-    """BASELINE configs[2] on ONE GPU: SLAMNetwork, d = 1015, 10 000 neurons per VCO, M = 10 150, c = 100, 10 landmarks."""
+def slam_leg(args, H, build, Simulator, OracleSimulator, dt, timed_steps, warm_steps=64, device=0, full=True, block=None):
+    """BASELINE configs[2] on ONE GPU: SLAMNetwork, d = 1015, 10 000 neurons per VCO, M = 10 150, c = 100, 10 landmarks.
+    ``full``: also the roofline, the per-kernel times and the parity / cpu_baseline window.  ``block``: the timesteps of a
+    bench step, whose samples --dump-outputs writes (None: no dump)."""
     t0 = time.time()
     k = max(0, args.slam_cpu_steps)
     n_run = max(k, warm_steps) + timed_steps + 64
@@ -357,6 +387,10 @@ def slam_leg(args, H, build, Simulator, OracleSimulator, dt, timed_steps, warm_s
         out.update(value=round(timed_steps * dt / wall, 4), unit="sim-sec/wall-sec", timesteps_timed=timed_steps,
                    us_per_timestep=round(1e6 * wall / timed_steps, 2), launches_per_timestep=c["launches_per_step"],
                    device_us_per_timestep=round(1e3 * c["last_run_ms"] / timed_steps, 2))
+        if args.dump_outputs and block:
+            dump_outputs(args, {"slam_output": sim.data[sm.probe][-block:]})
+        if not full:
+            return out
         out["roofline"] = slam_roofline(out["us_per_timestep"], model.n_neurons)
         out["plan"] = ("rounds: every operator in the earliest round its data hazards allow, one heterogeneous grid (k_round) per "
                        "round; the 16 timesteps of a step graph software-pipelined")
@@ -397,12 +431,13 @@ def slam_main(args):
     if not sharded:
         from oracle import OracleSimulator
         leg = slam_leg(args, H, build, Simulator, OracleSimulator, dt, timed_steps=args.steps * block, warm_steps=args.warmup * block,
-                       device=local_rank)
+                       device=local_rank, full=args.full, block=block)
         wall = leg["timesteps_timed"] * dt / leg["value"]
         out.update(value=leg["value"], ms_per_step=round(1e3 * wall / args.steps, 4),
                    config={"workload": leg["workload"], "timesteps_per_step": block, "dt": dt, "eval_points_per_vco": eval_points_label(args),
-                           "parallelism": "1 GPU", "build_seconds": leg["build_seconds"], "build_cache": leg.get("build_cache")},
-                   roofline=leg["roofline"], slam=leg)
+                           "parallelism": "1 GPU", "build_seconds": leg["build_seconds"], "build_cache": leg.get("build_cache")})
+        if args.full:
+            out.update(roofline=leg["roofline"], slam=leg)
         for key in ("cpu_baseline", "parity", "gpu_over_cpu"):
             if key in leg:
                 out[key] = leg[key]
@@ -432,6 +467,8 @@ def slam_main(args):
     w = torch.tensor([wall], device="cuda" if args.dist_backend == "nccl" else "cpu", dtype=torch.float64)
     dist.all_reduce(w, op=dist.ReduceOp.MAX)
     wall = float(w.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, {"slam_output": r.probe_data()[-block:]})
     n_ex = sum(hi - lo for lo, hi in r.model.exchange)
     out.update(value=round(args.steps * block * dt / wall, 4), ms_per_step=round(1e3 * wall / args.steps, 4),
                config={"workload": f"SLAMNetwork 2-D ssp_dim={args.ssp_dim} pi_n_neurons={args.pi_n_neurons}/VCO "
@@ -532,6 +569,9 @@ def pathint_main(args):
         wall = float(w.item())
     sim_seconds = args.steps * args.block * dt
     value = sim_seconds / wall
+    if args.dump_outputs and rank == 0:
+        # (before any leg below steps the simulator further or resets it)
+        dump_outputs(args, {"pathint_output": (sim.data[pm.probe] if runner is None else runner.probe_data())[-args.block:]})
 
     out = {
         "metric": METRIC,
@@ -550,7 +590,9 @@ def pathint_main(args):
         out["config"]["shard_plan"] = {"chosen": "streaming launch per timestep (flag 128)" if runner._flags == 128 else "planner default (k_ens_block where a VCO fits a workgroup)",
                                        "vcos_per_rank": runner.hi - runner.lo,
                                        "seconds_per_block": {str(k): round(v, 6) for k, v in (plan_seconds or {}).items()}}
-    if rank == 0 and not sharded:
+    if rank == 0 and not sharded and not args.full:
+        sim.close()
+    if rank == 0 and not sharded and args.full:
         # ---- roofline: HIP events around every launch of the dominant kernel in the timed region ------
         c = sim.counters()
         n_timed = c["dominant_launches"] - c_warm["dominant_launches"]

@@ -1,10 +1,11 @@
 """bench.py: the roofline arithmetic is reproducible from the files under profiles/ (CPU), and a small run prints one
-JSON line with the fields the bench contract names (GPU)."""
+JSON line with the fields the bench contract names (GPU) - the plain run the headline only, --full the other legs too."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,7 +100,7 @@ def test_gpus_flag_starts_the_ranks_itself(tmp_path, monkeypatch):
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ssp-dim", "55", "--pi-n-neurons", "500", "--steps", "2",
-                        "--warmup", "1", "--block", "256", "--cpu-steps", "20", "--cpu-warmup", "10", "--slam-steps", "0"],
+                        "--warmup", "1", "--block", "256", "--cpu-steps", "20", "--cpu-warmup", "10", "--slam-steps", "0", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -118,6 +119,29 @@ def test_bench_prints_one_contract_line():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and "sample" in c
     assert d["parity"]["max_cosine_error"] < 1e-3 and d["value_end_to_end"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full the line holds the headline and its config, none of the other legs; --dump-outputs DIR writes the
+    probed output of the last timed step (float64, one row per timestep of the step)."""
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ssp-dim", "55", "--pi-n-neurons", "500", "--steps", "3",
+                        "--warmup", "1", "--block", "256", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "parity", "value_end_to_end", "slam"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 3 * 256 * 0.001 / (3 * d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+    a = np.load(out / "pathint_output.npy")
+    assert a.dtype == np.float64 and a.shape == (256, 55) and np.isfinite(a).all() and np.abs(a).max() > 0.1
+    assert sorted(os.listdir(out)) == ["pathint_output.npy"]
 
 
 @pytest.mark.gpu
@@ -144,7 +168,7 @@ def test_bench_slam_workload_one_rank_and_two():
     common = ["--workload", "slam", "--ssp-dim", "55", "--pi-n-neurons", "100", "--mem-n-neurons", "300", "--circonv-n-neurons", "50",
               "--steps", "2", "--warmup", "1", "--block", "64", "--slam-cpu-steps", "60"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, capture_output=True, text=True, timeout=900, env=env)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + common, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and "SLAMNetwork" in d["config"]["workload"] and d["roofline"]["bound"] == "hbm"

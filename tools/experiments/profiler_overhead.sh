@@ -1,8 +1,8 @@
 R=$GRAFT_REPO_ROOT; OUT=gpurun_out/r3r; mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --steps 3 --warmup 1 --cpu-steps 0 --no-end-to-end --slam-steps 0 > $R/$OUT/plain_short.json 2>/dev/null
-python3 $R/bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-end-to-end --slam-steps 0 > $R/$OUT/plain_long.json 2>/dev/null
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -o r3 -- python3 $R/bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-end-to-end --slam-steps 0 > $R/$OUT/rocprof_long.json 2> $R/$OUT/stats.err
+python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-steps 0 --no-end-to-end --slam-steps 0 > $R/$OUT/plain_short.json 2>/dev/null
+python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-steps 0 --no-end-to-end --slam-steps 0 > $R/$OUT/plain_long.json 2>/dev/null
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -o r3 -- python3 $R/bench.py --full --steps 20 --warmup 5 --cpu-steps 0 --no-end-to-end --slam-steps 0 > $R/$OUT/rocprof_long.json 2> $R/$OUT/stats.err
 cp $(find $R/$OUT/stats -name "*kernel_stats.csv" | head -1) $R/$OUT/kernel_stats_long.csv
 rm -rf $R/$OUT/stats
 cd $R

@@ -9,10 +9,10 @@ OUT=${1:-gpurun_out/prof}
 R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --steps 3 --warmup 1 --cpu-steps 0 --no-end-to-end --slam-cpu-steps 0"
+B="$R/bench.py --full --steps 3 --warmup 1 --cpu-steps 0 --no-end-to-end --slam-cpu-steps 0"
 # (the stats pass runs the DRIVER's command shape - 20 timed blocks behind 5 warm-up ones: the first launches of a short run are
 #  ~13 % slower, and the average of a 3-block run does not agree with the bench line's)
-BS="$R/bench.py --steps 20 --warmup 5 --cpu-steps 0 --no-end-to-end --slam-cpu-steps 0"
+BS="$R/bench.py --full --steps 20 --warmup 5 --cpu-steps 0 --no-end-to-end --slam-cpu-steps 0"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -o r4 -- python3 $BS --slam-steps 256 > $R/$OUT/bench_under_rocprof.json 2> $R/$OUT/stats.err || exit 1
 find $R/$OUT/stats -name "*kernel_trace*" -delete; find $R/$OUT/stats -name "*agent_info*" -delete
 echo stats done

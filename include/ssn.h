@@ -100,6 +100,79 @@ typedef struct ssn_probe_desc {
 
 typedef struct ssn_range { int64_t lo, hi; } ssn_range;   /* signal range [lo, hi) */
 
+/* Plan switches: the bits of ssn_model_desc.flags.  Debug / A-B switches, default 0; tests check that every alternative
+ * plan gives the same results.  ssn_create refuses a value with any other bit set.
+ * (Round 1's opt-in experiments 32, 64, 2048, 16384, 32768 the multi-stream step graph 256 and the program-planner
+ *  switches 65536, 131072, 1048576 of the round-1 plan - all measured slower - were removed.) */
+enum ssn_plan_flag {
+  /* no fused recurrent-array core (generic programs) */
+  SSN_PLAN_NO_FUSED_CORE = 1,
+  /* no LIF fast path (unpacked state, dense row-major decoders) */
+  SSN_PLAN_NO_LIF_FAST = 2,
+  /* LIF fast path with dense decoders (no spike-sparse gather) */
+  SSN_PLAN_DENSE_DECODERS = 4,
+  /* dense decoder products for dense ensembles (no k_spmv_partial) */
+  SSN_PLAN_NO_SPMV = 8,
+  /* fused recurrent-array core always with a separate finish kernel
+   * (default: finish deferred into the next step's prologue, 1 launch per step) */
+  SSN_PLAN_SEPARATE_FINISH = 16,
+  /* no whole-block kernel for a recurrent array of independent ensembles (k_ens_block): step it once per timestep
+   * (k_ensarray) instead */
+  SSN_PLAN_NO_BLOCK_KERNEL = 128,
+  /* no FFT kernel for DFT-structured matvecs (always multiply by the matrix) */
+  SSN_PLAN_NO_FFT = 512,
+  /* k_spmv_partial rebuilds the spike list itself (no segmented list from k_neurons) */
+  SSN_PLAN_SPMV_OWN_LIST = 1024,
+  /* one launch per operator (adjacent independent operators of one kind are not batched); only acts together with
+   * SSN_PLAN_NO_ROUNDS */
+  SSN_PLAN_NO_ITEM_BATCH = 4096,
+  /* ensemble arrays always leave partial sums for a finish operator (no direct write when one workgroup covers an
+   * ensemble) */
+  SSN_PLAN_ENS_PARTIALS = 8192,
+  /* one launch per element-wise operator of the time-batched stages (no batching) */
+  SSN_PLAN_NO_STAGE_BATCH = 262144,
+  /* clean-up similarities always from the pass over the table (no factored grid) */
+  SSN_PLAN_NO_FACTORED_GRID = 524288,
+  /* no rounds: one launch per big operator and one k_program launch per run of small ones (the round-1 plan).
+   * Default: every operator takes the earliest round its data hazards allow and a round is ONE heterogeneous grid
+   * (k_round) */
+  SSN_PLAN_NO_ROUNDS = 2097152,
+  /* ensemble arrays are launched on their own, not as bodies of the round's grid */
+  SSN_PLAN_ENS_OWN_LAUNCH = 4194304,
+  /* the rounds of one timestep at a time (default: the steps_per_graph timesteps of a step graph are
+   * software-pipelined - an operator of step s + 1 may share a round with operators of step s) */
+  SSN_PLAN_NO_PIPELINE = 8388608,
+  /* heavy operators stay whole (default: the pipelined plan may run the blocks of a bandwidth-bound operator in pieces
+   * over the rounds of its slack window) */
+  SSN_PLAN_NO_BALANCE = 16777216,
+  /* merged element-wise operators stay whole (default: cut at the range endpoints of the other operators, so that each
+   * piece has its own hazards) */
+  SSN_PLAN_NO_CUTS = 33554432,
+  /* no chains (default: an element-wise micro-operator whose only hazards inside a round are on identical element
+   * ranges joins that round and runs behind its predecessor in the same block) */
+  SSN_PLAN_NO_CHAINS = 134217728,
+  /* k_dft also for chirp-z (Bluestein) transforms of 2048 points and more (default: their dense matrix - one workgroup
+   * needs 40 us for such a transform) */
+  SSN_PLAN_BLUESTEIN_FFT = 268435456,
+  /* the four-step FFT on the matrix cores (two small dense DFTs as f32 MFMA products around a twiddle multiply, round 3;
+   * any factorisation, primes up to 192 as one dense DFT) instead of the Stockham passes (generic radix-r butterflies
+   * through LDS).  Correct for every length of the tests, but measured no faster (its operand loads are
+   * latency-bound): opt-in */
+  SSN_PLAN_FOUR_STEP_FFT = 536870912,
+  /* split ensembles in the whole-block kernel (f32, at most 4 decoded rows): an array with fewer ensembles than the GPU
+   * has CUs (a 4- or 8-GPU shard of config 2) is stepped by 2 or 4 member workgroups per ensemble that exchange their
+   * partial sums every timestep; needs every workgroup of the launch resident at once, i.e. the GPU for this process
+   * alone */
+  SSN_PLAN_SPLIT_BLOCK = 1073741824
+};
+/* every bit that has a name */
+#define SSN_PLAN_ALL_FLAGS                                                                                                   \
+  (SSN_PLAN_NO_FUSED_CORE | SSN_PLAN_NO_LIF_FAST | SSN_PLAN_DENSE_DECODERS | SSN_PLAN_NO_SPMV | SSN_PLAN_SEPARATE_FINISH |   \
+   SSN_PLAN_NO_BLOCK_KERNEL | SSN_PLAN_NO_FFT | SSN_PLAN_SPMV_OWN_LIST | SSN_PLAN_NO_ITEM_BATCH | SSN_PLAN_ENS_PARTIALS |    \
+   SSN_PLAN_NO_STAGE_BATCH | SSN_PLAN_NO_FACTORED_GRID | SSN_PLAN_NO_ROUNDS | SSN_PLAN_ENS_OWN_LAUNCH |                      \
+   SSN_PLAN_NO_PIPELINE | SSN_PLAN_NO_BALANCE | SSN_PLAN_NO_CUTS | SSN_PLAN_NO_CHAINS | SSN_PLAN_BLUESTEIN_FFT |             \
+   SSN_PLAN_FOUR_STEP_FFT | SSN_PLAN_SPLIT_BLOCK)
+
 typedef struct ssn_model_desc {
   int32_t abi_version;  /* SSN_ABI_VERSION */
   int32_t dtype;        /* ssn_dtype       */
@@ -128,49 +201,7 @@ typedef struct ssn_model_desc {
   int32_t reserved;
   const ssn_range* exchange;
   int32_t block_steps;                /* timesteps per time-batched block; 0 = library default (1024, or 256 for very wide models) */
-  int32_t flags;                      /* debug / A-B switches (default 0; tests check that every alternative plan gives the same results):
-                                         1 = no fused recurrent-array core (generic programs),
-                                         2 = no LIF fast path (unpacked state, dense row-major decoders),
-                                         4 = LIF fast path with dense decoders (no spike-sparse gather),
-                                         8 = dense decoder products for dense ensembles (no k_spmv_partial),
-                                         16 = fused recurrent-array core always with a separate finish kernel
-                                              (default: finish deferred into the next step's prologue, 1 launch per step),
-                                         128 = no whole-block kernel for a recurrent array of independent ensembles
-                                              (k_ens_block): step it once per timestep (k_ensarray) instead,
-                                         512 = no FFT kernel for DFT-structured matvecs (always multiply by the matrix),
-                                         1024 = k_spmv_partial rebuilds the spike list itself (no segmented list from k_neurons),
-                                         4096 = one launch per operator (adjacent independent operators of one kind are not batched),
-                                         8192 = ensemble arrays always leave partial sums for a finish operator (no direct write
-                                              when one workgroup covers an ensemble),
-                                         262144 = one launch per element-wise operator of the time-batched stages (no batching),
-                                         524288 = clean-up similarities always from the pass over the table (no factored grid),
-                                         2097152 = no rounds: one launch per big operator and one k_program launch per run of
-                                              small ones (the round-1 plan; flag 4096 only acts
-                                              together with this one).  Default: every operator takes the earliest round its data
-                                              hazards allow and a round is ONE heterogeneous grid (k_round),
-                                         4194304 = ensemble arrays are launched on their own, not as bodies of the round's grid,
-                                         8388608 = the rounds of one timestep at a time (default: the steps_per_graph timesteps of a
-                                              step graph are software-pipelined - an operator of step s + 1 may share a round with
-                                              operators of step s),
-                                         16777216 = heavy operators stay whole (default: the pipelined plan may run the blocks of a
-                                              bandwidth-bound operator in pieces over the rounds of its slack window),
-                                         33554432 = merged element-wise operators stay whole (default: cut at the range endpoints of
-                                              the other operators, so that each piece has its own hazards),
-                                         134217728 = no chains (default: an element-wise micro-operator whose only hazards inside a
-                                              round are on identical element ranges joins that round and runs behind its
-                                              predecessor in the same block),
-                                         268435456 = k_dft also for chirp-z (Bluestein) transforms of 2048 points and more
-                                              (default: their dense matrix - one workgroup needs 40 us for such a transform).
-                                         536870912 = the four-step FFT on the matrix cores (two small dense DFTs as f32 MFMA products around a
-                                              twiddle multiply, round 3; any factorisation, primes up to 192 as one dense DFT) instead of
-                                              the Stockham passes (generic radix-r butterflies through LDS).  Correct for every length of the
-                                              tests, but measured no faster (its operand loads are latency-bound): opt-in.
-                                         1073741824 = split ensembles in the whole-block kernel (f32, at most 4 decoded rows): an array with fewer
-                                              ensembles than the GPU has CUs (a 4- or 8-GPU shard of config 2) is stepped by 2 or 4
-                                              member workgroups per ensemble that exchange their partial sums every timestep; needs every
-                                              workgroup of the launch resident at once, i.e. the GPU for this process alone.
-                                         (Round 1's opt-in experiments 32, 64, 2048, 16384, 32768 the multi-stream step graph 256 and the program-planner switches 65536, 131072, 1048576 of
-                                          the round-1 plan - all measured slower - were removed.) */
+  int32_t flags;                      /* plan switches: an OR of ssn_plan_flag values (default 0) */
 } ssn_model_desc;
 
 typedef struct ssn_counters {
@@ -189,7 +220,7 @@ typedef struct ssn_counters {
   int32_t block_threads;            /* threads actually launched per workgroup                    */
   int32_t fft_transforms;           /* DFT-structured matvecs of a timestep that run as k_dft (FFT) instead of the matrix */
   int32_t fft_bluestein;            /* ... of which through Bluestein's convolution (a prime factor > 32)           */
-  int32_t block_members;            /* member workgroups per ensemble of the whole-block kernel (flag 1073741824; 1 = not split, 0 = no block kernel) */
+  int32_t block_members;            /* member workgroups per ensemble of the whole-block kernel (SSN_PLAN_SPLIT_BLOCK; 1 = not split, 0 = no block kernel) */
   int32_t batch_products_skipped; /* time-batched products not multiplied out because their whole input was zero over the block (cumulative) */
   /* whole-block kernel (f32): (wave, round) slots stepped since create / reset, and how many of them were silent - no neuron of the
    * slot spiked in the timestep, so the spike-time arithmetic and the decode were left out (ABI 7; the VALU roofline of bench.py

@@ -15,6 +15,29 @@ SSN_BUF_REAL, SSN_BUF_I32 = 0, 1
 NEURON_CODE = {"lif": 0, "lifrate": 1, "relu": 2}
 OP_CODE = {"fill": 1, "table": 2, "axpy": 3, "matvec": 4, "lowpass": 5, "ensarray": 6, "neurons": 7,
            "pes": 8, "voja": 9, "cleanup": 10, "gate": 11, "lincomb": 12}
+# plan switches: the bits of ssn_model_desc.flags (enum ssn_plan_flag of include/ssn.h, which says what each one does)
+SSN_PLAN_NO_FUSED_CORE = 1
+SSN_PLAN_NO_LIF_FAST = 2
+SSN_PLAN_DENSE_DECODERS = 4
+SSN_PLAN_NO_SPMV = 8
+SSN_PLAN_SEPARATE_FINISH = 16
+SSN_PLAN_NO_BLOCK_KERNEL = 128
+SSN_PLAN_NO_FFT = 512
+SSN_PLAN_SPMV_OWN_LIST = 1024
+SSN_PLAN_NO_ITEM_BATCH = 4096
+SSN_PLAN_ENS_PARTIALS = 8192
+SSN_PLAN_NO_STAGE_BATCH = 262144
+SSN_PLAN_NO_FACTORED_GRID = 524288
+SSN_PLAN_NO_ROUNDS = 2097152
+SSN_PLAN_ENS_OWN_LAUNCH = 4194304
+SSN_PLAN_NO_PIPELINE = 8388608
+SSN_PLAN_NO_BALANCE = 16777216
+SSN_PLAN_NO_CUTS = 33554432
+SSN_PLAN_NO_CHAINS = 134217728
+SSN_PLAN_BLUESTEIN_FFT = 268435456
+SSN_PLAN_FOUR_STEP_FFT = 536870912
+SSN_PLAN_SPLIT_BLOCK = 1073741824
+PLAN_FLAGS = {k: v for k, v in list(globals().items()) if k.startswith("SSN_PLAN_")}
 PROBE_KINDS = {"v_pk_fma_f32": 0, "v_pk_mul_f32": 1, "v_pk_add_f32": 2, "trans": 3, "v_fma_f32": 4, "v_add_f32": 5, "dpp": 6,
                "v_mov_b32": 7, "lane": 8, "v_cndmask_b32": 9, "other": 10}
 STATUS = {0: "SSN_OK", -1: "SSN_EINVAL", -2: "SSN_EHIP", -3: "SSN_ERCCL", -4: "SSN_ENOMEM", -5: "SSN_EUNSUPPORTED"}

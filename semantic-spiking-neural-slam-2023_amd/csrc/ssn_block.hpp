@@ -862,10 +862,9 @@ static hipError_t launch_block_npt(hipStream_t s, const BlockArgs<T>& a) {
 }
 
 template <typename T>
-bool ens_block_supported(int din, int dout, int n, int* threads, int* tpb, int* npt, int* enc_lds) {
+bool ens_block_supported(int din, int dout, int n, const int want[3], int* threads, int* tpb, int* npt, int* enc_lds) {
   if (!(din == 3 && dout >= 3 && dout <= 5)) return false;
-  int want_tpb = 0, want_npt = 0, want_lds = 0;
-  if (const char* env = getenv("SSN_BLOCK_VARIANT")) sscanf(env, "%d,%d,%d", &want_tpb, &want_npt, &want_lds);   // tuning knob
+  const int want_tpb = want[0], want_npt = want[1], want_lds = want[2];      // tuning knob SSN_BLOCK_VARIANT (all 0: the first variant that fits)
   const int pk = sizeof(T) == 4 ? 2 : 1;         // neurons per group; single-group variants run n / pk threads
   for (int i = 0; i < BlockVariants<T>::N; ++i) {
     const BlockVariant v = BlockVariants<T>::v[i];

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -92,6 +93,84 @@ enum ItemType { IT_PROGRAM = 0, IT_ENS, IT_MATVEC, IT_NEURONS, IT_PES, IT_VOJA, 
                 IT_MATVEC_NEURONS,  // (round plan) a dense population's encoder product with the neuron update in its epilogue
                 IT_NONE };          // (round plan) an operator that was folded into another one
 
+// Plan options: ssn_model_desc.flags and the environment knobs, read once at ssn_create and constant for the simulator's
+// life.  PlanOptions::read is the only caller of getenv in the library.  One row per knob: how the variable is read, the
+// member, the variable, the default, the meaning ("Environment switches", lists the same rows).
+//   PRESENT  true when the variable is set at all        OFF0  false when it reads 0        ON1  true when it reads 1
+//   INT / LL / REAL  atoi / atoll / atof of the value (UNSET: absent, the planner decides)
+//   INT3  "a,b,c" (missing fields stay 0)
+#define SSN_PLAN_KNOBS(X)                                                                                                                          \
+  X(PRESENT, debug_plan, "SSN_DEBUG_PLAN", false, "print the plan to stderr at ssn_create (and per-item times after a profile = 2 run)")          \
+  X(INT, debug_deps, "SSN_DEBUG_DEPS", UNSET, "first of four pipelined rounds whose instances are printed with what they wait for")                \
+  X(INT, ens_sweeps, "SSN_ENS_SWEEPS", UNSET, "256-thread sweeps per workgroup of an ensemble array (clamped to what the array has)")            \
+  X(OFF0, small_ens, "SSN_SMALL_ENS", true, "a wave per ensemble for arrays of many small 1-D ensembles (RK_ENS_SMALL)")                          \
+  X(INT3, block_variant, "SSN_BLOCK_VARIANT", Int3(), "tpb,npt,lds of the whole-block kernel variant to use")                                     \
+  X(INT, block_split, "SSN_BLOCK_SPLIT", UNSET, "member workgroups per ensemble of the split whole-block kernel (1, 2, 4 or 8; others ignored)")  \
+  X(INT, block_split_cus, "SSN_BLOCK_SPLIT_CUS", UNSET, "CU count the split is sized for (tests: pretend the GPU is smaller / larger)")           \
+  X(ON1, block_sort, "SSN_BLOCK_SORT", false, "whole-block kernel: neurons in slot order (only pays with a SSN_BLOCK_SKIP build)")               \
+  X(PRESENT, dft_no_inplace, "SSN_DFT_NO_INPLACE", false, "Bluestein transforms never in place")                                                  \
+  X(INT, spmv_max_chunks, "SSN_SPMV_MAX_CHUNKS", 64, "most chunks of a segmented spike list per sparse decode (at least 1)")                     \
+  X(LL, grid_min_mb, "SSN_GRID_MIN_MB", 64, "smallest clean-up table (MB) whose similarities come from the factored grid as an MFMA product")     \
+  X(LL, grid_dot_min_mb, "SSN_GRID_DOT_MIN_MB", 16, "smallest clean-up table (MB) that goes through its factor tables as bodies of the round grid") \
+  X(INT, grid_split, "SSN_GRID_SPLIT", UNSET, "K-split of the grid product (clamped to 1..8)")                                                    \
+  X(INT, matvec_r1_max, "SSN_MATVEC_R1_MAX", 4096, "tallest matrix that runs four rows per workgroup in a round (taller: sixteen)")              \
+  X(REAL, cost_pes, "SSN_COST_PES", 2.0, "balancer: fraction of its matrix a PES update is priced at")                                            \
+  X(REAL, cost_voja, "SSN_COST_VOJA", 0.2, "balancer: fraction of its matrix a Voja update is priced at")                                         \
+  X(REAL, lat_dft, "SSN_LAT_DFT", 9.0, "balancer: latency of a transform body (us)")                                                              \
+  X(REAL, lat_solo, "SSN_LAT_SOLO", 3.0, "balancer: latency of a gate / argmax body (us)")                                                        \
+  X(OFF0, pes_fold, "SSN_PES_FOLD", true, "fold the filter of a PES rule's activities into the rule's body")                                      \
+  X(ON1, phased_pes_fold, "SSN_PHASED_PES_FOLD", false, "... also in neuron-sharded plans")                                                       \
+  X(OFF0, fuse_neurons, "SSN_FUSE_NEURONS", true, "neuron update of a dense population in the epilogue of its encoder product")                   \
+  X(INT, fuse_min_rows, "SSN_FUSE_MIN_ROWS", 4097, "smallest population that is fused so (tests lower it)")                                       \
+  X(OFF0, solo_chains, "SSN_SOLO_CHAINS", true, "serial chains of single-workgroup operators (RK_SOLO)")                                          \
+  X(OFF0, phased_solo, "SSN_PHASED_SOLO", true, "... in neuron-sharded plans")                                                                    \
+  X(ON1, solo_dft, "SSN_SOLO_DFT", false, "transforms as members of serial chains (measured slower)")                                             \
+  X(REAL, solo_cap_us, "SSN_SOLO_CAP_US", 16.0, "longest serial chain in estimated microseconds")                                                 \
+  X(LL, solo_max_len, "SSN_SOLO_MAX_LEN", 2048, "longest glue operator (elements) a single workgroup takes")                                      \
+  X(OFF0, round_interleave, "SSN_ROUND_INTERLEAVE", true, "interleaved dispatch of a round's big grids behind its latency-bound head")            \
+  X(OFF0, head_prio, "SSN_HEAD_PRIO", true, "raised wave priority for the head blocks of a round")                                                \
+  X(PRESENT, phase2_sequential, "SSN_PHASE2_SEQUENTIAL", false, "sharded: phase 1 of a timestep and phase 0 of the next as two sets of rounds")   \
+  X(INT, cycle_steps, "SSN_CYCLE_STEPS", 16, "sharded: timesteps pipelined over the exchange (2..64; 0 or 1: off)")                               \
+  X(PRESENT, no_batch_reorder, "SSN_NO_BATCH_REORDER", false, "time-batched stages keep the builder's operator order")                            \
+  X(PRESENT, no_zero_skip, "SSN_NO_ZERO_SKIP", false, "time-batched products are multiplied out even when their whole input is zero")
+
+struct PlanOptions {
+  struct Int3 { int v[3] = {0, 0, 0}; };
+  static constexpr int UNSET = INT_MIN;
+  enum Kind { K_PRESENT, K_OFF0, K_ON1, K_INT, K_LL, K_REAL, K_INT3 };
+  typedef bool T_PRESENT; typedef bool T_OFF0; typedef bool T_ON1; typedef int T_INT; typedef long long T_LL; typedef double T_REAL; typedef Int3 T_INT3;
+
+  int flags = 0;                              // ssn_model_desc.flags (ssn_plan_flag bits)
+#define X(kind, name, env, def, doc) T_##kind name = def;
+  SSN_PLAN_KNOBS(X)
+#undef X
+
+  bool has(int bit) const { return (flags & bit) != 0; }
+
+  static PlanOptions read(int flags) {
+    PlanOptions o;
+    o.flags = flags;
+    struct Row { const char* env; Kind kind; void* field; };
+#define X(kind, name, env, def, doc) {env, K_##kind, &o.name},
+    const Row rows[] = {SSN_PLAN_KNOBS(X)};
+#undef X
+    for (const Row& k : rows) {
+      const char* v = getenv(k.env);
+      if (!v) continue;
+      switch (k.kind) {
+        case K_PRESENT: *(bool*)k.field = true; break;
+        case K_OFF0: if (atoi(v) == 0) *(bool*)k.field = false; break;
+        case K_ON1: if (atoi(v) == 1) *(bool*)k.field = true; break;
+        case K_INT: *(int*)k.field = atoi(v); break;
+        case K_LL: *(long long*)k.field = atoll(v); break;
+        case K_REAL: *(double*)k.field = atof(v); break;
+        case K_INT3: { Int3* t = (Int3*)k.field; sscanf(v, "%d,%d,%d", &t->v[0], &t->v[1], &t->v[2]); break; }
+      }
+    }
+    return o;
+  }
+};
+
 }  // namespace
 
 struct ssn_sim {
@@ -167,7 +246,7 @@ struct Sim final : ssn_sim {
   T* bsig = nullptr;                          // [block+1][n_sig]
   int block = 0;                              // timesteps per block (0: staging off)
   bool core_empty = false;                    // no per-timestep work at all
-  int flags = 0;                              // ssn_model_desc.flags
+  const PlanOptions opt;                      // ssn_model_desc.flags and the environment knobs, as read at ssn_create
   bool fused_core = false;                    // core == one recurrent ensemble array: [k_ensarray, k_ens_finish]
   bool fused_defer = false;                   // ... with the finish deferred into the next step's prologue: [k_ensarray]
   ssn::FinishArgs<T> fin_begin, fin_flush;
@@ -207,7 +286,7 @@ struct Sim final : ssn_sim {
   // timestep k sits between segments k and k + 1 (ssn_run_phase / ssn_phase_async with phase 3 = "the next segment")
   std::vector<std::vector<Launch>> cycle_segs;
   int cycle_steps = 0, next_seg = 0;
-  int n_fused_populations = 0, n_serial_chains = 0, n_folded_inputs = 0;      // (counters of the round plan)
+  int n_fused_populations = 0, n_serial_chains = 0;      // (counters of the round plan)
   std::vector<hipGraph_t> cycle_graph;
   std::vector<hipGraphExec_t> cycle_exec;
   std::vector<Launch> phase2_list;            // neuron-sharded models: the updates of timestep s and timestep s + 1 up to its exchange,
@@ -268,6 +347,8 @@ struct Sim final : ssn_sim {
   int64_t type_launches[N_ITEM_TYPES] = {};
   std::vector<double> item_ms;                   // ... and per plan item (printed under SSN_DEBUG_PLAN)
   std::vector<int64_t> item_n;
+
+  explicit Sim(const ssn_model_desc* m) : opt(PlanOptions::read(m->flags)) {}
 
   ~Sim() override {
     hipSetDevice(device);
@@ -377,10 +458,10 @@ struct Sim final : ssn_sim {
 
   bool ens_fast(const ssn_op_desc& o) const {
     // spiking LIF with min_voltage == 0: packed state word + (dout >= 3) spike-sparse neuron-major decoders
-    return !(flags & 2) && o.i[11] == SSN_LIF && o.f[2] == 0.0;
+    return !opt.has(SSN_PLAN_NO_LIF_FAST) && o.i[11] == SSN_LIF && o.f[2] == 0.0;
   }
 
-  bool ens_sparse(const ssn_op_desc& o) const { return ens_fast(o) && !(flags & 4) && o.i[4] >= 3; }
+  bool ens_sparse(const ssn_op_desc& o) const { return ens_fast(o) && !opt.has(SSN_PLAN_DENSE_DECODERS) && o.i[4] >= 3; }
 
   // host [rows][cols] double -> device layout of buffer b
   int upload_buf(Buf& b, const double* src) {
@@ -499,7 +580,6 @@ struct Sim final : ssn_sim {
   int create(const ssn_model_desc* m) {
     device = m->device;
     dt = m->dt;
-    flags = m->flags;
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&ev_run0));
@@ -518,11 +598,11 @@ struct Sim final : ssn_sim {
     for (int i = 0; i < m->n_ops; ++i)
       if (m->ops[i].kind == SSN_OP_PES || m->ops[i].kind == SSN_OP_VOJA) learned_w.insert((int)m->ops[i].i[0]);
     // decoders applied to the spike vector of a dense LIF ensemble are kept neuron-major and multiplied sparsely
-    if (!(flags & 8))
+    if (!opt.has(SSN_PLAN_NO_SPMV))
       for (int i = 0; i < m->n_ops; ++i) {
         const ssn_op_desc& o = m->ops[i];
         if (o.kind != SSN_OP_MATVEC || o.stage != 1 || is_micro(o) || o.i[3] < 128) continue;
-        if (o.i[3] > 15000 && (flags & 1024)) continue;      // (a spike list rebuilt inside k_spmv_partial lives in LDS)
+        if (o.i[3] > 15000 && opt.has(SSN_PLAN_SPMV_OWN_LIST)) continue;      // (a spike list rebuilt inside k_spmv_partial lives in LDS)
         for (int j = 0; j < m->n_ops; ++j) {
           const ssn_op_desc& q = m->ops[j];
           if (q.kind == SSN_OP_NEURONS && q.i[5] == SSN_LIF && q.i[1] == o.i[1] && q.i[2] == o.i[3]) sparse_w.insert((int)o.i[4]);
@@ -705,7 +785,7 @@ struct Sim final : ssn_sim {
     int sweeps = 1;
     const int max_sweeps = (n_vec + 255) / 256;
     while (sweeps < max_sweeps && (int64_t)a.K * ((n_vec + 256 * (sweeps + 1) - 1) / (256 * (sweeps + 1))) >= min_wgs) ++sweeps;
-    if (const char* env = getenv("SSN_ENS_SWEEPS")) sweeps = std::max(1, std::min(max_sweeps, atoi(env)));   // tuning knob
+    if (opt.ens_sweeps != PlanOptions::UNSET) sweeps = std::max(1, std::min(max_sweeps, opt.ens_sweeps));   // tuning knob
     a.chunk_vec = 256 * sweeps;
     a.P = (n_vec + a.chunk_vec - 1) / a.chunk_vec;
   }
@@ -851,7 +931,7 @@ struct Sim final : ssn_sim {
     const int d = kind == 5 ? (int)o.i[2] : (int)o.i[3];
     *a = ssn::DftArgs{};
     if (d < 8 || d > 6400) return SSN_OK;
-    if (flags & 536870912) {
+    if (opt.has(SSN_PLAN_FOUR_STEP_FFT)) {
       // opt-in (round 3, measured slower than the Stockham passes as built - DESIGN.md): the four-step transform on the matrix
       // cores; a length without a usable divisor pair (a prime above 192, or 2 x such a prime ...) goes through Bluestein's
       // convolution of the cheapest length M in [2d - 1, 2d - 1 + 12 %]
@@ -894,7 +974,7 @@ struct Sim final : ssn_sim {
     if (rad.empty() || rad.size() > 12) return SSN_OK;
     float2* tw = nullptr;
     CHK(dft_table(dft_key(DK_TWIDDLE, L), twiddles(L), &tw));
-    bool small_only = M > 0 && !getenv("SSN_DFT_NO_INPLACE");          // every pass an in-register one: both transforms in place
+    bool small_only = M > 0 && !opt.dft_no_inplace;          // every pass an in-register one: both transforms in place
     for (int r : rad) small_only = small_only && (r == 8 || r == 4 || r == 2);
     if (M > 0) CHK(bluestein_tables(d, M, a, small_only ? &rad : nullptr));
     a->src = (const float*)(sig + o.i[1]); a->dst = (float*)(sig + o.i[0]); a->tw = tw; a->N = d; a->kind = kind;
@@ -1081,7 +1161,7 @@ struct Sim final : ssn_sim {
       }
     // ---- can the finish be deferred into the next step's prologue?  every recurrent term must read a
     //      filter state owned by a row of the SAME ensemble (ens_k -> Lowpass -> ens_k), one term per input
-    bool defer = !(flags & 16);        // decided below: only worth it in the latency-bound regime (few workgroups)
+    bool defer = !opt.has(SSN_PLAN_SEPARATE_FINISH);        // decided below: only worth it in the latency-bound regime (few workgroups)
     std::vector<int> xrow((size_t)(K * din), -1), lp_has((size_t)(K * dout), 0);
     std::vector<double> xalpha((size_t)(K * din), 0.0);
     {
@@ -1123,20 +1203,20 @@ struct Sim final : ssn_sim {
     // workgroups must be resident together, so P is only raised while K * P fits the CUs - and the caller only asks for
     // it when this process has the GPU to itself.
     int split_P = 1, n_member = 0;
-    if ((flags & 1073741824) && sizeof(T) == 4 && dout <= 4) {
+    if (opt.has(SSN_PLAN_SPLIT_BLOCK) && sizeof(T) == 4 && dout <= 4) {
       hipDeviceProp_t prop;
       int n_cu = 256;
       if (hipGetDeviceProperties(&prop, device) == hipSuccess) n_cu = prop.multiProcessorCount;
-      if (const char* env = getenv("SSN_BLOCK_SPLIT_CUS")) n_cu = atoi(env);            // (tests: pretend the GPU is smaller / larger)
+      if (opt.block_split_cus != PlanOptions::UNSET) n_cu = opt.block_split_cus;            // (tests: pretend the GPU is smaller / larger)
       const int64_t n_ens = eo.i[2];
       for (int cand : {4, 2}) {
         if (K * cand <= n_cu && n_ens / cand >= 1024) { split_P = cand; break; }
       }
-      if (const char* env = getenv("SSN_BLOCK_SPLIT")) { const int q = atoi(env); if (q == 1 || q == 2 || q == 4 || q == 8) split_P = q; }
+      { const int q = opt.block_split; if (q == 1 || q == 2 || q == 4 || q == 8) split_P = q; }
       if (split_P > 1) n_member = (int)(((n_ens + split_P - 1) / split_P + 3) / 4 * 4);
     }
-    if (defer && !(flags & 128) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt)) &&
-        ssn::ens_block_supported<T>((int)din, (int)dout, split_P > 1 ? n_member : (int)eo.i[2], &blk_threads, &blk_tpb, &blk_npt, &blk_lds)) {
+    if (defer && !opt.has(SSN_PLAN_NO_BLOCK_KERNEL) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt)) &&
+        ssn::ens_block_supported<T>((int)din, (int)dout, split_P > 1 ? n_member : (int)eo.i[2], opt.block_variant.v, &blk_threads, &blk_tpb, &blk_npt, &blk_lds)) {
       const int64_t nr = K * dout;
       int* d_lp = nullptr; T* d_a = nullptr; T* d_b = nullptr; unsigned char* d_ro = nullptr; int* d_xrow = nullptr; T* d_xalpha = nullptr;
       if ((*rc = dmalloc(&d_lp, nr * 4)) != SSN_OK) return true;
@@ -1185,7 +1265,7 @@ struct Sim final : ssn_sim {
       fused_core = fused_block = true;
       // (only worth anything with a kernel built with SSN_BLOCK_SKIP = 1 or 2 - both measured slower than the plain loop, round 4 -
       //  so the neuron order is the caller's unless SSN_BLOCK_SORT=1 asks for the slot order)
-      if (sizeof(T) == 4 && split_P == 1 && getenv("SSN_BLOCK_SORT") && atoi(getenv("SSN_BLOCK_SORT")) == 1)
+      if (sizeof(T) == 4 && split_P == 1 && opt.block_sort)
         *rc = reorder_block_neurons(m, eo, blk_npt == 2 ? blk_threads : blk_tpb, blk_npt);
       return true;
     }
@@ -1258,7 +1338,7 @@ struct Sim final : ssn_sim {
 
   int plan(const ssn_model_desc* m) {
     int frc = SSN_OK;
-    const bool fused = !(flags & 1) && try_fused_core(m, &frc);
+    const bool fused = !opt.has(SSN_PLAN_NO_FUSED_CORE) && try_fused_core(m, &frc);
     CHK(frc);
     std::vector<std::vector<MOp>> programs;   // programs in step order
     std::vector<int> item_prog;               // for IT_PROGRAM items: index into programs
@@ -1339,7 +1419,7 @@ struct Sim final : ssn_sim {
       struct LevelTag { std::vector<Item>& v; size_t from; int level; ~LevelTag() { for (size_t q = from; q < v.size(); ++q) if (v[q].type != IT_PROGRAM && v[q].level < 0) v[q].level = level; } }
           level_tag{items, items_before, o.level};
       if (o.stage == 1 && !fused && !pending_reduce.empty() &&
-          !(o.kind == SSN_OP_MATVEC && !is_micro(o) && bufs[o.i[4]].transposed && !(flags & 4096)))
+          !(o.kind == SSN_OP_MATVEC && !is_micro(o) && bufs[o.i[4]].transposed && !opt.has(SSN_PLAN_NO_ITEM_BATCH)))
         drain_reduces();
       if (o.stage != 1) {
         ssn::BatchOp<T> b{};
@@ -1403,8 +1483,8 @@ struct Sim final : ssn_sim {
           //  in-register radix-8 passes of round 3 (38.5 us with generic radix-16 butterflies) against ~7 us for its 26 MB matrix
           //  spread over the chip - measured on config 5: 266 us per timestep with the matrices, 288 - 295 with the FFT as a body
           //  of the round grid; the matrix is used for such a length unless flag 268435456 asks for the FFT)
-          if (o.i[6] && sizeof(T) == 4 && !(flags & 512) && plan_dft(o, &da) == SSN_OK && da.N &&
-              (da.M < 2048 || (flags & 268435456))) {
+          if (o.i[6] && sizeof(T) == 4 && !opt.has(SSN_PLAN_NO_FFT) && plan_dft(o, &da) == SSN_OK && da.N &&
+              (da.M < 2048 || opt.has(SSN_PLAN_BLUESTEIN_FFT))) {
             // the matrix is a real-DFT map of a circular-convolution network: mixed-radix FFT instead of a GEMV
             flush();
             Item it; it.type = IT_DFT; it.dft = da;
@@ -1424,7 +1504,7 @@ struct Sim final : ssn_sim {
             int seg = 0;
             if (std::find(seg_spikes.begin(), seg_spikes.end(), o.i[1]) != seg_spikes.end()) {
               const int n_seg = ((int)o.i[3] + 255) / 256;       // segments of 256 neurons, ~32 chunks
-              const int max_chunks = getenv("SSN_SPMV_MAX_CHUNKS") ? std::max(1, atoi(getenv("SSN_SPMV_MAX_CHUNKS"))) : 64;      // (A/B knob)
+              const int max_chunks = std::max(1, opt.spmv_max_chunks);      // (A/B knob)
               seg = std::max(1, (n_seg + max_chunks - 1) / max_chunks);
               chunks = (n_seg + seg - 1) / seg;
             }
@@ -1461,7 +1541,7 @@ struct Sim final : ssn_sim {
           const int64_t units = (int64_t)a.K * a.n;
           if (units > best_units) { best_units = units; best_item = (int)items.size(); }
           host_idx.push_back({bufs[o.i[8]].d, {(const int32_t*)m->buffers[o.i[8]].data, (int64_t)a.K * a.dout}});
-          if (a.P == 1 && !(flags & 8192)) {
+          if (a.P == 1 && !opt.has(SSN_PLAN_ENS_PARTIALS)) {
             // one workgroup covers a whole ensemble (the 8128 product ensembles of 50 neurons): it writes the decoded
             // rows itself, no finish operator (and no program launch) behind the kernel
             a.direct = 1; a.didx = (const int*)bufs[o.i[8]].d; a.sig_w = sig;
@@ -1485,7 +1565,7 @@ struct Sim final : ssn_sim {
             const ssn_op_desc& q = m->ops[j];
             if (q.kind == SSN_OP_MATVEC && q.stage == 1 && q.i[1] == o.i[1] && q.i[3] == o.i[2] && bufs[q.i[4]].transposed) feeds_sparse = true;
           }
-          if (feeds_sparse && !(flags & 1024)) {
+          if (feeds_sparse && !opt.has(SSN_PLAN_SPMV_OWN_LIST)) {
             // segmented spike list: every 256-neuron workgroup of k_neurons leaves its spikes as an ordered index list
             const int n_seg = ((int)o.i[2] + 255) / 256;
             CHK(dmalloc(&it.list, (int64_t)n_seg * 256 * 4));
@@ -1522,20 +1602,18 @@ struct Sim final : ssn_sim {
           // similarities S @ x into a scratch vector (k_matvec), then argmax + row gather in the next program
           flush();
           const Buf& w = bufs[o.i[4]];
-          const char* gmin = getenv("SSN_GRID_MIN_MB");
-          const int64_t grid_min_bytes = (gmin ? atoll(gmin) : 64) << 20;
-          bool grid_route = sizeof(T) == 4 && o.i[5] > 0 && !(flags & 524288) && o.i[2] * o.i[3] * (int64_t)sizeof(T) >= grid_min_bytes;
+          const int64_t grid_min_bytes = opt.grid_min_mb << 20;
+          bool grid_route = sizeof(T) == 4 && o.i[5] > 0 && !opt.has(SSN_PLAN_NO_FACTORED_GRID) && o.i[2] * o.i[3] * (int64_t)sizeof(T) >= grid_min_bytes;
           // Round 4: a smaller grid (2-D, 10^4 rows: 40 MB of HBM stream per timestep at d = 1015) also goes through its factor
           // tables when the step runs as rounds - as bodies of the round grid (no MFMA product: 10^4 dot products of length 2K
           // from two L2-resident 100 x 2K tables), so nothing is launched on its own.  SSN_GRID_DOT_MIN_MB moves the threshold.
-          const char* dmin = getenv("SSN_GRID_DOT_MIN_MB");
-          const bool grid_dot = !grid_route && sizeof(T) == 4 && o.i[5] > 0 && !(flags & (524288 | 2097152)) && o.i[2] < 65536 &&
+          const bool grid_dot = !grid_route && sizeof(T) == 4 && o.i[5] > 0 && !(opt.flags & (SSN_PLAN_NO_FACTORED_GRID | SSN_PLAN_NO_ROUNDS)) && o.i[2] < 65536 &&
                                 o.i[10] * (int64_t)sizeof(T) <= 48 * 1024 &&
-                                o.i[2] * o.i[3] * (int64_t)sizeof(T) >= ((dmin ? atoll(dmin) : 16) << 20);
+                                o.i[2] * o.i[3] * (int64_t)sizeof(T) >= (opt.grid_dot_min_mb << 20);
           grid_route = grid_route || grid_dot;
           // K-split of the grid product (partial products summed by the argmax's first stage): enough workgroups to hide latency
           int gsplit = grid_route && o.i[2] >= 65536 ? (int)std::min<int64_t>(4, std::max<int64_t>(1, o.i[10] / 448)) : 1;
-          if (grid_route && o.i[2] >= 65536 && getenv("SSN_GRID_SPLIT")) gsplit = std::max(1, std::min(8, atoi(getenv("SSN_GRID_SPLIT"))));
+          if (grid_route && o.i[2] >= 65536 && opt.grid_split != PlanOptions::UNSET) gsplit = std::max(1, std::min(8, opt.grid_split));
           for (int it2 = 0; it2 < 4; ++it2) {            // the split count the launcher's 32-column slabs actually produce
             const int kper = (((int)o.i[10] + gsplit - 1) / gsplit + 31) / 32 * 32;
             gsplit = ((int)o.i[10] + kper - 1) / kper;
@@ -1637,7 +1715,7 @@ struct Sim final : ssn_sim {
       dom_units = (int64_t)a.K * a.n;
       dom_bytes = (double)dom_units * (a.din + a.dout + 5) * sizeof(T);
     }
-    round_mode = !fused && !(flags & 2097152);
+    round_mode = !fused && !opt.has(SSN_PLAN_NO_ROUNDS);
     if (round_mode) {
       CHK(build_rounds(programs, item_prog));
       int n_core = 0;
@@ -1753,8 +1831,8 @@ struct Sim final : ssn_sim {
     core_empty = bsig && n_core_ops == 0 && !core_probe;
     if (core_empty) launches_per_step = 0;
     if (!fused) analyse_dependencies(programs, item_prog);
-    if (!fused && !(flags & (256 | 4096))) merge_adjacent_items();
-    if (getenv("SSN_DEBUG_PLAN")) {
+    if (!fused && !opt.has(SSN_PLAN_NO_ITEM_BATCH)) merge_adjacent_items();
+    if (opt.debug_plan) {
       int pj = 0;
       for (size_t i = 0; i < items.size(); ++i) {
         if (items[i].type != IT_PROGRAM) { fprintf(stderr, "[ssn] plan item %2zu type %d rows %d cols %d n %d\n", i, items[i].type, items[i].rows, items[i].cols, items[i].n); continue; }
@@ -1781,17 +1859,16 @@ struct Sim final : ssn_sim {
 
   // k_round body of an ensemble array (-1: its variant has none, it is launched on its own)
   int ens_round_kind(const ssn::EnsArgs<T>& a) const {
-    if ((a.defer && a.defer != 2) || a.xrows || (flags & 4194304)) return -1;
+    if (a.defer || a.xrows || opt.has(SSN_PLAN_ENS_OWN_LAUNCH)) return -1;
     if (a.fast == 1 && a.din == 3 && a.dout == 4) return ssn::RK_ENS_3_4_S;
     if (a.fast == 1 && a.din == 3 && a.dout == 5) return ssn::RK_ENS_3_5_S;
     if (a.fast == 2 && a.din == 1 && a.dout == 1) {
       // many small ensembles (the product arrays of a circular convolution): a wave per ensemble instead of a workgroup
-      if (a.n <= 64 && a.P == 1 && a.direct && !no_small_ens) return ssn::RK_ENS_SMALL;
+      if (a.n <= 64 && a.P == 1 && a.direct && opt.small_ens) return ssn::RK_ENS_SMALL;
       return ssn::RK_ENS_1_1_D;
     }
     return -1;
   }
-  const bool no_small_ens = getenv("SSN_SMALL_ENS") && atoi(getenv("SSN_SMALL_ENS")) == 0;      // A/B knob
   // blocks of an ensemble array's grid inside a round
   int ens_round_blocks(const ssn::EnsArgs<T>& a) const {
     return ens_round_kind(a) == ssn::RK_ENS_SMALL ? (a.K + 4 * ssn::ENS_SMALL_PER_WAVE - 1) / (4 * ssn::ENS_SMALL_PER_WAVE) : a.K * a.P;
@@ -1805,17 +1882,12 @@ struct Sim final : ssn_sim {
   //  1.3 % of the filtered activities are nonzero - SSN_COST_PES / SSN_COST_VOJA for A/B runs)
   // tallest matrix that runs four rows per workgroup with four vectors of a row in flight per lane (one trip for 1015 columns)
   // instead of sixteen rows per workgroup with one vector of four rows in flight (four trips)
-  int matvec_r1_max = getenv("SSN_MATVEC_R1_MAX") ? atoi(getenv("SSN_MATVEC_R1_MAX")) : 4096;
-  double cost_pes = getenv("SSN_COST_PES") ? atof(getenv("SSN_COST_PES")) : 2.0;
-  double cost_voja = getenv("SSN_COST_VOJA") ? atof(getenv("SSN_COST_VOJA")) : 0.2;
-  double lat_dft = getenv("SSN_LAT_DFT") ? atof(getenv("SSN_LAT_DFT")) : 9.0;
-  double lat_solo = getenv("SSN_LAT_SOLO") ? atof(getenv("SSN_LAT_SOLO")) : 3.0;
   void unit_cost(int mop, int item, double* us, double* lat, int* blocks) const {
     *us = 0.0; *lat = 0.0; *blocks = 0;
     const double per_us = 5.0e6;      // bytes per microsecond
     if (mop >= 0) {
       const MOp& op = mops[(size_t)mop];
-      if (op.kind == ssn::M_GATE || op.kind == ssn::M_ARGMAX_GATHER) *lat = lat_solo;
+      if (op.kind == ssn::M_GATE || op.kind == ssn::M_ARGMAX_GATHER) *lat = opt.lat_solo;
       else *us = (double)op.len * 3.0 * sizeof(T) / per_us;
       return;
     }
@@ -1827,14 +1899,14 @@ struct Sim final : ssn_sim {
         break;
       case IT_MATVEC:
         *us = (double)it.rows * it.ld * sizeof(T) / per_us;
-        if ((size_t)it.cols * sizeof(T) <= 48 * 1024) *blocks = it.rows <= matvec_r1_max ? (it.rows + 3) / 4 : (it.rows + 15) / 16;
+        if ((size_t)it.cols * sizeof(T) <= 48 * 1024) *blocks = it.rows <= opt.matvec_r1_max ? (it.rows + 3) / 4 : (it.rows + 15) / 16;
         break;
-      case IT_PES: *us = cost_pes * it.rows * it.ld * sizeof(T) / per_us; *blocks = ((it.cols + 1023) / 1024) * ((it.rows + ssn::PES_ROWS - 1) / ssn::PES_ROWS); break;
-      case IT_VOJA: *us = cost_voja * it.rows * it.ld * sizeof(T) / per_us; break;
+      case IT_PES: *us = opt.cost_pes * it.rows * it.ld * sizeof(T) / per_us; *blocks = ((it.cols + 1023) / 1024) * ((it.rows + ssn::PES_ROWS - 1) / ssn::PES_ROWS); break;
+      case IT_VOJA: *us = opt.cost_voja * it.rows * it.ld * sizeof(T) / per_us; break;
       case IT_SPMV: *us = 0.1 * (double)it.cols * it.ld * sizeof(T) / per_us; break;
       case IT_NEURONS: *us = (double)it.n * 5.0 * sizeof(T) / per_us; break;
       case IT_MATVEC_NEURONS: *us = (double)it.rows * it.ld * sizeof(T) / per_us; *blocks = (it.rows + 15) / 16; break;
-      case IT_DFT: *lat = lat_dft; break;
+      case IT_DFT: *lat = opt.lat_dft; break;
       default: *us = 1.0; break;
     }
   }
@@ -1898,7 +1970,7 @@ struct Sim final : ssn_sim {
       }
     }
     all.insert(all.end(), extra.begin(), extra.end());
-    if (getenv("SSN_DEBUG_PLAN")) {          // what the balancer believes the rounds cost (us): bandwidth-bound load | longest single-workgroup body
+    if (opt.debug_plan) {          // what the balancer believes the rounds cost (us): bandwidth-bound load | longest single-workgroup body
       fprintf(stderr, "[ssn] balanced rounds (load | latency, us):");
       double total = 0.0;
       for (int r = 0; r < nr; ++r) { fprintf(stderr, " %.0f|%.0f", load[(size_t)r], lat[(size_t)r]); total += std::max(load[(size_t)r], lat[(size_t)r]); }
@@ -1906,807 +1978,705 @@ struct Sim final : ssn_sim {
     }
   }
 
-  // Round plan, recurrent ensemble arrays (the SLAM network's oscillators, reference pathintegration.py:180-182: ensemble k ->
-  // Lowpass -> ensemble k).  As separate operators the recurrence costs four dependent rounds per timestep: array (partial sums
-  // per 1024-neuron chunk) -> M_ENS_FINISH (sums) -> M_LOWPASS (filter state) -> M_LINCOMB (input) -> array.  When every input
-  // element of the array takes its recurrent term from a filter fed by a decoded row of the SAME ensemble - the proof
-  // try_fused_core makes for the whole-block kernel, here on the micro-operators of the round plan - the array does it all in
-  // its prologue (ens_body, defer == 2): the filter and the recurrent term of the lincomb leave the plan, the finish stays for
-  // the other readers of the decoded rows (the to_SSP read-out).
-  std::vector<std::pair<void*, size_t>> zero_on_reset;      // scratch that holds state across timesteps (partial sums, filter states)
-  int fold_recurrent_filter(std::vector<std::vector<MOp>>& programs, const std::vector<int>& item_prog) {
-    for (size_t ei = 0; ei < items.size(); ++ei) {
-      Item& E = items[ei];
-      if (E.type != IT_ENS || E.ens.direct || E.ens.defer || E.ens.xrows || E.ens.P < 2 || ens_round_kind(E.ens) < 0) continue;
-      ssn::EnsArgs<T>& a = E.ens;
-      const int64_t K = a.K, din = a.din, dout = a.dout;
-      // the finish operator and the host copy of the destination indices
-      MOp* F = nullptr;
-      for (auto& pr : programs) for (MOp& op : pr) if (op.kind == ssn::M_ENS_FINISH && op.p0 == (const void*)a.partials) F = &op;
-      if (!F) continue;
-      const int32_t* didx = nullptr;
-      for (auto& h : host_idx) if (h.first == F->p1 && h.second.second == K * dout) didx = h.second.first;
-      if (!didx) continue;
-      std::map<long long, int> row_of;                          // decoded signal -> row index k * dout + r
-      for (int64_t j = 0; j < K * dout; ++j) row_of[didx[j]] = (int)j;
-      // filters fed by decoded rows of this array whose state is read by lincombs into the array's input range only
-      const long long x0 = a.x_off, x1 = a.x_off + K * din;
-      std::vector<int> xrow((size_t)(K * din), -1);
-      std::vector<double> xalpha((size_t)(K * din), 0.0), lpa((size_t)(K * dout), 0.0), lpb((size_t)(K * dout), 0.0);
-      struct Hit { size_t prog, op; };
-      std::vector<Hit> filters;
-      std::vector<std::pair<Hit, size_t>> terms;                // (lincomb, term index) to remove
-      bool ok = true;
-      for (size_t pi = 0; pi < programs.size() && ok; ++pi)
-        for (size_t oi = 0; oi < programs[pi].size() && ok; ++oi) {
-          const MOp& L = programs[pi][oi];
-          if (L.kind != ssn::M_LOWPASS) continue;
-          bool fed = false, foreign = false;
-          for (long long q = 0; q < L.len; ++q) { if (row_of.count(L.src + q)) fed = true; }
-          if (!fed) continue;
-          // every reader of the state range must be a lincomb into [x0, x1) with the state as one of its terms, element for element
-          std::vector<std::pair<Hit, size_t>> my_terms;
-          for (size_t pj = 0; pj < programs.size() && !foreign; ++pj)
-            for (size_t oj = 0; oj < programs[pj].size() && !foreign; ++oj) {
-              const MOp& X = programs[pj][oj];
-              if (&X == &L) continue;
-              std::vector<Rng> acc;
-              micro_access(acc, X, false);
-              bool touches = false;
-              for (const Rng& r : acc) if (r.space == (const void*)sig && r.lo < L.dst + L.len && L.dst < r.hi) touches = true;
-              if (!touches) continue;
-              if (X.kind != ssn::M_LINCOMB || X.dst < x0 || X.dst + X.len > x1) { foreign = true; break; }
-              auto lt = lin_terms.find(X.p0);
-              if (lt == lin_terms.end()) { foreign = true; break; }
-              for (size_t t = 0; t < lt->second.size(); ++t) {
-                const long long ts = lt->second[t].src;
-                if (ts + X.len <= L.dst || L.dst + L.len <= ts) continue;
-                if (ts < L.dst || ts + X.len > L.dst + L.len) { foreign = true; break; }
-                my_terms.push_back({Hit{pj, oj}, t});
-              }
-            }
-          for (auto& it2 : items) if (it2.type != IT_PROGRAM) { std::vector<Rng> acc; item_access(acc, it2); for (const Rng& r : acc) if (r.space == (const void*)sig && r.lo < L.dst + L.len && L.dst < r.hi) foreign = true; }
-          for (auto& pb : probes) if (pb.src < L.dst + L.len && L.dst < pb.src + pb.width) foreign = true;
-          if (foreign || my_terms.empty()) continue;             // somebody else needs this state: it stays an operator
-          for (long long q = 0; q < L.len && ok; ++q) if (sig_init[(size_t)(L.dst + q)] != 0.0) ok = false;      // (x of the first timestep uses the state as it stands)
-          // map every input element to the row that feeds it
-          for (auto& mt : my_terms) {
-            const MOp& X = programs[mt.first.prog][mt.first.op];
-            const auto& tt = lin_terms[X.p0][mt.second];
-            for (long long q = 0; q < X.len && ok; ++q) {
-              const long long e = X.dst + q - x0, st = tt.src + q;
-              auto f = row_of.find(L.src + (st - L.dst));
-              if (f == row_of.end()) continue;                   // a state no row feeds (dropped all-zero decoder row): stays 0
-              if (f->second / dout != e / din || xrow[(size_t)e] >= 0) { ok = false; break; }
-              xrow[(size_t)e] = (int)(f->second % dout); xalpha[(size_t)e] = (double)tt.alpha * (double)X.b;
-              lpa[(size_t)f->second] = (double)L.a; lpb[(size_t)f->second] = (double)L.b;
-            }
-            terms.push_back(mt);
-          }
-          filters.push_back(Hit{pi, oi});
-        }
-      if (!ok || filters.empty()) continue;
-      // device tables, the second set of partial sums, the filter states
-      const int64_t nr = K * dout, ps = (int64_t)K * a.P * dout;
-      int* d_xrow = nullptr; T* d_xalpha = nullptr; T* d_a = nullptr; T* d_b = nullptr; T* d_f = nullptr; T* d_part = nullptr;
-      CHK(dmalloc(&d_xrow, K * din * 4)); CHK(dmalloc(&d_xalpha, K * din * (int64_t)sizeof(T)));
-      CHK(dmalloc(&d_a, nr * (int64_t)sizeof(T))); CHK(dmalloc(&d_b, nr * (int64_t)sizeof(T)));
-      CHK(dmalloc(&d_f, 2 * nr * (int64_t)sizeof(T))); CHK(dmalloc(&d_part, 2 * ps * (int64_t)sizeof(T)));
-      for (void* q : {(void*)d_xrow, (void*)d_xalpha, (void*)d_a, (void*)d_b, (void*)d_f}) scratch_bufs.push_back(q);
-      HIPCHK(hipMemcpy(d_xrow, xrow.data(), (size_t)(K * din) * 4, hipMemcpyHostToDevice));
-      CHK(upload(xalpha.data(), d_xalpha, 1, K * din, K * din));
-      CHK(upload(lpa.data(), d_a, 1, nr, nr)); CHK(upload(lpb.data(), d_b, 1, nr, nr));
-      HIPCHK(hipMemset(d_f, 0, (size_t)(2 * nr) * sizeof(T))); HIPCHK(hipMemset(d_part, 0, (size_t)(2 * ps) * sizeof(T)));
-      zero_on_reset.push_back({(void*)d_f, (size_t)(2 * nr) * sizeof(T)}); zero_on_reset.push_back({(void*)d_part, (size_t)(2 * ps) * sizeof(T)});
-      hipFree(a.partials);                                      // (the single set planned before; ~Sim frees the new one through the item)
-      F->p0 = d_part; F->src = ps;
-      a.partials = d_part; a.partials_stride = ps; a.defer = 2; a.sub = 0;
-      a.xrow = d_xrow; a.xalpha = d_xalpha; a.lp_a = d_a; a.lp_b = d_b; a.fstate = d_f;
-      // the recurrent terms leave their lincombs (new term lists), the filters leave the plan
-      std::map<const void*, std::vector<size_t>> drop;          // lincomb term list -> term indices to drop
-      for (auto& mt : terms) drop[programs[mt.first.prog][mt.first.op].p0].push_back(mt.second);
-      for (auto& pr : programs)
-        for (MOp& op : pr) {
-          if (op.kind != ssn::M_LINCOMB) continue;
-          auto d = drop.find(op.p0);
-          if (d == drop.end()) continue;
-          std::vector<ssn::LinTerm<T>> tt;
-          const auto& old = lin_terms[op.p0];
-          for (size_t t = 0; t < old.size(); ++t) if (std::find(d->second.begin(), d->second.end(), t) == d->second.end()) tt.push_back(old[t]);
-          ssn::LinTerm<T>* d_terms = nullptr;
-          CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, tt.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
-          scratch_bufs.push_back(d_terms);
-          if (!tt.empty()) HIPCHK(hipMemcpy(d_terms, tt.data(), tt.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
-          lin_terms[(const void*)d_terms] = tt;
-          op.p0 = d_terms; op.i0 = (long long)tt.size();
-        }
-      std::sort(filters.begin(), filters.end(), [](const Hit& x, const Hit& y) { return x.prog != y.prog ? x.prog > y.prog : x.op > y.op; });
-      for (const Hit& h : filters) programs[h.prog].erase(programs[h.prog].begin() + (long)h.op);
-      if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, "[ssn] recurrent array of %lld ensembles completes its own previous timestep: %zu filter operator(s) and %zu lincomb term(s) folded\n", (long long)K, filters.size(), terms.size());
+  // ---- build_rounds: its working state and its steps, in the order the driver at the end calls them ----------------------
+  struct Unit { int mop = -1; int item = -1; int phase = 0; bool writes = false; std::vector<Rng> acc; };
+  // One instance of a unit: (unit, timestep offset inside the launch sequence, round).
+  struct Inst { int unit; int sub; int round; int lo = 0; int cnt = -1; int chain = -1; bool solo = false; };      // blocks [lo, lo + cnt) of the unit's grid (cnt < 0: all); solo: member of a serial chain
+  struct Fix { size_t rl; int entry; int what; size_t off; };     // what: 0 arena, 1 glue map, 2 micro-operator, 3 chain table
+  typedef std::vector<std::vector<Rng>> AccLists;      // access list per unit
+  typedef std::vector<std::vector<int>> Chains;        // members (indices into the instance list) per chain
+  struct SeqOp { int item; int prog; int op; std::vector<Rng> acc; };      // an operator in program order (prog / op: -1 for a big operator)
+  struct RoundBuild {
+    std::vector<Unit> units;
+    std::vector<ssn::GlueBlock> glue_map;      // block -> (operator, chunk) of the glue entries
+    std::vector<unsigned char> arena;          // body arguments of the big operators
+    std::vector<long long> unit_arg;           // arena offset of a big operator's body arguments (shared by its instances)
+    std::vector<Fix> fixes;                    // device pointers the round entries get once the tables are uploaded
+    std::vector<int> chain_tab;
+    size_t put(const void* src, size_t bytes) { const size_t off = (arena.size() + 15) / 16 * 16; arena.resize(off + bytes); memcpy(arena.data() + off, src, bytes); return off; }
+  };
+
+  // accesses of every operator in program order (the rewrite passes below and the cuts scan this list)
+  std::vector<SeqOp> program_order(const std::vector<std::vector<MOp>>& programs, const std::vector<int>& item_prog) const {
+    std::vector<SeqOp> seq;
+    int pj = 0;
+    for (size_t i = 0; i < items.size(); ++i) {
+      if (items[i].type == IT_PROGRAM) {
+        const int pr = item_prog[(size_t)pj++];
+        for (size_t q = 0; q < programs[(size_t)pr].size(); ++q) { seq.push_back(SeqOp{(int)i, pr, (int)q, {}}); micro_access(seq.back().acc, programs[(size_t)pr][q], false); }
+      } else {
+        seq.push_back(SeqOp{(int)i, -1, -1, {}});
+        item_access(seq.back().acc, items[i]);
+      }
     }
-    (void)item_prog;
+    return seq;
+  }
+
+  // Round 4: the critical recurrence of a SLAM timestep - memory spikes -> sparse decode -> PES (may not touch W before the
+  // decode has read it) -> filter of the activities PES reads (may not run before PES) -> next timestep's spikes (may not
+  // overwrite what that filter reads) - is four rounds of WAR hazards.  The filter update folded into the PES body (the
+  // workgroup that has read row r's factor advances it) takes one of them out.  Round 2 measured this fold slower because the
+  // oscillators' own four-round recurrence kept the period at four.  SSN_PES_FOLD=0: off.
+  // The filter update follows the rule in program order (reads before updates); nothing between the two may touch the filter's state
+  // or write its input, or the update could not move up to the rule.
+  void fold_pes_filters(std::vector<std::vector<MOp>>& programs, const std::vector<int>& item_prog) {
+    if (!((!phased || opt.phased_pes_fold) && opt.pes_fold)) return;
+    for (size_t i = 0; i < items.size(); ++i) {
+      Item& pe = items[i];
+      if (pe.type != IT_PES || pe.cols > 1024 || !(pe.aux0 >= sig && pe.aux0 < sig + n_sig)) continue;
+      const long long f0 = pe.aux0 - sig;
+      const std::vector<SeqOp> seq = program_order(programs, item_prog);
+      size_t at = 0;
+      while (seq[at].item != (int)i) ++at;
+      for (size_t e = at + 1; e < seq.size(); ++e) {
+        if (seq[e].prog < 0) continue;
+        std::vector<MOp>& pr = programs[(size_t)seq[e].prog];
+        const MOp& lp = pr[(size_t)seq[e].op];
+        if (!(lp.kind == ssn::M_LOWPASS && lp.dst == f0 && lp.len == pe.rows)) continue;
+        bool clear = true;
+        for (size_t v = at + 1; v < e && clear; ++v) clear = !hazard(seq[v].acc, seq[e].acc);
+        if (clear) {
+          pe.lp_dst = sig + lp.dst; pe.lp_src = sig + lp.src; pe.lp_a = lp.a; pe.lp_b = lp.b;
+          pr.erase(pr.begin() + seq[e].op);
+        }
+        break;
+      }
+    }
+  }
+
+  // Round 4: the neuron update of a dense population in the epilogue of its encoder product.  A population hop is four
+  // dependent rounds - product (J += W x) -> neurons -> sparse decode over the spike list -> reduction (+ filter) - and a
+  // neuron-sharded timestep adds the exchange and the filter behind it: six rounds between two exchanges.  Where the product is
+  // the last writer of the current vector J before the neurons, nothing else ever reads J, and nothing between the two touches
+  // the product's operands, the workgroup that owns 16 rows steps their 16 neurons itself (matvec_neurons_body).  The fused
+  // operator takes the neurons' place in program order (whatever reads the previous timestep's spikes between the two still
+  // comes first).  SSN_FUSE_NEURONS=0: off.
+  int fuse_product_neurons(const std::vector<std::vector<MOp>>& programs, const std::vector<int>& item_prog) {
+    if (!opt.fuse_neurons) return SSN_OK;
+    const std::vector<SeqOp> seq = program_order(programs, item_prog);
+    for (size_t jn = 0; jn < items.size(); ++jn) {
+      Item& N = items[jn];
+      if (N.type != IT_NEURONS || !(N.src >= sig && N.src < sig + n_sig)) continue;
+      const int64_t j0 = N.src - sig, j1 = j0 + N.n;
+      int jm = -1;
+      for (size_t j = 0; j < jn; ++j)
+        if (items[j].type == IT_MATVEC && items[j].dst == N.src && items[j].rows == N.n) jm = (int)j;
+      if (jm < 0) continue;
+      const Item& M = items[(size_t)jm];
+      // (smaller populations keep the four-rows-per-workgroup product, which fills more of the chip; SSN_FUSE_MIN_ROWS for tests)
+      if ((size_t)M.cols * sizeof(T) > 48 * 1024 || M.rows < opt.fuse_min_rows || M.phase != N.phase) continue;
+      std::vector<Rng> accM;
+      item_access(accM, M);
+      bool ok = true;
+      for (const auto& e : seq) {
+        if (e.item == jm || e.item == (int)jn) continue;
+        for (const Rng& r : e.acc) {
+          if (r.space != (const void*)sig || r.lo >= j1 || j0 >= r.hi) continue;
+          if (!r.w) ok = false;                                        // another reader of J
+          else if (e.item > jm && e.item < (int)jn) ok = false;      // another writer between the product and the neurons
+          else if (e.item > (int)jn) ok = false;                      // (a writer behind the neurons: not the pattern)
+        }
+        if (e.item > jm && e.item < (int)jn && hazard(e.acc, accM)) ok = false;      // the product's operands change on the way
+        if (!ok) break;
+      }
+      if (!ok) continue;
+      if (N.list) {                        // spike list in 16-neuron segments: counts per small segment, the spans of the products stay
+        int* cnt = nullptr;
+        const int n_small = (N.n + 15) / 16;
+        CHK(dmalloc(&cnt, (int64_t)n_small * 4 + 64));
+        HIPCHK(hipMemset(cnt, 0, (size_t)n_small * 4 + 64));
+        scratch_bufs.push_back(cnt);
+        for (Item& sp : items) if (sp.type == IT_SPMV && sp.list == N.list) { sp.count = cnt; sp.seg_len = 16; }
+        N.count = cnt;
+      }
+      N.type = IT_MATVEC_NEURONS;
+      N.Wm = M.Wm; N.aux0 = M.src; N.rows = M.rows; N.cols = M.cols; N.ld = M.ld; N.set = M.set;
+      items[(size_t)jm].type = IT_NONE;
+      n_fused_populations += 1;
+      if (opt.debug_plan) fprintf(stderr, "[ssn] encoder product %d x %d and the update of its %d neurons fused (items %d, %zu)\n", N.rows, N.cols, N.n, jm, jn);
+    }
     return SSN_OK;
   }
 
-  int build_rounds(const std::vector<std::vector<MOp>>& programs_in, const std::vector<int>& item_prog) {
-    struct Unit { int mop = -1; int item = -1; int phase = 0; bool writes = false; std::vector<Rng> acc; };
-    std::vector<Unit> units;
-    mops.clear();
-    std::vector<std::vector<MOp>> programs = programs_in;
-    // Round 4: the critical recurrence of a SLAM timestep - memory spikes -> sparse decode -> PES (may not touch W before the
-    // decode has read it) -> filter of the activities PES reads (may not run before PES) -> next timestep's spikes (may not
-    // overwrite what that filter reads) - is four rounds of WAR hazards.  The filter update folded into the PES body (the
-    // workgroup that has read row r's factor advances it) takes one of them out.  Round 2 measured this fold slower because the
-    // oscillators' own four-round recurrence kept the period at four; it pays together with the oscillator array completing
-    // its previous timestep itself (below).  SSN_PES_FOLD=0: off.
-    if ((!phased || (getenv("SSN_PHASED_PES_FOLD") && atoi(getenv("SSN_PHASED_PES_FOLD")) == 1)) && !(getenv("SSN_PES_FOLD") && atoi(getenv("SSN_PES_FOLD")) == 0))
-      for (size_t i = 0; i < items.size(); ++i) {
-        Item& pe = items[i];
-        if (pe.type != IT_PES || pe.cols > 1024 || !(pe.aux0 >= sig && pe.aux0 < sig + n_sig)) continue;
-        const long long f0 = pe.aux0 - sig;
-        bool done = false;
-        int pj = 0;
-        for (size_t j = 0; j < items.size() && !done; ++j) {
-          if (items[j].type != IT_PROGRAM) continue;
-          std::vector<MOp>& pr = programs[(size_t)item_prog[(size_t)pj++]];
-          if (j < i) continue;                                  // (the filter update follows the rule in program order: reads before updates)
-          for (size_t q = 0; q < pr.size(); ++q)
-            if (pr[q].kind == ssn::M_LOWPASS && pr[q].dst == f0 && pr[q].len == pe.rows) {
-              pe.lp_dst = sig + pr[q].dst; pe.lp_src = sig + pr[q].src; pe.lp_a = pr[q].a; pe.lp_b = pr[q].b;
-              pr.erase(pr.begin() + (long)q);
-              done = true;
-              break;
-            }
-        }
-      }
-    // Round 4: the neuron update of a dense population in the epilogue of its encoder product.  A population hop is four
-    // dependent rounds - product (J += W x) -> neurons -> sparse decode over the spike list -> reduction (+ filter) - and a
-    // neuron-sharded timestep adds the exchange and the filter behind it: six rounds between two exchanges.  Where the product is
-    // the last writer of the current vector J before the neurons, nothing else ever reads J, and nothing between the two touches
-    // the product's operands, the workgroup that owns 16 rows steps their 16 neurons itself (matvec_neurons_body).  The fused
-    // operator takes the neurons' place in program order (whatever reads the previous timestep's spikes between the two still
-    // comes first).  SSN_FUSE_NEURONS=0: off.
-    if (!(getenv("SSN_FUSE_NEURONS") && atoi(getenv("SSN_FUSE_NEURONS")) == 0)) {
-      // accesses of every operator in program order: (item index, accesses)
-      std::vector<std::pair<int, std::vector<Rng>>> seq;
-      {
-        int pj = 0;
-        for (size_t i = 0; i < items.size(); ++i) {
-          if (items[i].type == IT_PROGRAM) {
-            for (const MOp& op : programs[(size_t)item_prog[(size_t)pj]]) { seq.push_back({(int)i, {}}); micro_access(seq.back().second, op, false); }
-            ++pj;
-          } else {
-            seq.push_back({(int)i, {}});
-            item_access(seq.back().second, items[i]);
-          }
-        }
-      }
-      for (size_t jn = 0; jn < items.size(); ++jn) {
-        Item& N = items[jn];
-        if (N.type != IT_NEURONS || !(N.src >= sig && N.src < sig + n_sig)) continue;
-        const int64_t j0 = N.src - sig, j1 = j0 + N.n;
-        int jm = -1;
-        for (size_t j = 0; j < jn; ++j)
-          if (items[j].type == IT_MATVEC && items[j].dst == N.src && items[j].rows == N.n) jm = (int)j;
-        if (jm < 0) continue;
-        const Item& M = items[(size_t)jm];
-        // (smaller populations keep the four-rows-per-workgroup product, which fills more of the chip; SSN_FUSE_MIN_ROWS for tests)
-        const int fuse_min_rows = getenv("SSN_FUSE_MIN_ROWS") ? atoi(getenv("SSN_FUSE_MIN_ROWS")) : 4097;
-        if ((size_t)M.cols * sizeof(T) > 48 * 1024 || M.rows < fuse_min_rows || M.phase != N.phase) continue;
-        std::vector<Rng> accM;
-        item_access(accM, M);
-        bool ok = true;
-        for (const auto& e : seq) {
-          if (e.first == jm || e.first == (int)jn) continue;
-          for (const Rng& r : e.second) {
-            if (r.space != (const void*)sig || r.lo >= j1 || j0 >= r.hi) continue;
-            if (!r.w) ok = false;                                        // another reader of J
-            else if (e.first > jm && e.first < (int)jn) ok = false;      // another writer between the product and the neurons
-            else if (e.first > (int)jn) ok = false;                      // (a writer behind the neurons: not the pattern)
-          }
-          if (e.first > jm && e.first < (int)jn && hazard(e.second, accM)) ok = false;      // the product's operands change on the way
-          if (!ok) break;
-        }
-        if (!ok) continue;
-        if (N.list) {                        // spike list in 16-neuron segments: counts per small segment, the spans of the products stay
-          int* cnt = nullptr;
-          const int n_small = (N.n + 15) / 16;
-          CHK(dmalloc(&cnt, (int64_t)n_small * 4 + 64));
-          HIPCHK(hipMemset(cnt, 0, (size_t)n_small * 4 + 64));
-          scratch_bufs.push_back(cnt);
-          for (Item& sp : items) if (sp.type == IT_SPMV && sp.list == N.list) { sp.count = cnt; sp.seg_len = 16; }
-          N.count = cnt;
-        }
-        N.type = IT_MATVEC_NEURONS;
-        N.Wm = M.Wm; N.aux0 = M.src; N.rows = M.rows; N.cols = M.cols; N.ld = M.ld; N.set = M.set;
-        items[(size_t)jm].type = IT_NONE;
-        n_fused_populations += 1;
-        if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, "[ssn] encoder product %d x %d and the update of its %d neurons fused (items %d, %zu)\n", N.rows, N.cols, N.n, jm, jn);
-      }
-    }
-    // Round 4: the input of an ensemble array assembled by the array itself.  The product ensembles of a circular convolution read
-    // x = alpha_1 A + alpha_2 B of the two transforms' outputs (reference binding.py:297-317); as a lincomb operator of its own that
-    // sum is one more dependent round on the network's long loop, between the transforms and the ensembles.  EnsArgs carries up to
-    // four such terms already (the per-timestep PathIntegration kernel's input assembly): where a lincomb that SETS exactly the
-    // array's input range from at most four terms is the range's only writer, the array its only reader, the range starts at zero and
-    // nothing between the two writes a term's source, the terms move into the array and the operator leaves the plan.
-    // Measured at SLAM config 3 (four lincombs fold, 217 -> 204 rounds per 64 timesteps): 101.5 us per timestep against 100.3 without,
-    // twice on one box - like the transforms in serial chains, fewer rounds on the loop and no gain; opt-in (SSN_FOLD_ENS_INPUT=1).
-    if (getenv("SSN_FOLD_ENS_INPUT") && atoi(getenv("SSN_FOLD_ENS_INPUT")) == 1) {
-      for (size_t ei = 0; ei < items.size(); ++ei) {
-        Item& E = items[ei];
-        if (E.type != IT_ENS || E.ens.n_rec != 0 || E.ens.xrows || E.ens.defer || ens_round_kind(E.ens) < 0) continue;
-        const int64_t x0 = E.ens.x_off, xn = (int64_t)E.ens.K * E.ens.din;
-        // program-order positions: (item index, program, op index)
-        int pj = 0, lp = -1, lo = -1, li = -1;
-        bool ok = true;
-        std::vector<std::pair<int, std::vector<Rng>>> seq;           // (item index, accesses) of every other operator
-        for (size_t i = 0; i < items.size(); ++i) {
-          if (items[i].type == IT_PROGRAM) {
-            const int pr = item_prog[(size_t)pj++];
-            for (size_t q = 0; q < programs[(size_t)pr].size(); ++q) {
-              const MOp& op = programs[(size_t)pr][q];
-              if (op.kind == ssn::M_LINCOMB && op.dst == x0 && op.len == xn && lp < 0 && i < ei) { lp = pr; lo = (int)q; li = (int)i; continue; }
-              seq.push_back({(int)i, {}});
-              micro_access(seq.back().second, op, false);
-            }
-          } else if (i != ei) {
-            seq.push_back({(int)i, {}});
-            item_access(seq.back().second, items[i]);
-          }
-        }
-        if (lp < 0) continue;
-        const MOp L = programs[(size_t)lp][(size_t)lo];
-        auto lt = lin_terms.find(L.p0);
-        if (lt == lin_terms.end() || lt->second.empty() || lt->second.size() > 4 || L.a != T(0) || L.b != T(1) || L.c != T(0)) continue;
-        for (int64_t q = 0; q < xn && ok; ++q) if (sig_init[(size_t)(x0 + q)] != 0.0) ok = false;
-        for (const auto& e : seq) {
-          if (!ok) break;
-          for (const Rng& r : e.second) {
-            if (r.space != (const void*)sig) continue;
-            if (r.lo < x0 + xn && x0 < r.hi) ok = false;                                  // someone else touches the input range
-            if (r.w && e.first >= li && e.first <= (int)ei)
-              for (const auto& t : lt->second) if (r.lo < t.src + xn && t.src < r.hi) ok = false;      // a source changes between the two
-          }
-        }
-        if (!ok) continue;
-        E.ens.n_rec = (int)lt->second.size();
-        for (int j = 0; j < E.ens.n_rec; ++j) {
-          E.ens.rec_dst[j] = x0; E.ens.rec_len[j] = xn; E.ens.rec_src[j] = lt->second[(size_t)j].src; E.ens.rec_alpha[j] = lt->second[(size_t)j].alpha;
-        }
-        programs[(size_t)lp].erase(programs[(size_t)lp].begin() + lo);
-        n_folded_inputs += 1;
-        if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, "[ssn] input lincomb of %d terms folded into ensemble array %zu (K %d)\n", E.ens.n_rec, ei, E.ens.K);
-      }
-    }
-    // Element-wise micro-operators are cut at every range endpoint of the other operators.  The builder merges
-    // neighbouring resets / hand-offs into one long operator (one fill over all accumulators of a network); as a unit
-    // it would inherit the hazards of every signal it spans - the reset of an accumulator that is read in the last
-    // round of step s would hold back the whole head of step s + 1.
+  // Element-wise micro-operators are cut at every range endpoint of the other operators.  The builder merges
+  // neighbouring resets / hand-offs into one long operator (one fill over all accumulators of a network); as a unit
+  // it would inherit the hazards of every signal it spans - the reset of an accumulator that is read in the last
+  // round of step s would hold back the whole head of step s + 1.
+  std::vector<int64_t> range_cuts(const std::vector<std::vector<MOp>>& programs, const std::vector<int>& item_prog) const {
     std::vector<int64_t> cuts;
-    {
-      std::vector<Rng> all_acc;
-      int pj = 0;
-      for (size_t i = 0; i < items.size(); ++i) {
-        if (items[i].type == IT_PROGRAM) { for (const MOp& op : programs[(size_t)item_prog[(size_t)pj]]) micro_access(all_acc, op, false); ++pj; }
-        else item_access(all_acc, items[i]);
-      }
-      for (const Rng& r : all_acc) if (r.space == (const void*)sig) { cuts.push_back(r.lo); cuts.push_back(r.hi); }
-      std::sort(cuts.begin(), cuts.end());
-      cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    for (const SeqOp& e : program_order(programs, item_prog))
+      for (const Rng& r : e.acc) if (r.space == (const void*)sig) { cuts.push_back(r.lo); cuts.push_back(r.hi); }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    return cuts;
+  }
+  int split_micro(const MOp& op, const std::vector<int64_t>& cuts, std::vector<MOp>& out) {
+    const bool ew = op.kind == ssn::M_FILL || op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS ||
+                    op.kind == ssn::M_LINCOMB || op.kind == ssn::M_ROW_IN || op.kind == ssn::M_ROW_OUT;
+    if (!ew || op.len <= 1 || opt.has(SSN_PLAN_NO_CUTS)) { out.push_back(op); return SSN_OK; }
+    std::vector<int64_t> bases;                       // signal-space origins of the operator's operands
+    if (op.kind != ssn::M_ROW_OUT) bases.push_back(op.dst);
+    if (op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS || op.kind == ssn::M_ROW_OUT) bases.push_back(op.src);
+    const std::vector<ssn::LinTerm<T>>* terms = nullptr;
+    if (op.kind == ssn::M_LINCOMB) { auto f = lin_terms.find(op.p0); if (f != lin_terms.end()) { terms = &f->second; for (auto& t : *terms) bases.push_back(t.src); } }
+    std::vector<int64_t> offs{0, op.len};
+    for (int64_t b : bases) {
+      auto lo = std::upper_bound(cuts.begin(), cuts.end(), b), hi = std::lower_bound(cuts.begin(), cuts.end(), b + op.len);
+      for (auto it = lo; it < hi; ++it) offs.push_back(*it - b);
     }
-    auto split_micro = [&](const MOp& op, std::vector<MOp>& out) -> int {
-      const bool ew = op.kind == ssn::M_FILL || op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS ||
-                      op.kind == ssn::M_LINCOMB || op.kind == ssn::M_ROW_IN || op.kind == ssn::M_ROW_OUT;
-      if (!ew || op.len <= 1 || (flags & 33554432)) { out.push_back(op); return SSN_OK; }
-      std::vector<int64_t> bases;                       // signal-space origins of the operator's operands
-      if (op.kind != ssn::M_ROW_OUT) bases.push_back(op.dst);
-      if (op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS || op.kind == ssn::M_ROW_OUT) bases.push_back(op.src);
-      const std::vector<ssn::LinTerm<T>>* terms = nullptr;
-      if (op.kind == ssn::M_LINCOMB) { auto f = lin_terms.find(op.p0); if (f != lin_terms.end()) { terms = &f->second; for (auto& t : *terms) bases.push_back(t.src); } }
-      std::vector<int64_t> offs{0, op.len};
-      for (int64_t b : bases) {
-        auto lo = std::upper_bound(cuts.begin(), cuts.end(), b), hi = std::lower_bound(cuts.begin(), cuts.end(), b + op.len);
-        for (auto it = lo; it < hi; ++it) offs.push_back(*it - b);
+    std::sort(offs.begin(), offs.end());
+    offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
+    if (offs.size() > 64) { out.push_back(op); return SSN_OK; }       // (pathological fragmentation: keep the operator whole)
+    for (size_t q = 0; q + 1 < offs.size(); ++q) {
+      const int64_t o = offs[q];
+      MOp pc = op;
+      pc.len = offs[q + 1] - o;
+      pc.dst = op.dst + o;
+      if (op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS || op.kind == ssn::M_ROW_OUT) pc.src = op.src + o;
+      if (op.kind == ssn::M_ROW_IN || op.kind == ssn::M_ROW_OUT) pc.i1 = op.i1 + o;
+      if (terms && o != 0) {
+        std::vector<ssn::LinTerm<T>> tt = *terms;
+        for (auto& t : tt) t.src += o;
+        ssn::LinTerm<T>* d_terms = nullptr;
+        CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, tt.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
+        scratch_bufs.push_back(d_terms);
+        if (!tt.empty()) HIPCHK(hipMemcpy(d_terms, tt.data(), tt.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
+        lin_terms[(const void*)d_terms] = tt;
+        pc.p0 = d_terms;
       }
-      std::sort(offs.begin(), offs.end());
-      offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-      if (offs.size() > 64) { out.push_back(op); return SSN_OK; }       // (pathological fragmentation: keep the operator whole)
-      for (size_t q = 0; q + 1 < offs.size(); ++q) {
-        const int64_t o = offs[q];
-        MOp pc = op;
-        pc.len = offs[q + 1] - o;
-        pc.dst = op.dst + o;
-        if (op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS || op.kind == ssn::M_ROW_OUT) pc.src = op.src + o;
-        if (op.kind == ssn::M_ROW_IN || op.kind == ssn::M_ROW_OUT) pc.i1 = op.i1 + o;
-        if (terms && o != 0) {
-          std::vector<ssn::LinTerm<T>> tt = *terms;
-          for (auto& t : tt) t.src += o;
-          ssn::LinTerm<T>* d_terms = nullptr;
-          CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, tt.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
-          scratch_bufs.push_back(d_terms);
-          if (!tt.empty()) HIPCHK(hipMemcpy(d_terms, tt.data(), tt.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
-          lin_terms[(const void*)d_terms] = tt;
-          pc.p0 = d_terms;
-        }
-        out.push_back(pc);
-      }
-      return SSN_OK;
-    };
-    // (opt-in, SSN_ENS_SELF_FINISH=1: measured in round 4 at SLAM config 3 - 117.9 us per timestep alone, 111.0 together with the PES
-    //  fold, against 106.4 for the PES fold alone: the prologue's dependent loads lengthen every workgroup of the bandwidth-bound
-    //  round, and the greedy placement does not turn the freed recurrence into a shorter cycle)
-    if (!phased && getenv("SSN_ENS_SELF_FINISH") && atoi(getenv("SSN_ENS_SELF_FINISH")) == 1) CHK(fold_recurrent_filter(programs, item_prog));
+      out.push_back(pc);
+    }
+    return SSN_OK;
+  }
+
+  // every micro-operator (cut into pieces) and every big operator of the timestep as a unit, in program order
+  int make_units(RoundBuild& b, const std::vector<std::vector<MOp>>& programs, const std::vector<int>& item_prog) {
+    const std::vector<int64_t> cuts = range_cuts(programs, item_prog);
+    mops.clear();
     int prog_i = 0;
     for (size_t i = 0; i < items.size(); ++i) {
       const Item& it = items[i];
       if (it.type == IT_PROGRAM) {
         std::vector<MOp> pieces;
-        for (const MOp& op0 : programs[(size_t)item_prog[(size_t)prog_i]]) CHK(split_micro(op0, pieces));
+        for (const MOp& op0 : programs[(size_t)item_prog[(size_t)prog_i]]) CHK(split_micro(op0, cuts, pieces));
         for (const MOp& op0 : pieces) {
           MOp op = op0;
           op.barrier = 0;
           Unit u; u.mop = (int)mops.size(); u.phase = std::max(0, it.phase);
           micro_access(u.acc, op, true);
           mops.push_back(op);
-          units.push_back(std::move(u));
+          b.units.push_back(std::move(u));
         }
         ++prog_i;
       } else if (it.type != IT_NONE) {
         Unit u; u.item = (int)i; u.phase = std::max(0, it.phase);
         item_access(u.acc, it);
-        units.push_back(std::move(u));
+        b.units.push_back(std::move(u));
       }
     }
-    for (Unit& u : units) for (const Rng& r : u.acc) u.writes = u.writes || r.w;
-    // device copies: micro-operators, the block -> (operator, chunk) maps of the glue entries, body arguments
+    for (Unit& u : b.units) for (const Rng& r : u.acc) u.writes = u.writes || r.w;
+    b.unit_arg.assign(b.units.size(), -1);
     CHK(dmalloc(&d_mops, (int64_t)std::max<size_t>(1, mops.size()) * (int64_t)sizeof(MOp)));
     if (!mops.empty()) HIPCHK(hipMemcpy(d_mops, mops.data(), mops.size() * sizeof(MOp), hipMemcpyHostToDevice));
-    std::vector<ssn::GlueBlock> glue_map;
-    std::vector<unsigned char> arena;
-    auto put = [&](const void* src, size_t bytes) { const size_t off = (arena.size() + 15) / 16 * 16; arena.resize(off + bytes); memcpy(arena.data() + off, src, bytes); return off; };
-    std::vector<long long> unit_arg(units.size(), -1);      // arena offset of a big operator's body arguments (shared by its instances)
-    std::map<int, std::pair<long long, long long>> ens_parity_arg;      // ... of a self-finishing array: one copy per timestep parity
-    struct Fix { size_t rl; int entry; int what; size_t off; };     // what: 0 arena, 1 glue map, 2 micro-operator
-    std::vector<Fix> fixes;
-    round_launches.clear();
+    return SSN_OK;
+  }
 
-    // One instance of a unit: (unit, timestep offset inside the launch sequence, round).
-    struct Inst { int unit; int sub; int round; int lo = 0; int cnt = -1; int chain = -1; bool solo = false; };      // blocks [lo, lo + cnt) of the unit's grid (cnt < 0: all); solo: member of a serial chain
-    // Chains: an element-wise micro-operator whose only hazards inside a round are with other element-wise micro-operators
-    // on the SAME elements (equal ranges: a filter update behind the reduction it filters, the next step's input hand-off
-    // behind that update) joins their round - one block then runs the chain's operators back to back on 256 elements, the
-    // same thread on the same index in program order, with no barrier and no launch between them.
-    auto chainable = [&](const Unit& u) {
-      if (u.mop < 0 || (flags & 134217728)) return false;
-      switch (mops[(size_t)u.mop].kind) {
-        case ssn::M_FILL: case ssn::M_AXPY_INC: case ssn::M_AXPY_SET: case ssn::M_LOWPASS: case ssn::M_LINCOMB: case ssn::M_TABLE:
-        case ssn::M_ROW_IN: case ssn::M_ROW_OUT: case ssn::M_PROBE: case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC: return true;
-        default: return false;
+  // Chains: an element-wise micro-operator whose only hazards inside a round are with other element-wise micro-operators
+  // on the SAME elements (equal ranges: a filter update behind the reduction it filters, the next step's input hand-off
+  // behind that update) joins their round - one block then runs the chain's operators back to back on 256 elements, the
+  // same thread on the same index in program order, with no barrier and no launch between them.
+  bool chainable(const Unit& u) const {
+    if (u.mop < 0 || opt.has(SSN_PLAN_NO_CHAINS)) return false;
+    switch (mops[(size_t)u.mop].kind) {
+      case ssn::M_FILL: case ssn::M_AXPY_INC: case ssn::M_AXPY_SET: case ssn::M_LOWPASS: case ssn::M_LINCOMB: case ssn::M_TABLE:
+      case ssn::M_ROW_IN: case ssn::M_ROW_OUT: case ssn::M_PROBE: case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC: return true;
+      default: return false;
+    }
+  }
+  // Serial chains (round 4, second half).  The long loop of a SLAM timestep - clean-up -> binding -> memory -> unbinding -> gate ->
+  // oscillator input, one synapse delay per hop - is partly made of operators that ONE workgroup executes: glue over 1 - 2
+  // thousand elements, the gate, the argmax + gather, the transforms of the circular convolutions.  A single-workgroup unit
+  // whose only predecessors in the round before its own are members of one such chain (or one such unit) joins it instead of
+  // opening a round: the chain's block (RK_SOLO, solo_body) runs its members in program order with a workgroup barrier
+  // between them - results pass through global memory inside one workgroup, workgroup-scope visibility is all that needs.
+  // Measured at SLAM config 3 (profiles/round4_serial_chains.txt): a member costs ~2 us (one trip for its data, one for its
+  // store to land before the barrier; ~4 us before the members' descriptors were staged in LDS), a transform ~9.5 us.
+  //   * glue / gate / argmax members only (default): 102.7 vs 104.7 us per timestep, any cap between 8 and 24 us;
+  //   * with the transforms as members (SSN_SOLO_DFT=1) the plan drops from 3.78 to 3.0 - 3.3 rounds per timestep and gets
+  //     SLOWER - 110.8 us at a cap of 12 us, 114.8 at 16, 129 at 22, 139 at 26: a round now lasts as long as its longest
+  //     chain (transform + members: 20 - 45 us) and the bandwidth-bound work does not fill the time under it;
+  //   * neuron-sharded plans: nothing for the per-timestep phases (157.8 vs 155.3 us, ten launches either way); with the
+  //     plan pipelined over the exchange 123.0 vs 125.6 us at world 1 (72 vs 76 launches per 16 timesteps) - on there too
+  //     (SSN_PHASED_SOLO=0: off for sharded plans only).
+  // SSN_SOLO_CHAINS=0: off; SSN_SOLO_CAP_US: longest serial chain in estimated microseconds (default 16); SSN_SOLO_MAX_LEN:
+  // longest glue operator a single workgroup takes (default 2048 elements).
+  // LDS bytes of a transform as a round body
+  static size_t dft_lds(const Item& it) {
+    size_t lds = (size_t)(it.dft.M > 0 ? it.dft.M : it.dft.N) * (it.dft.N1 > 0 ? 4 * sizeof(float) : 3 * sizeof(float2));
+    if (it.dft.inplace) {                         // in place: M + M / 8 points + M / (smallest radix) twiddles
+      int rmin = 8;
+      for (int q = 0; q < it.dft.nr; ++q) rmin = std::min(rmin, it.dft.radix[q]);
+      lds = (size_t)(it.dft.M + it.dft.M / 8 + it.dft.M / rmin) * sizeof(float2);
+    }
+    return lds;
+  }
+  double solo_lat(const Unit& u) const {        // estimated serial time of the unit on one workgroup; < 0: not eligible
+    const bool solo_on = !(phased && !opt.phased_solo) && !opt.has(SSN_PLAN_NO_CHAINS) && opt.solo_chains;
+    if (!solo_on) return -1.0;
+    if (u.mop >= 0) {
+      const MOp& op = mops[(size_t)u.mop];
+      switch (op.kind) {
+        // (measured on the chains of SLAM config 3: ~2 us per glue member - one trip for its data, one for the store to land
+        //  before the barrier - with its descriptor already in LDS; a transform ~9.5 us)
+        case ssn::M_GATE: case ssn::M_ARGMAX_GATHER: return 3.5;
+        case ssn::M_FILL: case ssn::M_AXPY_INC: case ssn::M_AXPY_SET: case ssn::M_LOWPASS: case ssn::M_TABLE:
+        case ssn::M_ROW_IN: case ssn::M_ROW_OUT: case ssn::M_PROBE:
+          return op.len <= opt.solo_max_len ? 1.7 + 0.5 * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
+        case ssn::M_LINCOMB:
+          return op.len <= opt.solo_max_len ? 1.7 + (0.5 + 0.1 * (double)op.i0) * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
+        case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC:
+          return op.len <= opt.solo_max_len ? 1.7 + (double)((op.len + ssn::GLUE_ROWS - 1) / ssn::GLUE_ROWS) * (0.6 + 0.15 * (double)((op.i0 + 7) / 8)) : -1.0;
+        default: return -1.0;
       }
-    };
-    // Serial chains (round 4, second half).  The long loop of a SLAM timestep - clean-up -> binding -> memory -> unbinding -> gate ->
-    // oscillator input, one synapse delay per hop - is partly made of operators that ONE workgroup executes: glue over 1 - 2
-    // thousand elements, the gate, the argmax + gather, the transforms of the circular convolutions.  A single-workgroup unit
-    // whose only predecessors in the round before its own are members of one such chain (or one such unit) joins it instead of
-    // opening a round: the chain's block (RK_SOLO, solo_body) runs its members in program order with a workgroup barrier
-    // between them - results pass through global memory inside one workgroup, workgroup-scope visibility is all that needs.
-    // Measured at SLAM config 3 (profiles/round4_serial_chains.txt): a member costs ~2 us (one trip for its data, one for its
-    // store to land before the barrier; ~4 us before the members' descriptors were staged in LDS), a transform ~9.5 us.
-    //   * glue / gate / argmax members only (default): 102.7 vs 104.7 us per timestep, any cap between 8 and 24 us;
-    //   * with the transforms as members (SSN_SOLO_DFT=1) the plan drops from 3.78 to 3.0 - 3.3 rounds per timestep and gets
-    //     SLOWER - 110.8 us at a cap of 12 us, 114.8 at 16, 129 at 22, 139 at 26: a round now lasts as long as its longest
-    //     chain (transform + members: 20 - 45 us) and the bandwidth-bound work does not fill the time under it;
-    //   * neuron-sharded plans: nothing for the per-timestep phases (157.8 vs 155.3 us, ten launches either way); with the
-    //     plan pipelined over the exchange 123.0 vs 125.6 us at world 1 (72 vs 76 launches per 16 timesteps) - on there too
-    //     (SSN_PHASED_SOLO=0: off for sharded plans only).
-    // SSN_SOLO_CHAINS=0: off; SSN_SOLO_CAP_US: longest serial chain in estimated microseconds (default 16); SSN_SOLO_MAX_LEN:
-    // longest glue operator a single workgroup takes (default 2048 elements).
-    // LDS bytes of a transform as a round body
-    auto dft_lds = [&](const Item& it) {
-      size_t lds = (size_t)(it.dft.M > 0 ? it.dft.M : it.dft.N) * (it.dft.N1 > 0 ? 4 * sizeof(float) : 3 * sizeof(float2));
-      if (it.dft.inplace) {                         // in place: M + M / 8 points + M / (smallest radix) twiddles
-        int rmin = 8;
-        for (int q = 0; q < it.dft.nr; ++q) rmin = std::min(rmin, it.dft.radix[q]);
-        lds = (size_t)(it.dft.M + it.dft.M / 8 + it.dft.M / rmin) * sizeof(float2);
-      }
-      return lds;
-    };
-    const bool solo_on = !(phased && getenv("SSN_PHASED_SOLO") && atoi(getenv("SSN_PHASED_SOLO")) == 0) && !(flags & 134217728) && !(getenv("SSN_SOLO_CHAINS") && atoi(getenv("SSN_SOLO_CHAINS")) == 0);
-    const double solo_cap = getenv("SSN_SOLO_CAP_US") ? atof(getenv("SSN_SOLO_CAP_US")) : 16.0;
-    const bool solo_dft = getenv("SSN_SOLO_DFT") && atoi(getenv("SSN_SOLO_DFT")) == 1;      // transforms as chain members: measured slower (below)
-    const long long solo_max_len = getenv("SSN_SOLO_MAX_LEN") ? atoll(getenv("SSN_SOLO_MAX_LEN")) : 2048;
-    auto solo_lat = [&](const Unit& u) -> double {        // estimated serial time of the unit on one workgroup; < 0: not eligible
-      if (!solo_on) return -1.0;
-      if (u.mop >= 0) {
-        const MOp& op = mops[(size_t)u.mop];
-        switch (op.kind) {
-          // (measured on the chains of SLAM config 3: ~2 us per glue member - one trip for its data, one for the store to land
-          //  before the barrier - with its descriptor already in LDS; a transform ~9.5 us)
-          case ssn::M_GATE: case ssn::M_ARGMAX_GATHER: return 3.5;
-          case ssn::M_FILL: case ssn::M_AXPY_INC: case ssn::M_AXPY_SET: case ssn::M_LOWPASS: case ssn::M_TABLE:
-          case ssn::M_ROW_IN: case ssn::M_ROW_OUT: case ssn::M_PROBE:
-            return op.len <= solo_max_len ? 1.7 + 0.5 * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
-          case ssn::M_LINCOMB:
-            return op.len <= solo_max_len ? 1.7 + (0.5 + 0.1 * (double)op.i0) * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
-          case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC:
-            return op.len <= solo_max_len ? 1.7 + (double)((op.len + ssn::GLUE_ROWS - 1) / ssn::GLUE_ROWS) * (0.6 + 0.15 * (double)((op.i0 + 7) / 8)) : -1.0;
-          default: return -1.0;
+    }
+    if (u.item < 0) return -1.0;            // (the exchange of a sharded cycle plan)
+    const Item& it = items[(size_t)u.item];
+    if (opt.solo_dft && it.type == IT_DFT && it.dft.N1 == 0 && sizeof(T) == 4 && dft_lds(it) <= 60 * 1024) return 9.5;
+    return -1.0;
+  }
+  // 0: no hazard, 1: hazards only on identical signal ranges (element-aligned), 2: any other hazard
+  int conflict_kind(const std::vector<Rng>& x, const std::vector<Rng>& y) const {
+    int kind = 0;
+    for (const Rng& p : x)
+      for (const Rng& q : y)
+        if (p.space == q.space && p.lo < q.hi && q.lo < p.hi && (p.w || q.w)) {
+          if (p.space == (const void*)sig && p.lo == q.lo && p.hi == q.hi) kind = std::max(kind, 1);
+          else return 2;
         }
-      }
-      if (u.item < 0) return -1.0;            // (the exchange of a sharded cycle plan)
-      const Item& it = items[(size_t)u.item];
-      if (solo_dft && it.type == IT_DFT && it.dft.N1 == 0 && sizeof(T) == 4 && dft_lds(it) <= 60 * 1024) return 9.5;
-      return -1.0;
-    };
-    // 0: no hazard, 1: hazards only on identical signal ranges (element-aligned), 2: any other hazard
-    auto conflict_kind = [&](const std::vector<Rng>& x, const std::vector<Rng>& y) {
-      int kind = 0;
-      for (const Rng& p : x)
-        for (const Rng& q : y)
-          if (p.space == q.space && p.lo < q.hi && q.lo < p.hi && (p.w || q.w)) {
-            if (p.space == (const void*)sig && p.lo == q.lo && p.hi == q.hi) kind = std::max(kind, 1);
-            else return 2;
-          }
-      return kind;
-    };
-    // round of a new instance given the instances it may conflict with; joins a chain where it can
-    auto place = [&](std::vector<Inst>& placed, size_t from, int unit, const std::vector<std::vector<Rng>>& accs, int base_round,
-                     std::vector<std::vector<int>>& chains) {
-      const Unit& uu = units[(size_t)unit];
-      const bool can = chainable(uu);
-      const long long len = can ? (long long)mops[(size_t)uu.mop].len : 0;
-      int r_hard = base_round, r_soft = -1;
-      std::vector<size_t> soft, hard;
-      for (size_t v = from; v < placed.size(); ++v) {
-        if (placed[v].round < r_hard - 1 && placed[v].round < r_soft) continue;      // can neither raise a bound nor be a chain partner
-        const Unit& vv = units[(size_t)placed[v].unit];
-        const bool both = can && chainable(vv) && (long long)mops[(size_t)vv.mop].len == len;
-        const int k = both ? conflict_kind(accs[(size_t)unit], accs[(size_t)placed[v].unit])
-                           : (hazard(accs[(size_t)unit], accs[(size_t)placed[v].unit]) ? 2 : 0);
-        // (the exchange of a sharded cycle plan is no kernel: it happens in front of its round's launch, so what waits for it may
-        //  run in that very round)
-        if (k == 2) { r_hard = std::max(r_hard, placed[v].round + ((vv.mop < 0 && vv.item < 0) ? 0 : 1)); hard.push_back(v); }
-        else if (k == 1) { r_soft = std::max(r_soft, placed[v].round); soft.push_back(v); }
-      }
-      // serial chain: every hard predecessor in round r_hard - 1 is a single-workgroup unit of ONE chain (or one such unit alone)
-      const double my_lat = solo_lat(uu);
-      if (my_lat >= 0.0 && r_hard - 1 >= base_round && r_hard - 1 > r_soft) {
-        int chain = -2;               // -2: none seen, -3: not joinable, -1: one unchained instance (lone), >= 0: a chain
-        size_t lone = 0;
-        for (size_t v : hard) {
-          if (placed[v].round != r_hard - 1) continue;
-          if (solo_lat(units[(size_t)placed[v].unit]) < 0.0 || placed[v].cnt >= 0) { chain = -3; break; }
-          if (placed[v].chain >= 0) {
-            if (chain == -2) chain = placed[v].chain;
-            else if (chain != placed[v].chain) { chain = -3; break; }
-          } else {
-            if (chain == -2) { chain = -1; lone = v; }
-            else { chain = -3; break; }
-          }
-        }
-        if (chain >= 0 || chain == -1) {
-          double total = my_lat;
-          bool ok = true;
-          int transforms = uu.mop < 0 ? 1 : 0;        // (at most one per chain: solo_body runs it outside its member loops)
-          if (chain >= 0 && chains[(size_t)chain].size() + 1 > (size_t)ssn::SOLO_MAX_MEMBERS) ok = false;
-          if (chain == -1) { total += solo_lat(units[(size_t)placed[lone].unit]); transforms += units[(size_t)placed[lone].unit].mop < 0 ? 1 : 0; }
-          else
-            for (int mi : chains[(size_t)chain]) {
-              const double l = solo_lat(units[(size_t)placed[(size_t)mi].unit]);
-              if (l < 0.0 || placed[(size_t)mi].round != r_hard - 1) { ok = false; break; }
-              total += l;
-              transforms += units[(size_t)placed[(size_t)mi].unit].mop < 0 ? 1 : 0;
-            }
-          if (ok && transforms <= 1 && total <= solo_cap) {
-            if (chain == -1) { chain = (int)chains.size(); placed[lone].chain = chain; chains.push_back({(int)lone}); }
-            for (int mi : chains[(size_t)chain]) placed[(size_t)mi].solo = true;
-            Inst in{unit, 0, r_hard - 1, 0, -1, chain, true};
-            chains[(size_t)chain].push_back((int)placed.size());
-            placed.push_back(in);
-            return in.round;
-          }
-        }
-      }
-      Inst in{unit, 0, std::max(r_hard, r_soft), 0, -1, -1};
-      if (r_soft >= 0 && r_soft >= r_hard) {
-        int chain = -2;
-        for (size_t v : soft) {
-          if (placed[v].round != r_soft) continue;
-          if (placed[v].chain < 0) { placed[v].chain = (int)chains.size(); chains.push_back({(int)v}); }
+    return kind;
+  }
+  // round of a new instance given the instances it may conflict with; joins a chain where it can
+  int place(const RoundBuild& b, std::vector<Inst>& placed, size_t from, int unit, const AccLists& accs, int base_round, Chains& chains) const {
+    const Unit& uu = b.units[(size_t)unit];
+    const bool can = chainable(uu);
+    const long long len = can ? (long long)mops[(size_t)uu.mop].len : 0;
+    int r_hard = base_round, r_soft = -1;
+    std::vector<size_t> soft, hard;
+    for (size_t v = from; v < placed.size(); ++v) {
+      if (placed[v].round < r_hard - 1 && placed[v].round < r_soft) continue;      // can neither raise a bound nor be a chain partner
+      const Unit& vv = b.units[(size_t)placed[v].unit];
+      const bool both = can && chainable(vv) && (long long)mops[(size_t)vv.mop].len == len;
+      const int k = both ? conflict_kind(accs[(size_t)unit], accs[(size_t)placed[v].unit])
+                         : (hazard(accs[(size_t)unit], accs[(size_t)placed[v].unit]) ? 2 : 0);
+      // (the exchange of a sharded cycle plan is no kernel: it happens in front of its round's launch, so what waits for it may
+      //  run in that very round)
+      if (k == 2) { r_hard = std::max(r_hard, placed[v].round + ((vv.mop < 0 && vv.item < 0) ? 0 : 1)); hard.push_back(v); }
+      else if (k == 1) { r_soft = std::max(r_soft, placed[v].round); soft.push_back(v); }
+    }
+    // serial chain: every hard predecessor in round r_hard - 1 is a single-workgroup unit of ONE chain (or one such unit alone)
+    const double my_lat = solo_lat(uu);
+    if (my_lat >= 0.0 && r_hard - 1 >= base_round && r_hard - 1 > r_soft) {
+      int chain = -2;               // -2: none seen, -3: not joinable, -1: one unchained instance (lone), >= 0: a chain
+      size_t lone = 0;
+      for (size_t v : hard) {
+        if (placed[v].round != r_hard - 1) continue;
+        if (solo_lat(b.units[(size_t)placed[v].unit]) < 0.0 || placed[v].cnt >= 0) { chain = -3; break; }
+        if (placed[v].chain >= 0) {
           if (chain == -2) chain = placed[v].chain;
-          else if (chain != placed[v].chain) chain = -3;
+          else if (chain != placed[v].chain) { chain = -3; break; }
+        } else {
+          if (chain == -2) { chain = -1; lone = v; }
+          else { chain = -3; break; }
         }
-        if (chain >= 0 && placed[(size_t)chains[(size_t)chain][0]].solo && chains[(size_t)chain].size() + 1 > (size_t)ssn::SOLO_MAX_MEMBERS) chain = -3;
-        if (chain >= 0) { in.chain = chain; in.solo = placed[(size_t)chains[(size_t)chain][0]].solo; chains[(size_t)chain].push_back((int)placed.size()); }
-        else in.round = r_soft + 1;            // element-aligned with members of two chains: a round of its own
       }
-      placed.push_back(in);
-      return in.round;
-    };
-    // Launch sequence of a set of instances grouped by round (instances of one round are mutually independent).
-    const bool no_interleave = getenv("SSN_ROUND_INTERLEAVE") && atoi(getenv("SSN_ROUND_INTERLEAVE")) == 0;      // A/B knob
-    const bool head_prio = !(getenv("SSN_HEAD_PRIO") && atoi(getenv("SSN_HEAD_PRIO")) == 0);                       // A/B knob (ssn_round.hpp, k_round)
-    std::vector<int> chain_tab;
-    auto emit = [&](const std::vector<Inst>& insts, int n_rounds, std::vector<Launch>& out, const std::vector<std::vector<int>>& chains) {
-      std::vector<std::vector<const Inst*>> by_round((size_t)n_rounds);
-      for (const Inst& in : insts) by_round[(size_t)in.round].push_back(&in);
-      auto in_chain = [&](const Inst* in) { return in->chain >= 0 && chains[(size_t)in->chain].size() >= 2; };
-      for (int r = 0; r < n_rounds; ++r) {
-        RoundLaunch rl;
-        rl.round = r;
-        rl.args = ssn::RoundArgs<T>{};
-        rl.args.mops = d_mops; rl.args.sig = sig; rl.args.ctx = d_ctx;
-        int phase = 0;
-        std::vector<Launch> plain;
-        auto close = [&]() {
-          if (rl.args.n == 0) return;
-          // interleaved dispatch of the big grids behind the latency-bound head (RoundArgs::stride)
-          rl.args.head = 0; rl.args.stride = 0;
-          int head = 0;
-          for (int q = 0; q < rl.args.n; ++q) {
-            const int k = rl.args.e[q].kind;
-            if (k == ssn::RK_DFT || k == ssn::RK_SOLO || k == ssn::RK_GATE || k == ssn::RK_ARGMAX || k == ssn::RK_GLUE) head = rl.args.e[q].first + rl.args.e[q].cnt;
-            else break;
+      if (chain >= 0 || chain == -1) {
+        double total = my_lat;
+        bool ok = true;
+        int transforms = uu.mop < 0 ? 1 : 0;        // (at most one per chain: solo_body runs it outside its member loops)
+        if (chain >= 0 && chains[(size_t)chain].size() + 1 > (size_t)ssn::SOLO_MAX_MEMBERS) ok = false;
+        if (chain == -1) { total += solo_lat(b.units[(size_t)placed[lone].unit]); transforms += b.units[(size_t)placed[lone].unit].mop < 0 ? 1 : 0; }
+        else
+          for (int mi : chains[(size_t)chain]) {
+            const double l = solo_lat(b.units[(size_t)placed[(size_t)mi].unit]);
+            if (l < 0.0 || placed[(size_t)mi].round != r_hard - 1) { ok = false; break; }
+            total += l;
+            transforms += b.units[(size_t)placed[(size_t)mi].unit].mop < 0 ? 1 : 0;
           }
-          rl.args.prio = (head_prio && head < rl.n_blocks) ? head : 0;      // (blocks [0, prio) raise their waves' issue priority)
-          if (!no_interleave) {
-            const long long m = (long long)rl.n_blocks - head;
-            if (m >= 64) {
-              long long st = (long long)(0.6180339887 * (double)m);
-              auto gcd = [](long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; };
-              while (st > 1 && gcd(st, m) != 1) --st;
-              if (st > 1) { rl.args.head = head; rl.args.stride = (unsigned int)st; }
-            }
+        if (ok && transforms <= 1 && total <= opt.solo_cap_us) {
+          if (chain == -1) { chain = (int)chains.size(); placed[lone].chain = chain; chains.push_back({(int)lone}); }
+          for (int mi : chains[(size_t)chain]) placed[(size_t)mi].solo = true;
+          Inst in{unit, 0, r_hard - 1, 0, -1, chain, true};
+          chains[(size_t)chain].push_back((int)placed.size());
+          placed.push_back(in);
+          return in.round;
+        }
+      }
+    }
+    Inst in{unit, 0, std::max(r_hard, r_soft), 0, -1, -1};
+    if (r_soft >= 0 && r_soft >= r_hard) {
+      int chain = -2;
+      for (size_t v : soft) {
+        if (placed[v].round != r_soft) continue;
+        if (placed[v].chain < 0) { placed[v].chain = (int)chains.size(); chains.push_back({(int)v}); }
+        if (chain == -2) chain = placed[v].chain;
+        else if (chain != placed[v].chain) chain = -3;
+      }
+      if (chain >= 0 && placed[(size_t)chains[(size_t)chain][0]].solo && chains[(size_t)chain].size() + 1 > (size_t)ssn::SOLO_MAX_MEMBERS) chain = -3;
+      if (chain >= 0) { in.chain = chain; in.solo = placed[(size_t)chains[(size_t)chain][0]].solo; chains[(size_t)chain].push_back((int)placed.size()); }
+      else in.round = r_soft + 1;            // element-aligned with members of two chains: a round of its own
+    }
+    placed.push_back(in);
+    return in.round;
+  }
+
+  // k_round body of a big operator: kind, grid and LDS bytes; its arguments go to the arena once (ao: their offset, shared by the
+  // operator's instances).  kind < 0: the operator has no body there and is launched on its own.
+  struct RoundBody { int kind = -1; int gx = 1, gy = 1; size_t lds = 0; };
+  RoundBody round_body(RoundBuild& b, const Item& it, long long& ao) const {
+    const size_t xb = (size_t)it.cols * sizeof(T);
+    switch (it.type) {
+      case IT_MATVEC:
+        if (xb <= 48 * 1024) {
+          const bool r1 = it.rows <= opt.matvec_r1_max;
+          if (r1) {
+            ssn::MatvecArgs<T> a{it.Wm, it.src, it.dst, it.rows, it.cols, it.ld, it.set};
+            if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+          } else {                 // (the 16-rows-per-workgroup body is matvec_neurons_body's: no population behind this product)
+            ssn::MatvecNeuronsArgs<T> a{};
+            a.mv = ssn::MatvecArgs<T>{it.Wm, it.src, it.dst, it.rows, it.cols, it.ld, it.set};
+            if (ao < 0) ao = (long long)b.put(&a, sizeof a);
           }
-          Launch l; l.rl = (int)round_launches.size(); l.phase = phase;
-          rl.args.pad = l.rl;                    // (launch id: read by the diagnostic stamps of k_round, SSN_ROUND_STAMPS)
-          round_launches.push_back(rl);
-          out.push_back(l);
-          rl.args.n = 0; rl.n_blocks = 0; rl.lds = 0;
-        };
-        int part_lo = 0, part_cnt = -1;      // block range of the instance being emitted (set per instance below)
-        // The grid's blocks are dispatched in order: single-workgroup bodies whose latency bounds the round (a DFT: ~9 us)
-        // go first so that they run beside the bandwidth-bound blocks instead of behind them; then the small glue; then
-        // the big grids, longest first.
-        struct Pending { int kind, gx, gy, what, lo, cnt; size_t lds, off; };
-        std::vector<Pending> pending;
-        auto entry = [&](int kind, int gx, int gy, size_t lds, int what, size_t off) {
-          Pending q{kind, std::max(1, gx), std::max(1, gy), what, 0, 0, lds, off};
-          q.lo = part_cnt < 0 ? 0 : part_lo;
-          q.cnt = part_cnt < 0 ? q.gx * q.gy : std::min(part_cnt, q.gx * q.gy - q.lo);
-          pending.push_back(q);
-        };
-        auto flush_entries = [&]() {
-          auto prio = [](const Pending& q) { return (q.kind == ssn::RK_DFT || q.kind == ssn::RK_SOLO) ? 0 : (q.kind == ssn::RK_GATE || q.kind == ssn::RK_ARGMAX) ? 1 : q.kind == ssn::RK_GLUE ? 2 : 3; };
-          std::stable_sort(pending.begin(), pending.end(), [&](const Pending& a, const Pending& b) {
-            if (prio(a) != prio(b)) return prio(a) < prio(b);
-            return prio(a) == 3 && a.cnt > b.cnt;
-          });
-          for (const Pending& q : pending) {
-            if (rl.args.n == ssn::MAX_ROUND_ENTRIES) close();
-            ssn::RoundEntry& e = rl.args.e[rl.args.n];
-            e.kind = q.kind; e.first = rl.n_blocks; e.gx = q.gx; e.gy = q.gy; e.args = nullptr; e.lo = q.lo; e.cnt = q.cnt;
-            fixes.push_back(Fix{round_launches.size(), rl.args.n, q.what, q.off});
-            rl.n_blocks += e.cnt;
-            rl.lds = std::max(rl.lds, q.lds);
-            rl.args.n += 1;
+          return RoundBody{r1 ? ssn::RK_MATVEC_R1 : ssn::RK_MATVEC_R4, r1 ? (it.rows + 3) / 4 : (it.rows + 15) / 16, 1, (xb + 15) / 16 * 16 + 64};
+        }
+        break;
+      case IT_ENS: {
+        const ssn::EnsArgs<T>& a = it.ens;
+        const int kind = ens_round_kind(a);
+        if (kind >= 0) {
+          if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+          return RoundBody{kind, ens_round_blocks(a), 1, 512};
+        }
+        break;
+      }
+      case IT_SPMV: {
+        ssn::SpmvArgs<T> a{it.Wm, it.ld, it.src, it.cols, it.rows, it.dst, it.ld, it.n, it.list, it.count, it.seg, it.seg_len};
+        const size_t lds = 272 * sizeof(int) + (it.list ? 0 : (size_t)it.cols * sizeof(int));
+        if (lds <= 60 * 1024) {
+          if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+          return RoundBody{ssn::RK_SPMV, (it.rows + 255) / 256, it.n, lds};
+        }
+        break;
+      }
+      case IT_NEURONS: {
+        ssn::NeuronsArgs<T> a{it.np, it.src, it.dst, it.V, it.R, it.n, it.scalar, it.list, it.count};
+        if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+        return RoundBody{ssn::RK_NEURONS, (it.n + 255) / 256, 1, 64};
+      }
+      case IT_MATVEC_NEURONS: {
+        ssn::MatvecNeuronsArgs<T> a{ssn::MatvecArgs<T>{it.Wm, it.aux0, nullptr, it.rows, it.cols, it.ld, it.set},
+                                    ssn::NeuronsArgs<T>{it.np, it.src, it.dst, it.V, it.R, it.n, it.scalar, it.list, it.count}};
+        if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+        return RoundBody{ssn::RK_MATVEC_NEURONS, (it.rows + 15) / 16, 1, (xb + 15) / 16 * 16 + 64};
+      }
+      case IT_DFT: {
+        const size_t lds = dft_lds(it);
+        if (lds <= 64 * 1024 && it.dft.N1 == 0) {      // (the four-step engine is launched on its own: see dft_body<ROUND>)
+          if (ao < 0) ao = (long long)b.put(&it.dft, sizeof it.dft);
+          return RoundBody{ssn::RK_DFT, 1, 1, lds};
+        }
+        break;
+      }
+      case IT_GRID_LHS: {
+        ssn::GridLhsArgs<T> a{it.src, it.aux0, it.ld, it.dst, it.cols, it.rows, it.cols / 2};
+        if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+        return RoundBody{ssn::RK_GRID_LHS, (it.rows * (it.cols / 2) + 255) / 256, 1, 64};
+      }
+      case IT_GRID_DOT: {
+        ssn::GridDotArgs<T> a{it.src, it.cols, it.Wm, it.ld, it.dst, it.n, it.cols, it.rows};
+        if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+        return RoundBody{ssn::RK_GRID_DOT, (it.n + 15) / 16, it.rows, xb};
+      }
+      case IT_PES: {
+        ssn::PesArgs<T> a{it.Wm, it.aux0, it.aux1, it.rows, it.cols, it.ld, it.scalar, it.lp_dst, it.lp_src, it.lp_a, it.lp_b};
+        if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+        return RoundBody{ssn::RK_PES, (it.cols + 1023) / 1024, (it.rows + ssn::PES_ROWS - 1) / ssn::PES_ROWS, 64};
+      }
+      case IT_VOJA: {
+        ssn::VojaArgs<T> a{it.Wm, it.src, it.aux0, it.aux1, it.aux2, it.rows, it.cols, it.ld, it.scalar};
+        if (ao < 0) ao = (long long)b.put(&a, sizeof a);
+        return RoundBody{ssn::RK_VOJA, (it.rows + 4 * ssn::VOJA_ROWS_PER_WAVE - 1) / (4 * ssn::VOJA_ROWS_PER_WAVE), 1, 64};
+      }
+      default: break;
+    }
+    return RoundBody{};
+  }
+
+  // Launch sequence of a set of instances grouped by round (instances of one round are mutually independent).
+  void emit(RoundBuild& b, const std::vector<Inst>& insts, int n_rounds, std::vector<Launch>& out, const Chains& chains) {
+    std::vector<std::vector<const Inst*>> by_round((size_t)n_rounds);
+    for (const Inst& in : insts) by_round[(size_t)in.round].push_back(&in);
+    auto in_chain = [&](const Inst* in) { return in->chain >= 0 && chains[(size_t)in->chain].size() >= 2; };
+    for (int r = 0; r < n_rounds; ++r) {
+      RoundLaunch rl;
+      rl.round = r;
+      rl.args = ssn::RoundArgs<T>{};
+      rl.args.mops = d_mops; rl.args.sig = sig; rl.args.ctx = d_ctx;
+      int phase = 0;
+      std::vector<Launch> plain;
+      auto close = [&]() {
+        if (rl.args.n == 0) return;
+        // interleaved dispatch of the big grids behind the latency-bound head (RoundArgs::stride)
+        rl.args.head = 0; rl.args.stride = 0;
+        int head = 0;
+        for (int q = 0; q < rl.args.n; ++q) {
+          const int k = rl.args.e[q].kind;
+          if (k == ssn::RK_DFT || k == ssn::RK_SOLO || k == ssn::RK_GATE || k == ssn::RK_ARGMAX || k == ssn::RK_GLUE) head = rl.args.e[q].first + rl.args.e[q].cnt;
+          else break;
+        }
+        rl.args.prio = (opt.head_prio && head < rl.n_blocks) ? head : 0;      // (blocks [0, prio) raise their waves' issue priority)
+        if (opt.round_interleave) {
+          const long long m = (long long)rl.n_blocks - head;
+          if (m >= 64) {
+            long long st = (long long)(0.6180339887 * (double)m);
+            auto gcd = [](long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; };
+            while (st > 1 && gcd(st, m) != 1) --st;
+            if (st > 1) { rl.args.head = head; rl.args.stride = (unsigned int)st; }
           }
-          pending.clear();
-        };
-        // the exchange of a neuron-sharded cycle plan (a unit without operator): the caller's all-reduce comes before this round
-        for (const Inst* in : by_round[(size_t)r])
-          if (units[(size_t)in->unit].mop < 0 && units[(size_t)in->unit].item < 0) { Launch x; x.phase = -2; out.push_back(x); }
-        // serial chains: one block each, members in program order behind workgroup barriers (RK_SOLO; see solo_lat)
-        part_lo = 0; part_cnt = -1;
-        for (const Inst* in : by_round[(size_t)r]) {
-          if (!(in_chain(in) && in->solo)) continue;
+        }
+        Launch l; l.rl = (int)round_launches.size(); l.phase = phase;
+        rl.args.pad = l.rl;                    // (launch id: read by the diagnostic stamps of k_round, SSN_ROUND_STAMPS)
+        round_launches.push_back(rl);
+        out.push_back(l);
+        rl.args.n = 0; rl.n_blocks = 0; rl.lds = 0;
+      };
+      int part_lo = 0, part_cnt = -1;      // block range of the instance being emitted (set per instance below)
+      // The grid's blocks are dispatched in order: single-workgroup bodies whose latency bounds the round (a DFT: ~9 us)
+      // go first so that they run beside the bandwidth-bound blocks instead of behind them; then the small glue; then
+      // the big grids, longest first.
+      struct Pending { int kind, gx, gy, what, lo, cnt; size_t lds, off; };
+      std::vector<Pending> pending;
+      auto entry = [&](int kind, int gx, int gy, size_t lds, int what, size_t off) {
+        Pending q{kind, std::max(1, gx), std::max(1, gy), what, 0, 0, lds, off};
+        q.lo = part_cnt < 0 ? 0 : part_lo;
+        q.cnt = part_cnt < 0 ? q.gx * q.gy : std::min(part_cnt, q.gx * q.gy - q.lo);
+        pending.push_back(q);
+      };
+      auto flush_entries = [&]() {
+        auto prio = [](const Pending& q) { return (q.kind == ssn::RK_DFT || q.kind == ssn::RK_SOLO) ? 0 : (q.kind == ssn::RK_GATE || q.kind == ssn::RK_ARGMAX) ? 1 : q.kind == ssn::RK_GLUE ? 2 : 3; };
+        std::stable_sort(pending.begin(), pending.end(), [&](const Pending& a, const Pending& b) {
+          if (prio(a) != prio(b)) return prio(a) < prio(b);
+          return prio(a) == 3 && a.cnt > b.cnt;
+        });
+        for (const Pending& q : pending) {
+          if (rl.args.n == ssn::MAX_ROUND_ENTRIES) close();
+          ssn::RoundEntry& e = rl.args.e[rl.args.n];
+          e.kind = q.kind; e.first = rl.n_blocks; e.gx = q.gx; e.gy = q.gy; e.args = nullptr; e.lo = q.lo; e.cnt = q.cnt;
+          b.fixes.push_back(Fix{round_launches.size(), rl.args.n, q.what, q.off});
+          rl.n_blocks += e.cnt;
+          rl.lds = std::max(rl.lds, q.lds);
+          rl.args.n += 1;
+        }
+        pending.clear();
+      };
+      // the exchange of a neuron-sharded cycle plan (a unit without operator): the caller's all-reduce comes before this round
+      for (const Inst* in : by_round[(size_t)r])
+        if (b.units[(size_t)in->unit].mop < 0 && b.units[(size_t)in->unit].item < 0) { Launch x; x.phase = -2; out.push_back(x); }
+      // serial chains: one block each, members in program order behind workgroup barriers (RK_SOLO; see solo_lat)
+      part_lo = 0; part_cnt = -1;
+      for (const Inst* in : by_round[(size_t)r]) {
+        if (!(in_chain(in) && in->solo)) continue;
+        const std::vector<int>& members = chains[(size_t)in->chain];
+        if (&insts[(size_t)members[0]] != in) continue;
+        phase = b.units[(size_t)in->unit].phase;
+        const int ofs = (int)b.chain_tab.size();
+        size_t lds = 64;
+        b.chain_tab.push_back((int)members.size());
+        if (opt.debug_plan) fprintf(stderr, "[ssn]   serial chain in round %d:", r);
+        for (int mi : members) {
+          const Inst& m = insts[(size_t)mi];
+          const Unit& mu = b.units[(size_t)m.unit];
+          if (mu.mop >= 0) {
+            b.chain_tab.push_back(mu.mop);
+            if (opt.debug_plan) fprintf(stderr, " k%d/%lld(s%d)", mops[(size_t)mu.mop].kind, (long long)mops[(size_t)mu.mop].len, m.sub);
+          } else {
+            const Item& it = items[(size_t)mu.item];      // (a transform: solo_lat admits nothing else)
+            long long& ao = b.unit_arg[(size_t)m.unit];
+            if (ao < 0) ao = (long long)b.put(&it.dft, sizeof it.dft);
+            b.chain_tab.push_back(-(int)(ao / 16) - 1);
+            lds = std::max(lds, dft_lds(it));
+            if (opt.debug_plan) fprintf(stderr, " dft%d(s%d)", it.dft.kind, m.sub);
+          }
+          b.chain_tab.push_back(m.sub);
+        }
+        if (opt.debug_plan) fprintf(stderr, "\n");
+        entry(ssn::RK_SOLO, 1, 1, lds, 3, (size_t)ofs);
+      }
+      // glue: one entry for all chunked micro-operators of the round
+      const size_t map_begin = b.glue_map.size();
+      for (const Inst* in : by_round[(size_t)r]) {
+        const Unit& u = b.units[(size_t)in->unit];
+        phase = u.phase;
+        if (u.mop < 0) continue;
+        if (in_chain(in) && in->solo) continue;
+        const MOp& op = mops[(size_t)u.mop];
+        if (op.kind == ssn::M_GATE || op.kind == ssn::M_ARGMAX_GATHER) continue;
+        if (in_chain(in)) {
           const std::vector<int>& members = chains[(size_t)in->chain];
-          if (&insts[(size_t)members[0]] != in) continue;
-          phase = units[(size_t)in->unit].phase;
-          const int ofs = (int)chain_tab.size();
-          size_t lds = 64;
-          chain_tab.push_back((int)members.size());
-          if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, "[ssn]   serial chain in round %d:", r);
-          for (int mi : members) {
-            const Inst& m = insts[(size_t)mi];
-            const Unit& mu = units[(size_t)m.unit];
-            if (mu.mop >= 0) {
-              chain_tab.push_back(mu.mop);
-              if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, " k%d/%lld(s%d)", mops[(size_t)mu.mop].kind, (long long)mops[(size_t)mu.mop].len, m.sub);
-            } else {
-              const Item& it = items[(size_t)mu.item];      // (a transform: solo_lat admits nothing else)
-              long long& ao = unit_arg[(size_t)m.unit];
-              if (ao < 0) ao = (long long)put(&it.dft, sizeof it.dft);
-              chain_tab.push_back(-(int)(ao / 16) - 1);
-              lds = std::max(lds, dft_lds(it));
-              if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, " dft%d(s%d)", it.dft.kind, m.sub);
-            }
-            chain_tab.push_back(m.sub);
+          if (&insts[(size_t)members[0]] != in) continue;                 // emitted with its chain's first member
+          const int ofs = (int)b.chain_tab.size();
+          if (opt.debug_plan) {
+            fprintf(stderr, "[ssn]   chain in round %d (len %lld):", r, (long long)op.len);
+            for (int mi : members) fprintf(stderr, " k%d", mops[(size_t)b.units[(size_t)insts[(size_t)mi].unit].mop].kind);
+            fprintf(stderr, "\n");
           }
-          if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, "\n");
-          entry(ssn::RK_SOLO, 1, 1, lds, 3, (size_t)ofs);
+          b.chain_tab.push_back((int)members.size());
+          for (int mi : members) { b.chain_tab.push_back(b.units[(size_t)insts[(size_t)mi].unit].mop); b.chain_tab.push_back(insts[(size_t)mi].sub); }
+          const int blocks = (int)std::max<long long>(1, (op.len + ssn::GLUE_ROWS - 1) / ssn::GLUE_ROWS);
+          for (int c = 0; c < blocks; ++c) b.glue_map.push_back(ssn::GlueBlock{-(ofs + 1), c});
+          continue;
         }
-        // glue: one entry for all chunked micro-operators of the round
-        const size_t map_begin = glue_map.size();
-        for (const Inst* in : by_round[(size_t)r]) {
-          const Unit& u = units[(size_t)in->unit];
-          phase = u.phase;
-          if (u.mop < 0) continue;
-          if (in_chain(in) && in->solo) continue;
+        const long long per = glue_row_kind(op.kind) ? ssn::GLUE_ROWS : ssn::GLUE_CHUNK;
+        const int chunks = (int)std::max<long long>(1, (op.len + per - 1) / per);
+        for (int c = 0; c < chunks; ++c) b.glue_map.push_back(ssn::GlueBlock{u.mop, c | (in->sub << 24)});
+      }
+      if (b.glue_map.size() > map_begin) entry(ssn::RK_GLUE, (int)(b.glue_map.size() - map_begin), 1, 64, 1, map_begin);
+      for (const Inst* in : by_round[(size_t)r]) {
+        const Unit& u = b.units[(size_t)in->unit];
+        part_lo = in->lo; part_cnt = in->cnt;
+        if (in_chain(in) && in->solo) continue;
+        if (u.mop < 0 && u.item < 0) continue;        // (the exchange marker)
+        if (u.mop >= 0) {
           const MOp& op = mops[(size_t)u.mop];
-          if (op.kind == ssn::M_GATE || op.kind == ssn::M_ARGMAX_GATHER) continue;
-          if (in_chain(in)) {
-            const std::vector<int>& members = chains[(size_t)in->chain];
-            if (&insts[(size_t)members[0]] != in) continue;                 // emitted with its chain's first member
-            const int ofs = (int)chain_tab.size();
-            if (getenv("SSN_DEBUG_PLAN")) {
-              fprintf(stderr, "[ssn]   chain in round %d (len %lld):", r, (long long)op.len);
-              for (int mi : members) fprintf(stderr, " k%d", mops[(size_t)units[(size_t)insts[(size_t)mi].unit].mop].kind);
-              fprintf(stderr, "\n");
-            }
-            chain_tab.push_back((int)members.size());
-            for (int mi : members) { chain_tab.push_back(units[(size_t)insts[(size_t)mi].unit].mop); chain_tab.push_back(insts[(size_t)mi].sub); }
-            const int blocks = (int)std::max<long long>(1, (op.len + ssn::GLUE_ROWS - 1) / ssn::GLUE_ROWS);
-            for (int c = 0; c < blocks; ++c) glue_map.push_back(ssn::GlueBlock{-(ofs + 1), c});
-            continue;
-          }
-          const long long per = glue_row_kind(op.kind) ? ssn::GLUE_ROWS : ssn::GLUE_CHUNK;
-          const int chunks = (int)std::max<long long>(1, (op.len + per - 1) / per);
-          for (int c = 0; c < chunks; ++c) glue_map.push_back(ssn::GlueBlock{u.mop, c | (in->sub << 24)});
+          if (op.kind == ssn::M_GATE) entry(ssn::RK_GATE, 1, 1, 64, 2, (size_t)u.mop);
+          else if (op.kind == ssn::M_ARGMAX_GATHER) entry(ssn::RK_ARGMAX, 1, 1, 64, 2, (size_t)u.mop);
+          continue;
         }
-        if (glue_map.size() > map_begin) entry(ssn::RK_GLUE, (int)(glue_map.size() - map_begin), 1, 64, 1, map_begin);
-        for (const Inst* in : by_round[(size_t)r]) {
-          const Unit& u = units[(size_t)in->unit];
-          part_lo = in->lo; part_cnt = in->cnt;
-          if (in_chain(in) && in->solo) continue;
-          if (u.mop < 0 && u.item < 0) continue;        // (the exchange marker)
-          if (u.mop >= 0) {
-            const MOp& op = mops[(size_t)u.mop];
-            if (op.kind == ssn::M_GATE) entry(ssn::RK_GATE, 1, 1, 64, 2, (size_t)u.mop);
-            else if (op.kind == ssn::M_ARGMAX_GATHER) entry(ssn::RK_ARGMAX, 1, 1, 64, 2, (size_t)u.mop);
-            continue;
-          }
-          const Item& it = items[(size_t)u.item];
-          const size_t xb = (size_t)it.cols * sizeof(T);
-          long long& ao = unit_arg[(size_t)in->unit];
-          switch (it.type) {
-            case IT_MATVEC:
-              if (xb <= 48 * 1024) {
-                const bool r1 = it.rows <= matvec_r1_max;
-                if (r1) {
-                  ssn::MatvecArgs<T> a{it.Wm, it.src, it.dst, it.rows, it.cols, it.ld, it.set};
-                  if (ao < 0) ao = (long long)put(&a, sizeof a);
-                } else {                 // (the 16-rows-per-workgroup body is matvec_neurons_body's: no population behind this product)
-                  ssn::MatvecNeuronsArgs<T> a{};
-                  a.mv = ssn::MatvecArgs<T>{it.Wm, it.src, it.dst, it.rows, it.cols, it.ld, it.set};
-                  if (ao < 0) ao = (long long)put(&a, sizeof a);
-                }
-                entry(r1 ? ssn::RK_MATVEC_R1 : ssn::RK_MATVEC_R4, r1 ? (it.rows + 3) / 4 : (it.rows + 15) / 16, 1, (xb + 15) / 16 * 16 + 64, 0, (size_t)ao);
-                continue;
-              }
-              break;
-            case IT_ENS: {
-              const ssn::EnsArgs<T>& a = it.ens;
-              const int kind = ens_round_kind(a);
-              if (kind >= 0) {
-                if (a.defer == 2) {          // the timestep offset of the instance decides which set of partial sums it writes: two copies
-                  auto f = ens_parity_arg.find(in->unit);
-                  if (f == ens_parity_arg.end()) {
-                    ssn::EnsArgs<T> c0 = a, c1 = a;
-                    c0.sub = 0; c1.sub = 1;
-                    const long long o0 = (long long)put(&c0, sizeof c0), o1 = (long long)put(&c1, sizeof c1);
-                    f = ens_parity_arg.insert({in->unit, {o0, o1}}).first;
-                  }
-                  entry(kind, ens_round_blocks(a), 1, 512, 0, (size_t)((in->sub & 1) ? f->second.second : f->second.first));
-                  continue;
-                }
-                if (ao < 0) ao = (long long)put(&a, sizeof a);
-                entry(kind, ens_round_blocks(a), 1, 512, 0, (size_t)ao);
-                continue;
-              }
-              break;
-            }
-            case IT_SPMV: {
-              ssn::SpmvArgs<T> a{it.Wm, it.ld, it.src, it.cols, it.rows, it.dst, it.ld, it.n, it.list, it.count, it.seg, it.seg_len};
-              const size_t lds = 272 * sizeof(int) + (it.list ? 0 : (size_t)it.cols * sizeof(int));
-              if (lds <= 60 * 1024) {
-                if (ao < 0) ao = (long long)put(&a, sizeof a);
-                entry(ssn::RK_SPMV, (it.rows + 255) / 256, it.n, lds, 0, (size_t)ao);
-                continue;
-              }
-              break;
-            }
-            case IT_NEURONS: {
-              ssn::NeuronsArgs<T> a{it.np, it.src, it.dst, it.V, it.R, it.n, it.scalar, it.list, it.count};
-              if (ao < 0) ao = (long long)put(&a, sizeof a);
-              entry(ssn::RK_NEURONS, (it.n + 255) / 256, 1, 64, 0, (size_t)ao);
-              continue;
-            }
-            case IT_MATVEC_NEURONS: {
-              ssn::MatvecNeuronsArgs<T> a{ssn::MatvecArgs<T>{it.Wm, it.aux0, nullptr, it.rows, it.cols, it.ld, it.set},
-                                          ssn::NeuronsArgs<T>{it.np, it.src, it.dst, it.V, it.R, it.n, it.scalar, it.list, it.count}};
-              if (ao < 0) ao = (long long)put(&a, sizeof a);
-              entry(ssn::RK_MATVEC_NEURONS, (it.rows + 15) / 16, 1, (xb + 15) / 16 * 16 + 64, 0, (size_t)ao);
-              continue;
-            }
-            case IT_DFT: {
-              const size_t lds = dft_lds(it);
-              if (lds <= 64 * 1024 && it.dft.N1 == 0) {      // (the four-step engine is launched on its own: see dft_body<ROUND>)
-                if (ao < 0) ao = (long long)put(&it.dft, sizeof it.dft);
-                entry(ssn::RK_DFT, 1, 1, lds, 0, (size_t)ao);
-                continue;
-              }
-              break;
-            }
-            case IT_GRID_LHS: {
-              ssn::GridLhsArgs<T> a{it.src, it.aux0, it.ld, it.dst, it.cols, it.rows, it.cols / 2};
-              if (ao < 0) ao = (long long)put(&a, sizeof a);
-              entry(ssn::RK_GRID_LHS, (it.rows * (it.cols / 2) + 255) / 256, 1, 64, 0, (size_t)ao);
-              continue;
-            }
-            case IT_GRID_DOT: {
-              ssn::GridDotArgs<T> a{it.src, it.cols, it.Wm, it.ld, it.dst, it.n, it.cols, it.rows};
-              if (ao < 0) ao = (long long)put(&a, sizeof a);
-              entry(ssn::RK_GRID_DOT, (it.n + 15) / 16, it.rows, xb, 0, (size_t)ao);
-              continue;
-            }
-            case IT_PES: {
-              ssn::PesArgs<T> a{it.Wm, it.aux0, it.aux1, it.rows, it.cols, it.ld, it.scalar, it.lp_dst, it.lp_src, it.lp_a, it.lp_b};
-              if (ao < 0) ao = (long long)put(&a, sizeof a);
-              entry(ssn::RK_PES, (it.cols + 1023) / 1024, (it.rows + ssn::PES_ROWS - 1) / ssn::PES_ROWS, 64, 0, (size_t)ao);
-              continue;
-            }
-            case IT_VOJA: {
-              ssn::VojaArgs<T> a{it.Wm, it.src, it.aux0, it.aux1, it.aux2, it.rows, it.cols, it.ld, it.scalar};
-              if (ao < 0) ao = (long long)put(&a, sizeof a);
-              entry(ssn::RK_VOJA, (it.rows + 4 * ssn::VOJA_ROWS_PER_WAVE - 1) / (4 * ssn::VOJA_ROWS_PER_WAVE), 1, 64, 0, (size_t)ao);
-              continue;
-            }
-            default: break;
-          }
-          Launch l; l.item = u.item; l.phase = u.phase;
-          plain.push_back(l);
-        }
-        for (const Launch& l : plain) out.push_back(l);      // the plain launches first (ensemble arrays: the long ones), then the round's grid
-        flush_entries();
-        close();
+        const Item& it = items[(size_t)u.item];
+        long long& ao = b.unit_arg[(size_t)in->unit];
+        const RoundBody body = round_body(b, it, ao);
+        if (body.kind >= 0) { entry(body.kind, body.gx, body.gy, body.lds, 0, (size_t)ao); continue; }
+        Launch l; l.item = u.item; l.phase = u.phase;
+        plain.push_back(l);
       }
-    };
+      for (const Launch& l : plain) out.push_back(l);      // the plain launches first (ensemble arrays: the long ones), then the round's grid
+      flush_entries();
+      close();
+    }
+  }
 
-    // (diagnostic) the chain of binding hazards behind the last instance of a pipelined plan: what its period is made of
-    auto print_critical_chain = [&](const std::vector<Inst>& all, const std::vector<std::vector<Rng>>& accs) {
-      size_t cur = 0;
-      for (size_t i = 0; i < all.size(); ++i) if (all[i].round >= all[cur].round) cur = i;
-      fprintf(stderr, "[ssn] critical chain (backwards from the last round):\n");
-      for (int hop = 0; hop < 70 && all[cur].round > 0; ++hop) {
-        const Unit& u = units[(size_t)all[cur].unit];
-        if (u.mop >= 0) fprintf(stderr, "[ssn]   round %3d step %2d micro %d/%lld dst %lld\n", all[cur].round, all[cur].sub, mops[(size_t)u.mop].kind, (long long)mops[(size_t)u.mop].len, (long long)mops[(size_t)u.mop].dst);
-        else if (u.item < 0) fprintf(stderr, "[ssn]   round %3d step %2d EXCHANGE\n", all[cur].round, all[cur].sub);
-        else fprintf(stderr, "[ssn]   round %3d step %2d item %d type %d rows %d cols %d\n", all[cur].round, all[cur].sub, u.item, items[(size_t)u.item].type, items[(size_t)u.item].rows, items[(size_t)u.item].cols);
-        size_t prev = cur;
+  // access lists without the clock (timesteps planned together read it with an offset; it advances once, behind the last round)
+  AccLists accesses_without_clock(const RoundBuild& b) const {
+    AccLists acc(b.units.size());
+    for (size_t u = 0; u < b.units.size(); ++u) { if (b.units[u].mop >= 0) micro_access(acc[u], mops[(size_t)b.units[u].mop], false); else acc[u] = b.units[u].acc; }
+    return acc;
+  }
+  bool is_step_end(const Unit& u) const { return u.mop >= 0 && mops[(size_t)u.mop].kind == ssn::M_STEP_END; }
+
+  // n timesteps of the units in `order`, software-pipelined: instance (u, s) takes the earliest round that its hazards against
+  // the instances of timesteps s and s - 1 allow.  Returns the number of rounds.
+  int place_steps(RoundBuild& b, const std::vector<int>& order, int n_steps, const AccLists& accs, std::vector<Inst>& all, Chains& chains) {
+    all.reserve(order.size() * (size_t)n_steps);
+    int nr = 0;
+    const size_t per = order.size();
+    for (int st = 0; st < n_steps; ++st)
+      for (size_t q = 0; q < per; ++q) {
+        const size_t lo = st > 0 ? (size_t)(st - 1) * per : 0;
+        const int r = place(b, all, lo, order[q], accs, 0, chains);
+        all.back().sub = st;
+        nr = std::max(nr, r + 1);
+      }
+    return nr;
+  }
+  // the heavy instances of such a plan spread over their slack windows (`free_unit`: a unit without cost - the exchange of a sharded cycle plan)
+  void balance(const RoundBuild& b, std::vector<Inst>& all, int nr, size_t per, const AccLists& accs, int free_unit) {
+    if (opt.has(SSN_PLAN_NO_BALANCE)) return;
+    balance_rounds(all, nr, per, [&](int x, int y) { return hazard(accs[(size_t)x], accs[(size_t)y]); },
+                   [&](int u, double* us, double* lat, int* blocks) {
+                     if (u == free_unit) { *us = 0.0; *lat = 0.0; *blocks = 0; return; }
+                     unit_cost(b.units[(size_t)u].mop, b.units[(size_t)u].item, us, lat, blocks);
+                   });
+  }
+
+  // (diagnostic) the chain of binding hazards behind the last instance of a pipelined plan: what its period is made of
+  void print_critical_chain(const RoundBuild& b, const std::vector<Inst>& all, const AccLists& accs) const {
+    size_t cur = 0;
+    for (size_t i = 0; i < all.size(); ++i) if (all[i].round >= all[cur].round) cur = i;
+    fprintf(stderr, "[ssn] critical chain (backwards from the last round):\n");
+    for (int hop = 0; hop < 70 && all[cur].round > 0; ++hop) {
+      const Unit& u = b.units[(size_t)all[cur].unit];
+      if (u.mop >= 0) fprintf(stderr, "[ssn]   round %3d step %2d micro %d/%lld dst %lld\n", all[cur].round, all[cur].sub, mops[(size_t)u.mop].kind, (long long)mops[(size_t)u.mop].len, (long long)mops[(size_t)u.mop].dst);
+      else if (u.item < 0) fprintf(stderr, "[ssn]   round %3d step %2d EXCHANGE\n", all[cur].round, all[cur].sub);
+      else fprintf(stderr, "[ssn]   round %3d step %2d item %d type %d rows %d cols %d\n", all[cur].round, all[cur].sub, u.item, items[(size_t)u.item].type, items[(size_t)u.item].rows, items[(size_t)u.item].cols);
+      size_t prev = cur;
+      for (size_t v = cur; v-- > 0;)
+        if (all[v].round == all[cur].round - 1 && hazard(accs[(size_t)all[cur].unit], accs[(size_t)all[v].unit])) { prev = v; break; }
+      if (prev == cur)          // a chain member: its predecessor sits in the same round, in the same block
         for (size_t v = cur; v-- > 0;)
-          if (all[v].round == all[cur].round - 1 && hazard(accs[(size_t)all[cur].unit], accs[(size_t)all[v].unit])) { prev = v; break; }
-        if (prev == cur)          // a chain member: its predecessor sits in the same round, in the same block
-          for (size_t v = cur; v-- > 0;)
-            if (all[v].round == all[cur].round && all[v].chain >= 0 && all[v].chain == all[cur].chain) { prev = v; break; }
-        if (prev == cur) break;
-        cur = prev;
-      }
+          if (all[v].round == all[cur].round && all[v].chain >= 0 && all[v].chain == all[cur].chain) { prev = v; break; }
+      if (prev == cur) break;
+      cur = prev;
+    }
+  }
+  // (diagnostic, SSN_DEBUG_DEPS=<round>) what every instance of the steady-state rounds waits for in the round before it (diagnostic for in-launch dependencies)
+  void print_deps(const RoundBuild& b, const std::vector<Inst>& all, const AccLists& accs) const {
+    auto name = [&](const Inst& in) {
+      const Unit& u = b.units[(size_t)in.unit];
+      char buf[160];
+      if (u.mop >= 0) snprintf(buf, sizeof buf, "micro k%d len %lld dst %lld", mops[(size_t)u.mop].kind, (long long)mops[(size_t)u.mop].len, (long long)mops[(size_t)u.mop].dst);
+      else snprintf(buf, sizeof buf, "item %d type %d rows %d cols %d n %d", u.item, items[(size_t)u.item].type, items[(size_t)u.item].rows, items[(size_t)u.item].cols, items[(size_t)u.item].n);
+      return std::string(buf);
     };
+    const int r_lo = opt.debug_deps, r_hi = r_lo + 4;
+    for (size_t i = 0; i < all.size(); ++i) {
+      if (all[i].round < r_lo || all[i].round >= r_hi) continue;
+      fprintf(stderr, "[ssn] deps: round %d step %d %s\n", all[i].round, all[i].sub, name(all[i]).c_str());
+      for (size_t v = 0; v < all.size(); ++v) {
+        if (v == i || all[v].round != all[i].round - 1) continue;
+        const std::vector<Rng>& x = accs[(size_t)all[i].unit];
+        const std::vector<Rng>& y = accs[(size_t)all[v].unit];
+        bool raw = false, war = false, waw = false;
+        for (const Rng& p : x) for (const Rng& q : y)
+          if (p.space == q.space && p.lo < q.hi && q.lo < p.hi) { if (!p.w && q.w) raw = true; if (p.w && !q.w) war = true; if (p.w && q.w) waw = true; }
+        if ((raw || war || waw) && (v < i)) fprintf(stderr, "[ssn] deps:     <- step %d %s%s%s%s\n", all[v].sub, name(all[v]).c_str(), raw ? " RAW" : "", war ? " WAR" : "", waw ? " WAW" : "");
+      }
+    }
+  }
+  void print_round_plan(const RoundBuild& b, const std::vector<Inst>& one, int n_rounds, int launches_unpipelined) const {
+    fprintf(stderr, "[ssn] round plan: %zu units in %d rounds, %d launches per timestep; %d timesteps pipelined: %d rounds, %zu launches\n",
+            b.units.size(), n_rounds, launches_unpipelined, steps_per_graph, graph_rounds, graph_list.size());
+    for (const Launch& l : launch_list) {
+      if (l.rl < 0) { const Item& it = items[(size_t)l.item]; fprintf(stderr, "[ssn]   plain item %d type %d rows %d cols %d n %d\n", l.item, it.type, it.rows, it.cols, it.n); continue; }
+      const RoundLaunch& rl = round_launches[(size_t)l.rl];
+      fprintf(stderr, "[ssn]   round %2d phase %d: %d blocks, %zu B LDS:", rl.round, l.phase, rl.n_blocks, rl.lds);
+      for (int q = 0; q < rl.args.n; ++q) fprintf(stderr, " %d[%dx%d]", rl.args.e[q].kind, rl.args.e[q].gx, rl.args.e[q].gy);
+      fprintf(stderr, "\n");
+      for (const Inst& in : one)
+        if (in.round == rl.round && b.units[(size_t)in.unit].mop >= 0) {
+          const MOp& o = mops[(size_t)b.units[(size_t)in.unit].mop];
+          fprintf(stderr, "[ssn]       micro %d/%lld dst %lld src %lld\n", o.kind, (long long)o.len, (long long)o.dst, (long long)o.src);
+        }
+    }
+    for (const Launch& l : graph_list) {
+      if (l.rl < 0) { fprintf(stderr, "[ssn]   pipelined: plain item %d type %d\n", l.item, items[(size_t)l.item].type); continue; }
+      const RoundLaunch& rl = round_launches[(size_t)l.rl];
+      fprintf(stderr, "[ssn]   pipelined round %3d: %6d blocks, %5zu B LDS:", rl.round, rl.n_blocks, rl.lds);
+      for (int q = 0; q < rl.args.n; ++q) fprintf(stderr, " %d[%d]", rl.args.e[q].kind, rl.args.e[q].cnt);
+      fprintf(stderr, "\n");
+    }
+  }
 
-    // ---- one timestep: the eager / profiled / phased sequence --------------------------------------------------------
-    std::vector<Inst> one;
+  // ---- one timestep: the eager / profiled / phased sequence --------------------------------------------------------
+  int plan_one_step(RoundBuild& b, std::vector<Inst>& one) {
     int n_rounds = 0, phase1_base = 0;
     bool in_phase1 = false;
-    std::vector<std::vector<Rng>> acc_all(units.size());
-    for (size_t u = 0; u < units.size(); ++u) acc_all[u] = units[u].acc;
-    std::vector<std::vector<int>> chains_one;
+    AccLists acc_all(b.units.size());
+    for (size_t u = 0; u < b.units.size(); ++u) acc_all[u] = b.units[u].acc;
+    Chains chains_one;
     size_t phase1_from = 0;
-    for (size_t u = 0; u < units.size(); ++u) {
-      if (units[u].phase == 1 && !in_phase1) { in_phase1 = true; phase1_base = n_rounds; phase1_from = one.size(); }
+    for (size_t u = 0; u < b.units.size(); ++u) {
+      if (b.units[u].phase == 1 && !in_phase1) { in_phase1 = true; phase1_base = n_rounds; phase1_from = one.size(); }
       // (no chain across the exchange: a phase-1 instance only sees soft hazards with phase-1 instances; hard ones with all)
-      int r = place(one, 0, (int)u, acc_all, in_phase1 ? phase1_base : 0, chains_one);
+      int r = place(b, one, 0, (int)u, acc_all, in_phase1 ? phase1_base : 0, chains_one);
       if (in_phase1 && one.back().chain >= 0 && (size_t)chains_one[(size_t)one.back().chain][0] < phase1_from) {
         // joined a chain that started before the exchange: undo, take the first round of phase 1 instead
         chains_one[(size_t)one.back().chain].pop_back();
@@ -2717,214 +2687,163 @@ struct Sim final : ssn_sim {
       n_rounds = std::max(n_rounds, r + 1);
     }
     launch_list.clear();
-    emit(one, n_rounds, launch_list, chains_one);
+    emit(b, one, n_rounds, launch_list, chains_one);
     n_serial_chains = 0;
     for (size_t c = 0; c < chains_one.size(); ++c) if (chains_one[c].size() >= 2 && one[(size_t)chains_one[c][0]].solo) n_serial_chains += 1;
     launches_per_step = (int)launch_list.size();
-    const int launches_unpipelined = launches_per_step;
+    return n_rounds;
+  }
 
-    // ---- G timesteps software-pipelined: the sequence a step graph replays -------------------------------------------
-    // Instance (u, s) takes the earliest round that its hazards against the instances of timesteps s and s - 1 allow
-    // (a writer conflicts with itself one step earlier, so older steps are ordered transitively).  The recurrence of a
-    // SLAM step runs through synapse states only: the long un-filtered chain of step s (two circular convolutions in
-    // series) ends in filter updates that step s + 1 reads only to update other filters, so the head of step s + 1 -
-    // the bandwidth-bound oscillators and encoder products - runs in the rounds where step s has one latency-bound
-    // workgroup left.  Clock readers take the step number from StepCtx plus their own offset; the clock itself
-    // advances once, behind the last round (k_advance).
+  // ---- G timesteps software-pipelined: the sequence a step graph replays -------------------------------------------
+  // Instance (u, s) takes the earliest round that its hazards against the instances of timesteps s and s - 1 allow
+  // (a writer conflicts with itself one step earlier, so older steps are ordered transitively).  The recurrence of a
+  // SLAM step runs through synapse states only: the long un-filtered chain of step s (two circular convolutions in
+  // series) ends in filter updates that step s + 1 reads only to update other filters, so the head of step s + 1 -
+  // the bandwidth-bound oscillators and encoder products - runs in the rounds where step s has one latency-bound
+  // workgroup left.  Clock readers take the step number from StepCtx plus their own offset; the clock itself
+  // advances once, behind the last round (k_advance).
+  void plan_pipelined(RoundBuild& b) {
     graph_list.clear();
     graph_rounds = 0;
     const int G = steps_per_graph;
-    if (!phased && G > 1 && !(flags & 8388608) && units.size() * (size_t)G <= 40000) {
-      std::vector<int> keep;
-      for (size_t u = 0; u < units.size(); ++u)
-        if (!(units[u].mop >= 0 && mops[(size_t)units[u].mop].kind == ssn::M_STEP_END)) keep.push_back((int)u);
-      std::vector<std::vector<Rng>> acc_nc(units.size());     // access lists without the clock
-      for (int u : keep) { if (units[(size_t)u].mop >= 0) micro_access(acc_nc[(size_t)u], mops[(size_t)units[(size_t)u].mop], false); else acc_nc[(size_t)u] = units[(size_t)u].acc; }
-      std::vector<Inst> all;
-      std::vector<std::vector<int>> chains_all;
-      all.reserve(keep.size() * (size_t)G);
-      int nr = 0;
-      const size_t per = keep.size();
-      for (int st = 0; st < G; ++st)
-        for (size_t q = 0; q < per; ++q) {
-          const int u = keep[q];
-          const size_t lo = st > 0 ? (size_t)(st - 1) * per : 0;
-          const int r = place(all, lo, u, acc_nc, 0, chains_all);
-          all.back().sub = st;
-          nr = std::max(nr, r + 1);
-        }
-      if (getenv("SSN_DEBUG_PLAN")) print_critical_chain(all, acc_nc);
-      if (getenv("SSN_DEBUG_DEPS")) {
-        // what every instance of the steady-state rounds waits for in the round before it (diagnostic for in-launch dependencies)
-        auto name = [&](const Inst& in) {
-          const Unit& u = units[(size_t)in.unit];
-          char buf[160];
-          if (u.mop >= 0) snprintf(buf, sizeof buf, "micro k%d len %lld dst %lld", mops[(size_t)u.mop].kind, (long long)mops[(size_t)u.mop].len, (long long)mops[(size_t)u.mop].dst);
-          else snprintf(buf, sizeof buf, "item %d type %d rows %d cols %d n %d", u.item, items[(size_t)u.item].type, items[(size_t)u.item].rows, items[(size_t)u.item].cols, items[(size_t)u.item].n);
-          return std::string(buf);
-        };
-        const int r_lo = atoi(getenv("SSN_DEBUG_DEPS")), r_hi = r_lo + 4;
-        for (size_t i = 0; i < all.size(); ++i) {
-          if (all[i].round < r_lo || all[i].round >= r_hi) continue;
-          fprintf(stderr, "[ssn] deps: round %d step %d %s\n", all[i].round, all[i].sub, name(all[i]).c_str());
-          for (size_t v = 0; v < all.size(); ++v) {
-            if (v == i || all[v].round != all[i].round - 1) continue;
-            const std::vector<Rng>& x = acc_nc[(size_t)all[i].unit];
-            const std::vector<Rng>& y = acc_nc[(size_t)all[v].unit];
-            bool raw = false, war = false, waw = false;
-            for (const Rng& p : x) for (const Rng& q : y)
-              if (p.space == q.space && p.lo < q.hi && q.lo < p.hi) { if (!p.w && q.w) raw = true; if (p.w && !q.w) war = true; if (p.w && q.w) waw = true; }
-            if ((raw || war || waw) && (v < i)) fprintf(stderr, "[ssn] deps:     <- step %d %s%s%s%s\n", all[v].sub, name(all[v]).c_str(), raw ? " RAW" : "", war ? " WAR" : "", waw ? " WAW" : "");
-          }
-        }
-      }
-      if (!(flags & 16777216)) balance_rounds(all, nr, per, [&](int a, int b) { return hazard(acc_nc[(size_t)a], acc_nc[(size_t)b]); },
-                                              [&](int u, double* us, double* lat, int* blocks) { unit_cost(units[(size_t)u].mop, units[(size_t)u].item, us, lat, blocks); });
-      emit(all, nr, graph_list, chains_all);
-      graph_rounds = nr;
-      launches_per_step = ((int)graph_list.size() + G - 1) / G;       // (average of the replayed sequence)
-    }
+    if (phased || G <= 1 || opt.has(SSN_PLAN_NO_PIPELINE) || b.units.size() * (size_t)G > 40000) return;
+    std::vector<int> keep;
+    for (size_t u = 0; u < b.units.size(); ++u) if (!is_step_end(b.units[u])) keep.push_back((int)u);
+    const AccLists acc_nc = accesses_without_clock(b);
+    std::vector<Inst> all;
+    Chains chains_all;
+    const int nr = place_steps(b, keep, G, acc_nc, all, chains_all);
+    if (opt.debug_plan) print_critical_chain(b, all, acc_nc);
+    if (opt.debug_deps != PlanOptions::UNSET) print_deps(b, all, acc_nc);
+    balance(b, all, nr, keep.size(), acc_nc, -1);
+    emit(b, all, nr, graph_list, chains_all);
+    graph_rounds = nr;
+    launches_per_step = ((int)graph_list.size() + G - 1) / G;       // (average of the replayed sequence)
+  }
 
-    // ---- neuron-sharded models: what runs between two exchanges - the updates of timestep s (phase 1) and timestep s + 1 up to
-    // its exchange (phase 0) - as ONE set of rounds.  A phase-0 operator of s + 1 waits only for the phase-1 operators whose
-    // results it reads: table rows, the encoder products of tabulated inputs and whatever else does not hang on a filter state
-    // start beside the filter updates, PES and Voja instead of behind them.  The clock is read with an offset (phase-0
-    // instances: + 1) and advanced once behind the last round, as in the pipelined step graph.
+  // ---- neuron-sharded models: what runs between two exchanges - the updates of timestep s (phase 1) and timestep s + 1 up to
+  // its exchange (phase 0) - as ONE set of rounds.  A phase-0 operator of s + 1 waits only for the phase-1 operators whose
+  // results it reads: table rows, the encoder products of tabulated inputs and whatever else does not hang on a filter state
+  // start beside the filter updates, PES and Voja instead of behind them.  The clock is read with an offset (phase-0
+  // instances: + 1) and advanced once behind the last round, as in the pipelined step graph.
+  void plan_phase2(RoundBuild& b) {
     phase2_list.clear();
-    if (phased && !(flags & 8388608) && !getenv("SSN_PHASE2_SEQUENTIAL")) {
-      std::vector<std::vector<Rng>> acc_p(units.size());
-      for (size_t u = 0; u < units.size(); ++u) { if (units[u].mop >= 0) micro_access(acc_p[u], mops[(size_t)units[u].mop], false); else acc_p[u] = units[u].acc; }
-      std::vector<Inst> comb;
-      std::vector<std::vector<int>> chains_comb;
-      int nr = 0;
-      for (int ph = 1; ph >= 0; --ph)
-        for (size_t u = 0; u < units.size(); ++u) {
-          if (units[u].phase != ph) continue;
-          if (units[u].mop >= 0 && mops[(size_t)units[u].mop].kind == ssn::M_STEP_END) continue;
-          const int r = place(comb, 0, (int)u, acc_p, 0, chains_comb);
-          comb.back().sub = ph == 0 ? 1 : 0;
-          nr = std::max(nr, r + 1);
-        }
-      emit(comb, nr, phase2_list, chains_comb);
-      if (getenv("SSN_DEBUG_PLAN")) fprintf(stderr, "[ssn] phased plan: %zu launches per timestep apart (phase 0 + phase 1), %zu with the updates of s and the head of s + 1 planned together\n", launch_list.size(), phase2_list.size());
-      launches_per_step = (int)phase2_list.size();
-    }
+    if (!phased || opt.has(SSN_PLAN_NO_PIPELINE) || opt.phase2_sequential) return;
+    const AccLists acc_p = accesses_without_clock(b);
+    std::vector<Inst> comb;
+    Chains chains_comb;
+    int nr = 0;
+    for (int ph = 1; ph >= 0; --ph)
+      for (size_t u = 0; u < b.units.size(); ++u) {
+        if (b.units[u].phase != ph || is_step_end(b.units[u])) continue;
+        const int r = place(b, comb, 0, (int)u, acc_p, 0, chains_comb);
+        comb.back().sub = ph == 0 ? 1 : 0;
+        nr = std::max(nr, r + 1);
+      }
+    emit(b, comb, nr, phase2_list, chains_comb);
+    if (opt.debug_plan) fprintf(stderr, "[ssn] phased plan: %zu launches per timestep apart (phase 0 + phase 1), %zu with the updates of s and the head of s + 1 planned together\n", launch_list.size(), phase2_list.size());
+    launches_per_step = (int)phase2_list.size();
+  }
 
-    // ---- neuron-sharded models, pipelined over the exchange (round 4).  The plan above still starts every
-    // timestep from an empty chip behind its exchange: ten rounds per timestep, none of them shared with another timestep.  Here
-    // the exchange of timestep s is a unit of the plan like any other - it reads and writes the exchanged signal ranges, so the
-    // operators that complete the partial sums come before it and their consumers (synapse filters, probes) behind it - and C
-    // timesteps are placed together as in the unsharded step graph: what does not hang on the exchange of s (the head of
-    // s + 1: tabulated inputs, encoder products, neuron updates of populations whose input is ready) shares rounds with the
-    // tail of s.  The launch sequence is cut at the exchanges into C + 1 segments; the caller runs segment, all-reduce,
-    // segment, ... (phase 3), the clock advances by C behind the last one.  SSN_CYCLE_STEPS: C (default 16; 0: off).
+  // ---- neuron-sharded models, pipelined over the exchange (round 4).  The plan above still starts every
+  // timestep from an empty chip behind its exchange: ten rounds per timestep, none of them shared with another timestep.  Here
+  // the exchange of timestep s is a unit of the plan like any other - it reads and writes the exchanged signal ranges, so the
+  // operators that complete the partial sums come before it and their consumers (synapse filters, probes) behind it - and C
+  // timesteps are placed together as in the unsharded step graph: what does not hang on the exchange of s (the head of
+  // s + 1: tabulated inputs, encoder products, neuron updates of populations whose input is ready) shares rounds with the
+  // tail of s.  The launch sequence is cut at the exchanges into C + 1 segments; the caller runs segment, all-reduce,
+  // segment, ... (phase 3), the clock advances by C behind the last one.  SSN_CYCLE_STEPS: C (default 16; 0: off).
+  void plan_cycle(RoundBuild& b) {
     cycle_segs.clear();
     cycle_steps = 0;
-    {
-      const int C = getenv("SSN_CYCLE_STEPS") ? atoi(getenv("SSN_CYCLE_STEPS")) : 16;
-      if (phased && C > 1 && C <= 64 && !(flags & 8388608) && (units.size() + 1) * (size_t)C <= 40000) {
-        const int xu = (int)units.size();
-        {
-          Unit x; x.phase = 0; x.writes = true;
-          for (auto& r : exchange) x.acc.push_back(Rng{(const void*)sig, (int64_t)r.lo, (int64_t)r.hi, true});
-          units.push_back(std::move(x));
-          unit_arg.push_back(-1);
-        }
-        std::vector<std::vector<Rng>> acc_c(units.size());
-        std::vector<int> order;              // program order of one timestep with the exchange between its phases
-        bool seen1 = false;
-        for (int u = 0; u < xu; ++u) {
-          if (units[(size_t)u].mop >= 0) micro_access(acc_c[(size_t)u], mops[(size_t)units[(size_t)u].mop], false); else acc_c[(size_t)u] = units[(size_t)u].acc;
-          if (units[(size_t)u].mop >= 0 && mops[(size_t)units[(size_t)u].mop].kind == ssn::M_STEP_END) continue;
-          if (units[(size_t)u].phase == 1 && !seen1) { seen1 = true; order.push_back(xu); }
-          order.push_back(u);
-        }
-        acc_c[(size_t)xu] = units[(size_t)xu].acc;
-        if (seen1) {
-          std::vector<Inst> all;
-          std::vector<std::vector<int>> chains_c;
-          int nr = 0;
-          const size_t per = order.size();
-          for (int st = 0; st < C; ++st)
-            for (size_t q = 0; q < per; ++q) {
-              const size_t lo = st > 0 ? (size_t)(st - 1) * per : 0;
-              const int r = place(all, lo, order[q], acc_c, 0, chains_c);
-              all.back().sub = st;
-              nr = std::max(nr, r + 1);
-            }
-          if (!(flags & 16777216))
-            balance_rounds(all, nr, per, [&](int a, int b) { return hazard(acc_c[(size_t)a], acc_c[(size_t)b]); },
-                           [&](int u, double* us, double* lat, int* blocks) {
-                             if (u == xu) { *us = 0.0; *lat = 0.0; *blocks = 0; return; }
-                             unit_cost(units[(size_t)u].mop, units[(size_t)u].item, us, lat, blocks);
-                           });
-          if (getenv("SSN_DEBUG_PLAN")) print_critical_chain(all, acc_c);
-          std::vector<Launch> seq;
-          emit(all, nr, seq, chains_c);
-          cycle_segs.emplace_back();
-          for (const Launch& l : seq) {
-            if (l.phase == -2) { cycle_segs.emplace_back(); continue; }
-            cycle_segs.back().push_back(l);
-          }
-          if ((int)cycle_segs.size() == C + 1) {
-            cycle_steps = C;
-            launches_per_step = ((int)(seq.size() - (size_t)C) + C - 1) / C;       // (average over the cycle)
-            if (getenv("SSN_DEBUG_PLAN")) {
-              fprintf(stderr, "[ssn] sharded plan pipelined over the exchange: %d timesteps in %d rounds, %zu launches, segments:", C, nr, seq.size() - (size_t)C);
-              for (auto& sg : cycle_segs) fprintf(stderr, " %zu", sg.size());
-              fprintf(stderr, "\n");
-            }
-          } else {
-            cycle_segs.clear();
-          }
-        }
-        units.pop_back();
-        unit_arg.pop_back();
-      }
+    const int C = opt.cycle_steps;
+    if (!(phased && C > 1 && C <= 64 && !opt.has(SSN_PLAN_NO_PIPELINE) && (b.units.size() + 1) * (size_t)C <= 40000)) return;
+    const int xu = (int)b.units.size();      // (the exchange's unit, below)
+    std::vector<int> order;              // program order of one timestep with the exchange between its phases
+    bool seen1 = false;
+    for (int u = 0; u < xu; ++u) {
+      if (is_step_end(b.units[(size_t)u])) continue;
+      if (b.units[(size_t)u].phase == 1 && !seen1) { seen1 = true; order.push_back(xu); }
+      order.push_back(u);
     }
+    if (!seen1) return;
+    {
+      Unit x; x.phase = 0; x.writes = true;
+      for (auto& r : exchange) x.acc.push_back(Rng{(const void*)sig, (int64_t)r.lo, (int64_t)r.hi, true});
+      b.units.push_back(std::move(x));
+      b.unit_arg.push_back(-1);
+    }
+    const AccLists acc_c = accesses_without_clock(b);
+    std::vector<Inst> all;
+    Chains chains_c;
+    const int nr = place_steps(b, order, C, acc_c, all, chains_c);
+    balance(b, all, nr, order.size(), acc_c, xu);
+    if (opt.debug_plan) print_critical_chain(b, all, acc_c);
+    std::vector<Launch> seq;
+    emit(b, all, nr, seq, chains_c);
+    cycle_segs.emplace_back();
+    for (const Launch& l : seq) {
+      if (l.phase == -2) { cycle_segs.emplace_back(); continue; }
+      cycle_segs.back().push_back(l);
+    }
+    if ((int)cycle_segs.size() == C + 1) {
+      cycle_steps = C;
+      launches_per_step = ((int)(seq.size() - (size_t)C) + C - 1) / C;       // (average over the cycle)
+      if (opt.debug_plan) {
+        fprintf(stderr, "[ssn] sharded plan pipelined over the exchange: %d timesteps in %d rounds, %zu launches, segments:", C, nr, seq.size() - (size_t)C);
+        for (auto& sg : cycle_segs) fprintf(stderr, " %zu", sg.size());
+        fprintf(stderr, "\n");
+      }
+    } else {
+      cycle_segs.clear();
+    }
+    b.units.pop_back();
+    b.unit_arg.pop_back();
+  }
 
+  // device copies of the arena, the glue map and the chain table; the round entries get their pointers
+  int upload_round_tables(const RoundBuild& b) {
     T* d_arena = nullptr; ssn::GlueBlock* d_map = nullptr;
-    CHK(dmalloc(&d_arena, (int64_t)arena.size() + 16));
+    CHK(dmalloc(&d_arena, (int64_t)b.arena.size() + 16));
     round_bufs.push_back(d_arena);
-    CHK(dmalloc(&d_map, (int64_t)(glue_map.size() + 1) * (int64_t)sizeof(ssn::GlueBlock)));
+    CHK(dmalloc(&d_map, (int64_t)(b.glue_map.size() + 1) * (int64_t)sizeof(ssn::GlueBlock)));
     round_bufs.push_back(d_map);
-    if (!arena.empty()) HIPCHK(hipMemcpy(d_arena, arena.data(), arena.size(), hipMemcpyHostToDevice));
-    if (!glue_map.empty()) HIPCHK(hipMemcpy(d_map, glue_map.data(), glue_map.size() * sizeof(ssn::GlueBlock), hipMemcpyHostToDevice));
+    if (!b.arena.empty()) HIPCHK(hipMemcpy(d_arena, b.arena.data(), b.arena.size(), hipMemcpyHostToDevice));
+    if (!b.glue_map.empty()) HIPCHK(hipMemcpy(d_map, b.glue_map.data(), b.glue_map.size() * sizeof(ssn::GlueBlock), hipMemcpyHostToDevice));
     int* d_chain = nullptr;
-    CHK(dmalloc(&d_chain, (int64_t)(chain_tab.size() + 1) * 4));
+    CHK(dmalloc(&d_chain, (int64_t)(b.chain_tab.size() + 1) * 4));
     round_bufs.push_back(d_chain);
-    if (!chain_tab.empty()) HIPCHK(hipMemcpy(d_chain, chain_tab.data(), chain_tab.size() * 4, hipMemcpyHostToDevice));
+    if (!b.chain_tab.empty()) HIPCHK(hipMemcpy(d_chain, b.chain_tab.data(), b.chain_tab.size() * 4, hipMemcpyHostToDevice));
     for (RoundLaunch& rl : round_launches) { rl.args.chain = d_chain; rl.args.arena = (const unsigned char*)d_arena; }
-    for (const Fix& f : fixes) {
+    for (const Fix& f : b.fixes) {
       ssn::RoundEntry& e = round_launches[f.rl].args.e[f.entry];
       if (f.what == 0) e.args = (const unsigned char*)d_arena + f.off;
       else if (f.what == 1) e.args = d_map + f.off;
       else if (f.what == 3) e.args = d_chain + f.off;
       else e.args = d_mops + f.off;
     }
-    if (getenv("SSN_DEBUG_PLAN")) {
-      fprintf(stderr, "[ssn] round plan: %zu units in %d rounds, %d launches per timestep; %d timesteps pipelined: %d rounds, %zu launches\n",
-              units.size(), n_rounds, launches_unpipelined, G, graph_rounds, graph_list.size());
-      for (const Launch& l : launch_list) {
-        if (l.rl < 0) { const Item& it = items[(size_t)l.item]; fprintf(stderr, "[ssn]   plain item %d type %d rows %d cols %d n %d\n", l.item, it.type, it.rows, it.cols, it.n); continue; }
-        const RoundLaunch& rl = round_launches[(size_t)l.rl];
-        fprintf(stderr, "[ssn]   round %2d phase %d: %d blocks, %zu B LDS:", rl.round, l.phase, rl.n_blocks, rl.lds);
-        for (int q = 0; q < rl.args.n; ++q) fprintf(stderr, " %d[%dx%d]", rl.args.e[q].kind, rl.args.e[q].gx, rl.args.e[q].gy);
-        fprintf(stderr, "\n");
-        for (const Inst& in : one)
-          if (in.round == rl.round && units[(size_t)in.unit].mop >= 0) {
-            const MOp& o = mops[(size_t)units[(size_t)in.unit].mop];
-            fprintf(stderr, "[ssn]       micro %d/%lld dst %lld src %lld\n", o.kind, (long long)o.len, (long long)o.dst, (long long)o.src);
-          }
-      }
-      for (const Launch& l : graph_list) {
-        if (l.rl < 0) { fprintf(stderr, "[ssn]   pipelined: plain item %d type %d\n", l.item, items[(size_t)l.item].type); continue; }
-        const RoundLaunch& rl = round_launches[(size_t)l.rl];
-        fprintf(stderr, "[ssn]   pipelined round %3d: %6d blocks, %5zu B LDS:", rl.round, rl.n_blocks, rl.lds);
-        for (int q = 0; q < rl.args.n; ++q) fprintf(stderr, " %d[%d]", rl.args.e[q].kind, rl.args.e[q].cnt);
-        fprintf(stderr, "\n");
-      }
-    }
+    return SSN_OK;
+  }
+
+  int build_rounds(const std::vector<std::vector<MOp>>& programs_in, const std::vector<int>& item_prog) {
+    std::vector<std::vector<MOp>> programs = programs_in;
+    RoundBuild b;
+    // rewrites of the operator list
+    fold_pes_filters(programs, item_prog);
+    CHK(fuse_product_neurons(programs, item_prog));
+    // units (micro-operators cut at the other operators' range endpoints), the micro-operators on the device
+    CHK(make_units(b, programs, item_prog));
+    // launch sequences: one timestep; steps_per_graph timesteps pipelined; sharded models: what runs between two exchanges, and
+    // cycle_steps timesteps pipelined over the exchange
+    round_launches.clear();
+    std::vector<Inst> one;
+    const int n_rounds = plan_one_step(b, one);
+    const int launches_unpipelined = launches_per_step;
+    plan_pipelined(b);
+    plan_phase2(b);
+    plan_cycle(b);
+    CHK(upload_round_tables(b));
+    if (opt.debug_plan) print_round_plan(b, one, n_rounds, launches_unpipelined);
     return SSN_OK;
   }
 
@@ -3120,7 +3039,7 @@ struct Sim final : ssn_sim {
   // operators are sorted by level and kind, and neighbouring scans with equal coefficients over adjacent ranges are joined
   // again.  run_batch then packs consecutive element-wise operators - also dependent ones, see batch_hazard - into launches.
   void optimise_batch(std::vector<ssn::BatchOp<T>>& ops) {
-    if (ops.size() < 2 || getenv("SSN_NO_BATCH_REORDER")) return;
+    if (ops.size() < 2 || opt.no_batch_reorder) return;
     typedef ssn::BatchOp<T> Op;
     std::vector<long long> cuts;
     for (const Op& o : ops) {
@@ -3173,7 +3092,7 @@ struct Sim final : ssn_sim {
       out.push_back(o);
       last_level = level[k];
     }
-    if (getenv("SSN_DEBUG_PLAN")) {
+    if (opt.debug_plan) {
       fprintf(stderr, "[ssn] time-batched stage: %zu operators -> %zu\n", ops.size(), out.size());
       for (const Op& o : out) fprintf(stderr, "[ssn]   batch op kind %d dst %lld src %lld len %lld cols %d prev %d\n", o.kind, (long long)o.dst, (long long)o.src, (long long)o.len, o.cols, o.src_prev);
     }
@@ -3187,7 +3106,7 @@ struct Sim final : ssn_sim {
     // copies / products make of zeros.  A product whose whole input is zero is not multiplied out (PathIntegration config 2:
     // the 1000 x 1015 x 1524 to_Fourier GEMM of every block but the first - 47 of a block's 3480 us).
     std::vector<char> zero((size_t)n_sig, 0);
-    const bool track = !getenv("SSN_NO_ZERO_SKIP");
+    const bool track = !opt.no_zero_skip;
     auto all_zero = [&](long long lo, long long n) { for (long long q = lo; q < lo + n; ++q) if (!zero[(size_t)q]) return false; return n > 0; };
     auto set_zero = [&](long long lo, long long n, bool v) { for (long long q = lo; q < lo + n; ++q) zero[(size_t)q] = v ? 1 : 0; };
     auto note = [&](const ssn::BatchOp<T>& o) {              // effect of an operator that IS executed on the zero map
@@ -3208,7 +3127,7 @@ struct Sim final : ssn_sim {
     };
     for (size_t i = 0; i < ops.size();) {
       ops[i].B = B; ops[i].step0 = step0;
-      if (elementwise(ops[i]) && !(flags & 262144)) {
+      if (elementwise(ops[i]) && !opt.has(SSN_PLAN_NO_STAGE_BATCH)) {
         // consecutive element-wise operators share one launch unless a hazard between them crosses threads (batch_hazard)
         ssn::BatchOpList<T> l{};
         l.op[0] = ops[i];
@@ -3699,7 +3618,7 @@ struct Sim final : ssn_sim {
       dom_ms += ms;
       dom_launches += 1;
     }
-    if (profile == 2 && getenv("SSN_DEBUG_PLAN")) {
+    if (profile == 2 && opt.debug_plan) {
       // diagnostic build (F32_EXTRA=-DSSN_PROGRAM_STAMPS): shader cycles each operator of each program took in the last timestep
       typedef int (*stamp_fn)(unsigned long long*, int);
       if (stamp_fn fn = (stamp_fn)dlsym(RTLD_DEFAULT, "ssn_debug_program_stamps")) {
@@ -3720,7 +3639,7 @@ struct Sim final : ssn_sim {
           }
       }
     }
-    if (profile == 2 && getenv("SSN_DEBUG_PLAN"))
+    if (profile == 2 && opt.debug_plan)
       for (size_t i = 0; i < item_ms.size(); ++i)
         if (item_n[i]) {
           if (i < items.size()) fprintf(stderr, "[ssn] item %2zu type %2d batch %d: %8.2f us avg over %lld launches\n", i, items[i].type, items[i].batch,
@@ -3766,7 +3685,6 @@ struct Sim final : ssn_sim {
     dom_launches = 0; dom_ms = 0.0;
     for (int t = 0; t < N_ITEM_TYPES; ++t) { type_ms[t] = 0.0; type_launches[t] = 0; }
     if (fused_block && blk.slot_stats) HIPCHK(hipMemset(blk.slot_stats, 0, 16));
-    for (auto& z : zero_on_reset) HIPCHK(hipMemset(z.first, 0, z.second));
     return SSN_OK;
   }
 
@@ -3983,7 +3901,7 @@ struct Sim final : ssn_sim {
 
 template <typename T>
 int create_sim(const ssn_model_desc* desc, ssn_sim** out) {
-  auto s = std::make_unique<Sim<T>>();
+  auto s = std::make_unique<Sim<T>>(desc);
   int rc = s->create(desc);
   if (rc != SSN_OK) return rc;
   *out = s.release();
@@ -3998,6 +3916,8 @@ int ssn_create(const ssn_model_desc* desc, ssn_sim** out) {
   if (!desc || !out) return fail(SSN_EINVAL, "null argument");
   *out = nullptr;
   if (desc->abi_version != SSN_ABI_VERSION) return fail(SSN_EINVAL, "ABI version %d != %d", desc->abi_version, SSN_ABI_VERSION);
+  if (desc->flags & ~SSN_PLAN_ALL_FLAGS)
+    return fail(SSN_EINVAL, "flags %d: the bits %d are no plan switch (ssn_plan_flag in ssn.h)", desc->flags, desc->flags & ~SSN_PLAN_ALL_FLAGS);
   if (desc->n_signals <= 0 || !desc->signal_init || desc->n_ops <= 0 || !desc->ops || desc->dt <= 0)
     return fail(SSN_EINVAL, "empty or inconsistent model description");
   int ndev = 0;

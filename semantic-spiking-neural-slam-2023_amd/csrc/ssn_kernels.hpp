@@ -158,7 +158,7 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
   long long step = 0;
   if (a.xrows || a.defer) step = a.ctx->step + a.sub;
   // (the self-finishing form exists in the round grid only: in the stand-alone kernel - config 4's - its branch cost 1 %)
-  if (RND && a.defer == 2) {
+  if (RND && a.defer == 2) {      // (no host path sets defer == 2 any more: the self-finishing array was removed from the planner)
     // Round plan (round 4): the array completes ITS OWN previous timestep.  Every workgroup of ensemble k sums the P partial
     // sums that the ensemble's workgroups left at timestep s - 1 for the rows that feed its inputs, advances the recurrent
     // filter states (identical values in every workgroup; workgroup p = 0 keeps them: fstate ping-pongs by timestep parity)
@@ -2270,7 +2270,7 @@ namespace ssn {
 #define SSN_INSTANTIATE(T)                                                                                   \
   template hipError_t launch_ens_block<T>(hipStream_t, const BlockArgs<T>&);                                 \
   template hipError_t launch_dft<T>(hipStream_t, const DftBatch&, int);                                            \
-  template bool ens_block_supported<T>(int, int, int, int*, int*, int*, int*);                                         \
+  template bool ens_block_supported<T>(int, int, int, const int*, int*, int*, int*, int*);                             \
   template hipError_t launch_ensarray<T>(hipStream_t, const EnsArgs<T>&);                                    \
   template hipError_t launch_ensarray_batch<T>(hipStream_t, const EnsBatch<T>&, int);                        \
   template hipError_t launch_dec_pack<T>(hipStream_t, const T*, T*, int, int, int, int, int, int);           \

@@ -315,7 +315,7 @@ template <typename T> hipError_t launch_state_unpack(hipStream_t, const T* src, 
 template <typename T> hipError_t launch_ens_finish(hipStream_t, const FinishArgs<T>&);
 template <typename T> hipError_t launch_dft(hipStream_t, const DftBatch&, int count);   // (T only selects the translation unit)
 template <typename T> hipError_t launch_ens_block(hipStream_t, const BlockArgs<T>&);
-template <typename T> bool ens_block_supported(int din, int dout, int n, int* threads, int* tpb, int* npt, int* enc_lds);
+template <typename T> bool ens_block_supported(int din, int dout, int n, const int want[3], int* threads, int* tpb, int* npt, int* enc_lds);
 template <typename T> hipError_t launch_program(hipStream_t, const MicroOp<T>* ops, const ProgDesc* progs, int n_progs, T* sig, StepCtx* ctx);
 template <typename T> hipError_t launch_vecops(hipStream_t, const MicroOp<T>* ops, int n_ops, int wgs, T* sig, const StepCtx* ctx);
 template <typename T> hipError_t launch_matvec(hipStream_t, const MatvecBatch<T>&, int count);

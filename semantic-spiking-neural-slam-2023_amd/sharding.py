@@ -22,6 +22,7 @@ import threading
 
 import numpy as np
 
+from . import _lib
 from . import frontend as nengo
 from .modelcache import cached_build as build      # (a rank's shard is keyed by its (rank, world) like any other build argument)
 
@@ -141,9 +142,9 @@ class ShardedPathIntegration:
             raise nengo.BuildError("this simulator factory takes no plan switches (flags=%d asked for)" % flags)
         return self._sim_factory(model)
 
-    def choose_plan(self, candidates=(0, 128), steps=None):
+    def choose_plan(self, candidates=(0, _lib.SSN_PLAN_NO_BLOCK_KERNEL), steps=None):
         """Time one block of this rank's shard under each candidate plan (simulator flags: 0 = the planner's choice -
-        the whole-block kernel k_ens_block where a VCO fits one workgroup; 128 = one k_ensarray launch per timestep,
+        the whole-block kernel k_ens_block where a VCO fits one workgroup; SSN_PLAN_NO_BLOCK_KERNEL = one k_ensarray launch per timestep,
         which splits an ensemble over several workgroups and so fills the chip when a shard has fewer VCOs than the GPU
         has CUs) and keep the fastest.  Decided collectively - the slowest rank's time counts - so every rank must call
         it, before ``prepare``.  Returns {flags: seconds per block}."""

@@ -22,6 +22,13 @@ import time
 import numpy as np
 
 from . import _lib
+from ._lib import (  # noqa: F401  (plan switches, for the callers of Simulator(flags=...))
+    SSN_PLAN_NO_FUSED_CORE, SSN_PLAN_NO_LIF_FAST, SSN_PLAN_DENSE_DECODERS, SSN_PLAN_NO_SPMV, SSN_PLAN_SEPARATE_FINISH,
+    SSN_PLAN_NO_BLOCK_KERNEL, SSN_PLAN_NO_FFT, SSN_PLAN_SPMV_OWN_LIST, SSN_PLAN_NO_ITEM_BATCH, SSN_PLAN_ENS_PARTIALS,
+    SSN_PLAN_NO_STAGE_BATCH, SSN_PLAN_NO_FACTORED_GRID, SSN_PLAN_NO_ROUNDS, SSN_PLAN_ENS_OWN_LAUNCH,
+    SSN_PLAN_NO_PIPELINE, SSN_PLAN_NO_BALANCE, SSN_PLAN_NO_CUTS, SSN_PLAN_NO_CHAINS, SSN_PLAN_BLUESTEIN_FFT,
+    SSN_PLAN_FOUR_STEP_FFT, SSN_PLAN_SPLIT_BLOCK,
+    PLAN_FLAGS)
 from . import frontend as fe
 from .builder import BuiltModel, build
 

@@ -75,3 +75,20 @@ def test_pack_model_encodes_ops():
     assert [desc.ops[j].i[a] for a in (1, 2, 3, 4)] == [e["K"], e["n"], e["din"], e["dout"]]
     assert abs(desc.ops[j].f[0] - 0.02) < 1e-15 and abs(desc.ops[j].f[1] - 0.002) < 1e-15
     assert len(sig_probes) == 1 and desc.probes[0].width == 7
+
+
+def test_plan_flags_match_header():
+    """The plan switches of _lib.py (re-exported by the simulator module) are the enum ssn_plan_flag of include/ssn.h, name for
+    name and value for value, and SSN_PLAN_ALL_FLAGS names every one of them."""
+    from sspslam_amd import simulator
+    hdr = open(os.path.join(ROOT, "include", "ssn.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    body = re.search(r"enum\s+ssn_plan_flag\s*\{(.*?)\}", hdr, flags=re.S).group(1)
+    in_header = {n: int(v) for n, v in re.findall(r"\b(SSN_PLAN_[A-Z0-9_]+)\s*=\s*(\d+)", body)}
+    assert len(in_header) == 21 and in_header == _lib.PLAN_FLAGS, set(in_header.items()) ^ set(_lib.PLAN_FLAGS.items())
+    assert len(set(in_header.values())) == 21 and all(v & (v - 1) == 0 for v in in_header.values())      # one bit each
+    assert in_header["SSN_PLAN_NO_BLOCK_KERNEL"] == 128          # (what bench.py passes for --plan stream)
+    for n, v in in_header.items():
+        assert getattr(_lib, n) == v and getattr(simulator, n) == v
+    all_flags = re.search(r"#define\s+SSN_PLAN_ALL_FLAGS((?:.*\\\n)*.*)", hdr).group(1)
+    assert set(re.findall(r"SSN_PLAN_[A-Z0-9_]+", all_flags)) == set(in_header)

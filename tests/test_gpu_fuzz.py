@@ -10,6 +10,7 @@ import pytest
 
 import sspslam_amd.frontend as nengo
 from sspslam_amd.builder import build
+from sspslam_amd import simulator as PLAN
 from oracle import OracleSimulator
 
 from helpers import random_network
@@ -103,7 +104,7 @@ def test_random_network_learned_decoders_and_encoders_match_oracle(Simulator, se
 def test_random_network_under_the_opt_in_plans(Simulator, seed):
     """The same networks with the planner's size thresholds and switches moved so that small graphs take the paths of big ones:
     every dense population's neuron update fused into its encoder product (SSN_FUSE_MIN_ROWS=1), transforms allowed into serial
-    chains with a generous cap, 16 timesteps per graph, and the one-launch-per-operator plan of round 1 (flag 2097152)."""
+    chains with a generous cap, 16 timesteps per graph, and the one-launch-per-operator plan of round 1 (SSN_PLAN_NO_ROUNDS)."""
     import os
     net, probes = random_network(seed)
     model = build(net)
@@ -113,7 +114,7 @@ def test_random_network_under_the_opt_in_plans(Simulator, seed):
     saved = {k: os.environ.get(k) for k in ("SSN_FUSE_MIN_ROWS", "SSN_SOLO_DFT", "SSN_SOLO_CAP_US")}
     try:
         os.environ.update(SSN_FUSE_MIN_ROWS="1", SSN_SOLO_DFT="1", SSN_SOLO_CAP_US="60")
-        for kw in (dict(steps_per_graph=16), dict(flags=2097152), dict(steps_per_graph=1)):
+        for kw in (dict(steps_per_graph=16), dict(flags=PLAN.SSN_PLAN_NO_ROUNDS), dict(steps_per_graph=1)):
             with Simulator(None, model=model, dtype="f64", **kw) as sim:
                 sim.run_steps(steps)
                 for p in probes:

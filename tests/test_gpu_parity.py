@@ -11,6 +11,7 @@ import pytest
 
 import sspslam_amd.frontend as nengo
 from sspslam_amd import harness as H
+from sspslam_amd import simulator as PLAN
 from sspslam_amd.modelcache import cached_build as build      # (one build per model and session: conftest.py gives the suite a cache)
 from oracle import OracleSimulator
 
@@ -426,7 +427,7 @@ def test_dft_kernel_matches_the_transform_matrices(Simulator):
     inverse transform."""
     from sspslam_amd.networks import CircularConvolution
     from sspslam_amd.builder import dft_structure
-    FOURSTEP, BIG = 536870912, 268435456
+    FOURSTEP, BIG = PLAN.SSN_PLAN_FOUR_STEP_FFT, PLAN.SSN_PLAN_BLUESTEIN_FFT
     # (even lengths: 40 = 8 x 5, 44 = 4 x 11 and 70 = 2 x 7 x 5 run a radix-8 / 4 / 2 pass as in-register butterflies between
     #  generic ones - dft_pass_small; the odd lengths' chirp-z transforms run them in place - dft_pass_inplace)
     for d, inv_a, inv_b in ((25, False, True), (55, True, False), (217, False, False), (97, False, True), (1015, True, False),
@@ -479,27 +480,27 @@ def test_slam_optin_plans_equal_default(Simulator):
     model = build(sm.model)
     ref = OracleSimulator(model)
     ref.run_steps(120)
-    OLD = 2097152
+    OLD = PLAN.SSN_PLAN_NO_ROUNDS
     outs, launches = {}, {}
-    for flags in (0, 1024, 8192, 4194304, 8388608, 16777216, 33554432, 134217728,
-                  OLD, OLD | 4096, 262144):
+    for flags in (0, PLAN.SSN_PLAN_SPMV_OWN_LIST, PLAN.SSN_PLAN_ENS_PARTIALS, PLAN.SSN_PLAN_ENS_OWN_LAUNCH, PLAN.SSN_PLAN_NO_PIPELINE, PLAN.SSN_PLAN_NO_BALANCE, PLAN.SSN_PLAN_NO_CUTS, PLAN.SSN_PLAN_NO_CHAINS,
+                  OLD, OLD | PLAN.SSN_PLAN_NO_ITEM_BATCH, PLAN.SSN_PLAN_NO_STAGE_BATCH):
         with Simulator(None, model=model, dtype="f64", flags=flags) as sim:
             sim.run_steps(120)             # 7 graph replays of 16 pipelined steps + 8 steps launched one round at a time
             outs[flags] = sim.data[sm.probe]
             launches[flags] = sim.counters()["launches_per_step"]
     np.testing.assert_allclose(outs[0], ref.probe_data(0), atol=1e-9, rtol=0)
     np.testing.assert_allclose(outs[1024], outs[0], atol=1e-12, rtol=0)   # spike list rebuilt in the product kernel: other chunking
-    np.testing.assert_allclose(outs[8192], outs[0], atol=1e-12, rtol=0)   # finish operator vs direct write of one-workgroup ensembles
-    for flags in (4194304,        # ensemble arrays launched on their own vs as bodies of the round's grid
-                  8388608,        # one timestep's rounds at a time vs 16 timesteps software-pipelined
-                  16777216,       # no splitting of heavy operators over the rounds of their slack window
-                  33554432,       # merged element-wise operators kept whole vs cut at the other operators' range endpoints
-                  134217728,      # no chains of element-aligned micro-operators inside a block
-                  262144):        # one launch per element-wise operator of the batched stages
+    np.testing.assert_allclose(outs[PLAN.SSN_PLAN_ENS_PARTIALS], outs[0], atol=1e-12, rtol=0)   # finish operator vs direct write of one-workgroup ensembles
+    for flags in (PLAN.SSN_PLAN_ENS_OWN_LAUNCH,        # ensemble arrays launched on their own vs as bodies of the round's grid
+                  PLAN.SSN_PLAN_NO_PIPELINE,        # one timestep's rounds at a time vs 16 timesteps software-pipelined
+                  PLAN.SSN_PLAN_NO_BALANCE,       # no splitting of heavy operators over the rounds of their slack window
+                  PLAN.SSN_PLAN_NO_CUTS,       # merged element-wise operators kept whole vs cut at the other operators' range endpoints
+                  PLAN.SSN_PLAN_NO_CHAINS,      # no chains of element-aligned micro-operators inside a block
+                  PLAN.SSN_PLAN_NO_STAGE_BATCH):        # one launch per element-wise operator of the batched stages
         np.testing.assert_array_equal(outs[flags], outs[0], err_msg=str(flags))
     np.testing.assert_allclose(outs[OLD], outs[0], atol=1e-12, rtol=0)       # (the gate's dot product sums 16 wave partials there, 4 here)
-    np.testing.assert_array_equal(outs[OLD | 4096], outs[OLD])      # one launch per operator vs batched neighbours
-    assert launches[0] < launches[8388608] < launches[OLD]
+    np.testing.assert_array_equal(outs[OLD | PLAN.SSN_PLAN_NO_ITEM_BATCH], outs[OLD])      # one launch per operator vs batched neighbours
+    assert launches[0] < launches[PLAN.SSN_PLAN_NO_PIPELINE] < launches[OLD]
 
 
 def test_serial_chains_equal_plain_rounds(Simulator):
@@ -928,7 +929,7 @@ def test_fused_recurrent_core_equals_generic_path(Simulator):
     pm = small_pathint(ssp_dim=55, n=2500, T=10.0, limit=0.2)
     model = build(pm.model, n_eval_points=600)
     outs = []
-    for flags in (128, 1, 16):    # deferred finish (1 launch/step) | generic programs | fused with separate finish kernel
+    for flags in (PLAN.SSN_PLAN_NO_BLOCK_KERNEL, PLAN.SSN_PLAN_NO_FUSED_CORE, PLAN.SSN_PLAN_SEPARATE_FINISH):    # deferred finish (1 launch/step) | generic programs | fused with separate finish kernel
         with Simulator(None, model=model, dtype="f64", flags=flags, block_steps=96) as sim:
             sim.run_steps(150)
             sim.run_steps(150)        # block boundaries, eager remainders and a second call: flush/begin paths
@@ -938,7 +939,7 @@ def test_fused_recurrent_core_equals_generic_path(Simulator):
     np.testing.assert_array_equal(outs[0], outs[2])
     np.testing.assert_array_equal(outs[0], outs[4])
     # LIF fast path (packed state word, spike-sparse neuron-major decoders) vs the generic kernel: same bits
-    with Simulator(None, model=model, dtype="f64", flags=2, block_steps=96) as sim:
+    with Simulator(None, model=model, dtype="f64", flags=PLAN.SSN_PLAN_NO_LIF_FAST, block_steps=96) as sim:
         sim.run_steps(300)
         np.testing.assert_array_equal(sim.data[pm.probe], outs[0])
     ref = OracleSimulator(model)
@@ -957,7 +958,7 @@ def test_fused_recurrent_core_equals_generic_path(Simulator):
         np.testing.assert_allclose(got_v, np.asarray(ref.buf[v_buf]).reshape(got_v.shape), atol=1e-9, rtol=0)
         batched_stage_out = sim.data[pm.probe]
     # one launch per element-wise operator of the time-batched stages vs independent neighbours sharing a launch
-    with Simulator(None, model=model, dtype="f64", block_steps=96, flags=262144) as sim:
+    with Simulator(None, model=model, dtype="f64", block_steps=96, flags=PLAN.SSN_PLAN_NO_STAGE_BATCH) as sim:
         sim.run_steps(150)
         sim.run_steps(150)
         np.testing.assert_array_equal(sim.data[pm.probe], batched_stage_out)
@@ -1030,7 +1031,7 @@ def test_slam_at_ssp_dim_1015_matches_oracle(Simulator):
         np.testing.assert_allclose(sim.data[sm.weights_probe], ref.probe_data(1), atol=1e-12, rtol=1e-9)
         np.testing.assert_allclose(sim.data[p_clean], ref.probe_data(2), atol=1e-12, rtol=0)
     outs = []
-    for flags in (0, 512, 2097152 | 4096):       # FFT kernels | the dense transform matrices | the round-1 plan, one launch per operator
+    for flags in (0, PLAN.SSN_PLAN_NO_FFT, PLAN.SSN_PLAN_NO_ROUNDS | PLAN.SSN_PLAN_NO_ITEM_BATCH):       # FFT kernels | the dense transform matrices | the round-1 plan, one launch per operator
         with Simulator(None, model=model, dtype="f32", flags=flags) as sim:
             sim.run_steps(100)
             outs.append(sim.data[sm.probe])
@@ -1072,7 +1073,7 @@ def test_slam_3d_matches_oracle(Simulator):
     # default for tables >= 64 MB) or from the pass over the table (flag 524288).  Near-ties between neighbouring grid
     # points (cosine 0.99 apart) may resolve differently in f32, so: the same row on nearly all steps, a neighbour otherwise
     launches = []
-    for flags, split in ((0, None), (524288, None), (0, "2")):      # last: K-split product, partials summed by the argmax stage
+    for flags, split in ((0, None), (PLAN.SSN_PLAN_NO_FACTORED_GRID, None), (0, "2")):      # last: K-split product, partials summed by the argmax stage
         os.environ.pop("SSN_GRID_SPLIT", None)
         if split:
             os.environ["SSN_GRID_SPLIT"] = split
@@ -1158,7 +1159,7 @@ def test_block_kernel_variants_f32(Simulator):
                        (2500, "1024,6,0"), (2500, "512,10,0")):
         pm = small_pathint(ssp_dim=19, n=n, T=10.0, limit=0.2)
         model = build(pm.model, n_eval_points=300)
-        with Simulator(None, model=model, dtype="f32", flags=128, block_steps=64) as sim:
+        with Simulator(None, model=model, dtype="f32", flags=PLAN.SSN_PLAN_NO_BLOCK_KERNEL, block_steps=64) as sim:
             sim.run_steps(150)
             want = sim.data[pm.probe]
         os.environ.pop("SSN_BLOCK_VARIANT", None)
@@ -1302,7 +1303,7 @@ def test_gridcell_populations_match_oracle(Simulator):
         ref.run_steps(300)
         idx = {id(p["probe"]): i for i, p in enumerate(model.probes)}
         want = ref.probe_data(idx[id(probes[0])])
-        for flags in (0, 8388608, 2097152):        # pipelined rounds | one timestep's rounds at a time | one launch per operator
+        for flags in (0, PLAN.SSN_PLAN_NO_PIPELINE, PLAN.SSN_PLAN_NO_ROUNDS):        # pipelined rounds | one timestep's rounds at a time | one launch per operator
             with Simulator(None, model=model, dtype="f32", flags=flags) as sim:
                 sim.run_steps(300)
                 ce = H.cosine_error(sim.data[probes[0]][20:], want[20:])
@@ -1371,8 +1372,8 @@ def test_config3_full_size_with_learning_matches_oracle(Simulator):
 
 def test_sharded_pathint_streaming_plan_and_choose_plan(Simulator):
     """BASELINE configs[3]'s shard plan at test size: VCOs of 12 000 neurons do not fit a k_ens_block workgroup (capacity
-    10 752), so a rank's shard is stepped by one streaming k_ensarray launch per timestep - also what flags = 128 forces.
-    ShardedPathIntegration(flags=128) and choose_plan (bench.py's default at N > 1: both candidates timed, the faster kept)
+    10 752), so a rank's shard is stepped by one streaming k_ensarray launch per timestep - also what SSN_PLAN_NO_BLOCK_KERNEL forces.
+    ShardedPathIntegration(flags=SSN_PLAN_NO_BLOCK_KERNEL) and choose_plan (bench.py's default at N > 1: both candidates timed, the faster kept)
     must step to the oracle's trajectory."""
     from sspslam_amd.sharding import ShardedPathIntegration
     kw = dict(ssp_dim=7, n=12000, T=10.0, limit=0.2)
@@ -1380,7 +1381,7 @@ def test_sharded_pathint_streaming_plan_and_choose_plan(Simulator):
     ref = OracleSimulator(model)
     ref.run_steps(256)
     want = ref.probe_data(0)
-    r = ShardedPathIntegration(small_pathint(**kw), 0, 1, dtype="f64", block=128, n_eval_points=1500, flags=128)
+    r = ShardedPathIntegration(small_pathint(**kw), 0, 1, dtype="f64", block=128, n_eval_points=1500, flags=PLAN.SSN_PLAN_NO_BLOCK_KERNEL)
     r.prepare(256)
     r.run_steps(256)
     assert r.sim.counters()["launches_per_step"] == 1 and r.sim.counters()["block_tpb"] == 0 and r.sim.counters()["block_members"] == 0
@@ -1516,7 +1517,7 @@ def test_split_vco_members_match_oracle(Simulator):
     unsplit kernel (the sums are re-associated over the members: rounding only), members of unequal size (n not a multiple of
     4 P), several launches in a run (the exchange words are reset at every kernel boundary), the planner's own choice of P,
     and the cases it must leave alone (f64; a fifth decoded row; more VCOs than CUs)."""
-    SPLIT = 1073741824
+    SPLIT = PLAN.SSN_PLAN_SPLIT_BLOCK
     os.environ.pop("SSN_BLOCK_SPLIT", None)
     os.environ.pop("SSN_BLOCK_SPLIT_CUS", None)
     try:

@@ -1,7 +1,7 @@
 """Whole-block VCO kernel (k_ens_block) variants vs the per-timestep kernel, one process (A/B on one box).
 
 usage: bench_block.py ssp_dim n_per_vco steps n_eval variant[;variant...]
-  variant = "tpb,npt,lds" (SSN_BLOCK_VARIANT), "auto" (library's choice) or "step" (flags=128: k_ensarray per timestep)
+  variant = "tpb,npt,lds" (SSN_BLOCK_VARIANT), "auto" (library's choice) or "step" (SSN_PLAN_NO_BLOCK_KERNEL: k_ensarray per timestep)
 """
 import os
 import sys
@@ -12,6 +12,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sspslam_amd import harness as H
 from sspslam_amd.modelcache import cached_build as build
+from sspslam_amd import simulator as PLAN
 from sspslam_amd.simulator import Simulator
 
 d, n, steps, m_eval = [int(a) for a in sys.argv[1:5]]
@@ -28,7 +29,7 @@ for v in variants:
     os.environ.pop("SSN_BLOCK_VARIANT", None)
     flags = 0
     if v == "step":
-        flags = 128
+        flags = PLAN.SSN_PLAN_NO_BLOCK_KERNEL
     elif v != "auto":
         os.environ["SSN_BLOCK_VARIANT"] = v
     try:

@@ -9,9 +9,10 @@ import numpy as np
 import sspslam_amd.frontend as nengo
 from sspslam_amd.modelcache import cached_build as build
 from sspslam_amd.networks import CircularConvolution
+from sspslam_amd import simulator as PLAN
 from sspslam_amd.simulator import Simulator
 
-PER_OP, FOURSTEP, BIG, MATRIX = 2097152, 536870912, 268435456, 512
+PER_OP, FOURSTEP, BIG, MATRIX = PLAN.SSN_PLAN_NO_ROUNDS, PLAN.SSN_PLAN_FOUR_STEP_FFT, PLAN.SSN_PLAN_BLUESTEIN_FFT, PLAN.SSN_PLAN_NO_FFT
 for d in [int(x) for x in sys.argv[1:]] or [55, 217, 1015, 1801, 2049]:
     rng = np.random.RandomState(d)
     fa = rng.randn(d) / np.sqrt(d)

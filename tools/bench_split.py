@@ -6,9 +6,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from sspslam_amd import harness as H
 from sspslam_amd.modelcache import cached_build as build
+from sspslam_amd import simulator as PLAN
 from sspslam_amd.simulator import Simulator
 
-SPLIT = 1073741824
+SPLIT = PLAN.SSN_PLAN_SPLIT_BLOCK
 space = H.make_ssp_space(2, 1015)
 path, vels = H.make_random_path(20.0, limit=0.1, seed=0)
 for world in [int(x) for x in sys.argv[1:]] or [4, 8]:

@@ -6,6 +6,7 @@ sys.path.insert(0, os.getcwd())
 import numpy as np
 from sspslam_amd import harness as H
 from sspslam_amd.modelcache import cached_build as build
+from sspslam_amd import simulator as PLAN
 from sspslam_amd.simulator import Simulator
 dt, view_rad, M, d = 0.001, 0.2, 10150, 1015
 s = H.make_ssp_space(2, d)
@@ -27,7 +28,7 @@ bm = build(sm.model, n_eval_points=4000)
 for name, t0 in (("landmark in view", t_in), ("no landmark in view", t_out)):
     if t0 is None:
         continue
-    with Simulator(None, model=bm, dtype="f32", flags=2097152) as sim:
+    with Simulator(None, model=bm, dtype="f32", flags=PLAN.SSN_PLAN_NO_ROUNDS) as sim:
         sim.prepare(t0 + W + 8)
         sim.run_steps(t0, collect=False)
         sim.run_steps(W, profile=2, collect=False)

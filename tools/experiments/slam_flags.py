@@ -1,12 +1,12 @@
 """Config-3 SLAM timestep under alternative plans: one model build, one simulator per flag set.
-usage: python tools/experiments/slam_flags.py [flags[,ENV=value...] ...]      (default: 0 256)
+usage: python tools/experiments/slam_flags.py [flags[,ENV=value...] ...]      (default: 0)
   e.g.  0  0,SSN_ROUND_INTERLEAVE=0  536870912      (default plan | contiguous block order | Stockham FFT)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from sspslam_amd import harness as H
 from sspslam_amd.modelcache import cached_build as build
 from sspslam_amd.simulator import Simulator
-flag_sets = sys.argv[1:] or ["0", "256"]
+flag_sets = sys.argv[1:] or ["0"]
 SPG = [int(x) for x in os.environ.get("SSN_SPG", "0").split(",")]
 SWEEPS = [x for x in os.environ.get("SSN_SWEEPS", "").split(",")]
 s = H.make_ssp_space(2, 1015)

@@ -5,6 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from sspslam_amd import harness as H
 from sspslam_amd.modelcache import cached_build as build
+from sspslam_amd import simulator as PLAN
 from sspslam_amd.simulator import Simulator
 
 T = float(sys.argv[1]) if len(sys.argv) > 1 else 10.0
@@ -16,7 +17,7 @@ bm = build(pm.model, n_eval_points=4000)
 n = int(T / dt)
 true = s.encode(path[:n]) if hasattr(s, "encode") else None
 out = {}
-for name, dtype, flags in (("block", "f32", 0), ("step", "f32", 128), ("f64", "f64", 0)):
+for name, dtype, flags in (("block", "f32", 0), ("step", "f32", PLAN.SSN_PLAN_NO_BLOCK_KERNEL), ("f64", "f64", 0)):
     with Simulator(None, model=bm, dtype=dtype, flags=flags) as sim:
         t0 = time.perf_counter()
         sim.run_steps(n)

@@ -151,6 +151,10 @@ __device__ inline f32x2 pk_fma_clamp01_vs_negv(f32x2 x, f32x2 y, f32x2 z) {     
 //   w' = (Wn + nmt) + spk * nu    (spiking: Wn = 1, nmt = 0; silent: spk = 0 - exact selects, products with 0 / 1)
 // Requires dt / tau_rc <= 1/20 and tau_ref >= dt (checked by the host planner).
 struct LifConstV3 { float na, ca, m1, c1, c2, c3, p0, p1, p2, ktau_ref, K; };      // p: K tau_rc phi(u) ~ p0 + p1 u + p2 u^2
+// The same constants as the time loop reads them: every one as a pair of equal halves, the operand form of the packed
+// instructions.  (Scalar fields, splat at each use, come out of the optimizer as overlapping two-word loads of neighbouring
+// fields, which keep the whole structure in scratch memory once the loop reads it at more places.)
+struct LifConstV3P { f32x2 na, ca, m1, c1, c2, c3, p0, p1, p2, ktau_ref; };
 
 // K, the constants of dl / nmt and the coefficients of P for dl in units of dt (uniform; evaluated once per launch, in double)
 __device__ inline LifConstV3 lif_const_v3(double dt, double tau_rc, double tau_ref) {
@@ -184,18 +188,31 @@ __device__ inline LifConstV3 lif_const_v3(double dt, double tau_rc, double tau_r
   return c;
 }
 
-// The step in two halves: lif_state_part needs only the state word, lif_input_part is what needs J.  (Measured and dropped in
-// round 3: running the state half for all of a thread's neurons in the tail of the previous timestep, behind the workgroup
-// barrier or - the older wave of each SIMD - in front of it, 40 more registers: 2.90 - 2.92 ms per 1000 steps either way against
-// 2.91 - 2.92 with the halves back to back, same box; alternating s_setprio between the two waves of a SIMD: 3.21 ms.)
-__device__ inline void lif_state_part(f32x2 w, const LifConstV3& c, f32x2& W0, f32x2& em) {
-  W0 = pk_clamp01(w);
-  const f32x2 dl = pk_fma_clamp01_vsv(w, (f32x2)(c.na), (f32x2)(c.ca));      // clamp(c - a w)
-  // (uniform coefficients as scalar-register pairs: one constant-bus operand per instruction, the first FMA's second
-  //  coefficient lives in a vector register pair)
+// The step in two halves: lif_state_part needs only the state word, lif_input_part is what needs J.  The time loop runs the
+// state half of some groups one timestep ahead, INSIDE the waits of the cross-wave sum (SSN_BLOCK_HOIST_*).
+// (Measured and dropped in round 3: the state half of ALL of a thread's neurons as one lump in the tail of the previous timestep,
+// behind the wait for the wave sums - where it overlaps nothing - or, the older wave of each SIMD, in front of the barrier, 40 more
+// registers: 2.90 - 2.92 ms per 1000 steps either way against 2.91 - 2.92 with the halves back to back, same box; alternating
+// s_setprio between the two waves of a SIMD: 3.21 ms.)
+// (its instructions one by one, for the time loop's tail, which places them between the steps of the cross-wave sum)
+__device__ inline f32x2 lif_state_dl(f32x2 w, f32x2 na, f32x2 ca) {
+  return pk_fma_clamp01_vsv(w, (f32x2)(na), (f32x2)(ca));                   // clamp(c - a w)
+}
+// (uniform coefficients as scalar-register pairs: one constant-bus operand per instruction, the first FMA's second
+//  coefficient lives in a vector register pair)
+__device__ inline f32x2 lif_state_p1(f32x2 dl, f32x2 c3, f32x2 c2) {
   f32x2 P;
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(dl), "v"((f32x2)(c.c3)), "s"((f32x2)(c.c2)));
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(dl), "v"(P), "s"((f32x2)(c.c1)));
+  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(dl), "v"((f32x2)(c3)), "s"((f32x2)(c2)));
+  return P;
+}
+__device__ inline f32x2 lif_state_p2(f32x2 dl, f32x2 P, f32x2 c1) {
+  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(dl), "v"(P), "s"((f32x2)(c1)));
+  return P;
+}
+__device__ inline void lif_state_part(f32x2 w, const LifConstV3P& c, f32x2& W0, f32x2& em) {
+  W0 = pk_clamp01(w);
+  const f32x2 dl = lif_state_dl(w, c.na, c.ca);
+  const f32x2 P = lif_state_p2(dl, lif_state_p1(dl, c.c3, c.c2), c.c1);
   em = dl * P;
 }
 // The input half in three pieces, so that a wave whose neurons are all silent in a timestep can leave out the spike-time
@@ -203,12 +220,12 @@ __device__ inline void lif_state_part(f32x2 w, const LifConstV3& c, f32x2& W0, f
 // is the rest of lif_input_part; lif_finish_silent is what that rest computes when every indicator is 0 - bit for bit:
 // Wn = clamp(0 * 2^100 - U) = clamp(-U), w' = fma(0, nu, Wn + nmt) = Wn + nmt (nu is a number in [0, 1] after its clamp, so
 // 0 * nu = +0, and Wn + nmt >= 0).
-__device__ inline f32x2 lif_spike_test(f32x2 Jm1, f32x2 w, f32x2 W0, f32x2 em, const LifConstV3& c, f32x2 big, f32x2& U, f32x2& nmt) {
+__device__ inline f32x2 lif_spike_test(f32x2 Jm1, f32x2 w, f32x2 W0, f32x2 em, const LifConstV3P& c, f32x2 big, f32x2& U, f32x2& nmt) {
   nmt = pk_sub_clamp01(w, (f32x2)(c.m1));                                    // clamp(w - 1 - K dt)
   U = __builtin_elementwise_fma(Jm1 + W0, em, -W0);
   return pk_mul_clamp01(U, big);
 }
-__device__ inline void lif_finish_spiking(f32x2 Jm1, f32x2& w, f32x2 U, f32x2 nmt, f32x2 spk, const LifConstV3& c, f32x2 big) {
+__device__ inline void lif_finish_spiking(f32x2 Jm1, f32x2& w, f32x2 U, f32x2 nmt, f32x2 spk, const LifConstV3P& c, f32x2 big) {
   f32x2 rc;
   rc.x = __builtin_amdgcn_rcpf(Jm1.x);
   rc.y = __builtin_amdgcn_rcpf(Jm1.y);
@@ -225,7 +242,7 @@ __device__ inline void lif_finish_silent(f32x2& w, f32x2 U, f32x2 nmt) {
   asm("v_pk_mul_f32 %0, %1, -1.0 op_sel_hi:[1,0] clamp" : "=v"(Wn) : "v"(U));          // clamp(-U)
   w = Wn + nmt;
 }
-__device__ inline f32x2 lif_input_part(f32x2 Jm1, f32x2& w, f32x2 W0, f32x2 em, const LifConstV3& c, f32x2 big) {
+__device__ inline f32x2 lif_input_part(f32x2 Jm1, f32x2& w, f32x2 W0, f32x2 em, const LifConstV3P& c, f32x2 big) {
   const f32x2 nmt = pk_sub_clamp01(w, (f32x2)(c.m1));                        // clamp(w - 1 - K dt)
   const f32x2 U = __builtin_elementwise_fma(Jm1 + W0, em, -W0);
   const f32x2 spk = pk_mul_clamp01(U, big);
@@ -261,11 +278,14 @@ __device__ inline unsigned int f_bits(float x) { return __builtin_bit_cast(unsig
 //   [2] wave reduction + publication of the wave sums in LDS              [3] wait at the workgroup barrier
 //   [4] totals over the waves, filter update, hand-off to the post stage  [5] wave-timesteps counted
 //   [6] / [7] s_memtime / s_memrealtime ticks of workgroup 0's time loop (shader clock = 100 MHz * [6] / [7])
-__device__ unsigned long long g_block_stamps[8];
+//   [8] the part of [4] from the barrier to the totals over the waves (LDS read of the wave sums + row sum); the rest of [4]
+//       is the filter update, the next timestep's input (pipelined loop: there [0] is empty) and the hand-off
+// (callers pass room for 9 words)
+__device__ unsigned long long g_block_stamps[9];
 inline hipError_t read_block_stamps(unsigned long long* out, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_block_stamps), sizeof(unsigned long long) * 8);
+  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_block_stamps), sizeof(unsigned long long) * 9);
   if (e == hipSuccess && reset) {
-    const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const unsigned long long z[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_block_stamps), z, sizeof z);
   }
   return e;
@@ -281,6 +301,42 @@ inline hipError_t read_block_stamps(unsigned long long* out, int reset) {
 #define SSN_BSTAMP(var) do {} while (0)
 #define SSN_BSTAMP_ADD(i, a, b) do {} while (0)
 #endif
+
+#ifndef SSN_BLOCK_SKIP
+#define SSN_BLOCK_SKIP 0      // silent-slot modes of the f32 neuron rounds (compile-time, default off: see the time loop)
+#endif
+// The f32 time loop's tail, pipelined (variants with five or more neuron groups; 0 restores the plain loop):
+//   SSN_BLOCK_PIPE     the next timestep's input row is read from LDS in front of the wave reduction and x of timestep jj + 1 is
+//                      assembled at the end of timestep jj, so that no LDS round trip sits between the totals and the first encode FMA
+//   SSN_BLOCK_HOIST_A  neuron groups whose lif_state_part of timestep jj + 1 runs between the publication of the wave sums and the barrier
+//   SSN_BLOCK_HOIST_B  ... between the LDS read of the wave sums and the wait for it
+//   SSN_BLOCK_HOIST_C  ... (0 or 2) instruction by instruction between the four DPP steps of the row sum, in their wait states
+// A hoisted group costs four registers from the tail to its round of the next timestep; block_hoist() cuts the three
+// counts to what the variant's register budget (512 / waves per SIMD) leaves.  Measured at (512, 20, LDS), ms per bench step
+// against 2.98 - 3.00 for the plain loop (profiles/block_tail_placements.txt): A 2, B 4, C 2 2.79 - 2.81; A 0 2.90 - 2.96 and
+// A 4 2.84 - 2.99 whatever B is; C 0 2.86 - 3.00.  Outputs are bit for bit those of the plain loop for every setting.
+#ifndef SSN_BLOCK_PIPE
+#define SSN_BLOCK_PIPE 1
+#endif
+#ifndef SSN_BLOCK_HOIST_A
+#define SSN_BLOCK_HOIST_A 2
+#endif
+#ifndef SSN_BLOCK_HOIST_B
+#define SSN_BLOCK_HOIST_B 4
+#endif
+#ifndef SSN_BLOCK_HOIST_C
+#define SSN_BLOCK_HOIST_C 2
+#endif
+struct BlockHoist { int a, b, c; };
+constexpr BlockHoist block_hoist(bool pipe, int tpb, int ng) {
+  if (!pipe || SSN_BLOCK_SKIP != 0) return {0, 0, 0};
+  const int room = tpb <= 512 && ng >= 10 ? ng : 0;         // only two waves per SIMD at ten groups have registers to spare: 768 threads
+                                                            // spill, (512, 10) would drop from three waves per SIMD to two
+  const int c = SSN_BLOCK_HOIST_C >= 2 && room >= 2 ? 2 : 0;      // (a pair or nothing: two instructions fill a DPP step's wait states)
+  int b = SSN_BLOCK_HOIST_B < room - c ? SSN_BLOCK_HOIST_B : room - c;
+  int a_ = SSN_BLOCK_HOIST_A < room - c - b ? SSN_BLOCK_HOIST_A : room - c - b;
+  return {a_, b, c};
+}
 
 // Neurons are dealt to threads in groups of PK adjacent neurons (PK = 2 for f32: one 64-bit register pair,
 // 1 for f64): neuron index of (group g, thread tid, component c) = (g * nthr + tid) * PK + c - coalesced.
@@ -309,6 +365,10 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
   constexpr int PK = F32 ? 2 : 1;
   constexpr int NG = NPT / PK;
   static_assert(NPT % PK == 0, "f32 variants handle neuron pairs");
+  constexpr bool PIPE = F32 && NG >= 5 && SSN_BLOCK_PIPE != 0;     // (variants with one to three groups keep the plain loop: their
+                                                                   //  1024-thread workgroups have no register to spare for the row)
+  constexpr BlockHoist HO = block_hoist(PIPE, TPB, NG);
+  constexpr int HC = HO.c, HA = HO.a, HB = HO.b, HT = HC + HA + HB;      // hoisted groups: [0, HC) | [HC, HC + HA) | [HC + HA, HT)
   using G = typename std::conditional<F32, f32x2, T>::type;   // one group of neurons
   constexpr int DP = DOUT <= 4 ? 4 : 8;
   // split ensembles: P consecutive workgroups are the members of ensemble k (f32, DOUT <= 4 only - the planner sees to it)
@@ -330,9 +390,11 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
   // (uniform values: readfirstlane moves them to scalar registers, where the packed instructions of the time loop can take
   //  them as their one constant-bus operand)
   auto uni = [](float v) { return bits_f(__builtin_amdgcn_readfirstlane(f_bits(v))); };
-  LifConstV3 lc = lif_const_v3((double)np.dt, (double)np.tau_rc, (double)np.tau_ref);
-  lc.na = uni(lc.na); lc.ca = uni(lc.ca); lc.m1 = uni(lc.m1); lc.c1 = uni(lc.c1); lc.c2 = uni(lc.c2); lc.c3 = uni(lc.c3); lc.p0 = uni(lc.p0); lc.p1 = uni(lc.p1); lc.p2 = uni(lc.p2); lc.ktau_ref = uni(lc.ktau_ref);
-  lc.K = uni(lc.K);
+  const LifConstV3 lc0 = lif_const_v3((double)np.dt, (double)np.tau_rc, (double)np.tau_ref);
+  auto uni2 = [&](float v) { const float u = uni(v); return (f32x2){u, u}; };
+  const LifConstV3P lc = {uni2(lc0.na), uni2(lc0.ca), uni2(lc0.m1), uni2(lc0.c1), uni2(lc0.c2), uni2(lc0.c3), uni2(lc0.p0), uni2(lc0.p1),
+                          uni2(lc0.p2), uni2(lc0.ktau_ref)};
+  const float lcK = uni(lc0.K);
   const f32x2 big = {0x1p100f, 0x1p100f};
 
   // ---- parameters and state of this thread's neurons -> registers ---------------------------------------------
@@ -369,7 +431,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
     s[g] = ld(Sp + ii);
     if constexpr (F32) {                                   // the time loop's forms: J - 1, distance to the threshold (lif_state_part / lif_input_part)
       b[g] = b[g] - 1.0f;
-      s[g] = (f32x2){lif_word_in(s[g].x, lc.K), lif_word_in(s[g].y, lc.K)};
+      s[g] = (f32x2){lif_word_in(s[g].x, lcK), lif_word_in(s[g].y, lcK)};
     }
     if (a.dec_neuron_major) {
       const T* dp = a.dec + ((size_t)k * row + noff + ii) * DP;
@@ -452,10 +514,34 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
       for (int d = 0; d < LDSW; ++d) en[u][d] = *lds_group(d, u);
   }
 #ifdef SSN_BLOCK_STAMPS
-  unsigned long long bst[5] = {0, 0, 0, 0, 0}, bt0 = 0, bt1 = 0, bt2 = 0, bt3 = 0, bt4 = 0, bt5 = 0, bm0 = 0, br0 = 0;
+  unsigned long long bst[6] = {0, 0, 0, 0, 0, 0}, bt0 = 0, bt1 = 0, bt2 = 0, bt3 = 0, bt4 = 0, bt5 = 0, bt6 = 0, bm0 = 0, br0 = 0;
   asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(bm0), "=s"(br0) :: "memory");
 #endif
   unsigned int n_slots = 0, n_silent = 0;      // (wave-uniform: scalar registers)
+  T x[DIN];
+  int xl[DIN];                                 // lane of F0 that holds the state input d reads (uniform: a scalar register, read once)
+#pragma unroll
+  for (int d = 0; d < DIN; ++d) xl[d] = __builtin_amdgcn_readfirstlane((xr[d] & 3) << 4);
+  // f32 input: pre-stage row + alpha * the filter state it reads - row xr[d] of the lane-distributed registers (uniform lane index)
+  auto assemble_x = [&](const float4 xv) {
+    const float xin[4] = {xv.x, xv.y, xv.z, xv.w};
+    float f1 = 0.0f;
+    if constexpr (DOUT > 4) f1 = bits_f(__builtin_amdgcn_readlane(f_bits(F1), 0));
+#pragma unroll
+    for (int d = 0; d < DIN; ++d) {
+      const float f0 = bits_f(__builtin_amdgcn_readlane(f_bits(F0), xl[d]));
+      float st = f0;                                            // (a v_cndmask costs five issue slots: only where a fifth row exists)
+      if constexpr (DOUT > 4) st = xr[d] >= 4 ? f1 : f0;
+      x[d] = __builtin_fmaf(xa[d], st, xin[d]);                 // (xa = 0 where no state feeds the input)
+    }
+  };
+  // pipelined tail: the state half (W0, em) of the hoisted groups' NEXT step, computed in the waits of the cross-wave sum
+  // (the state word is final when a group's round ends; after the last timestep of the launch the values are dropped)
+  f32x2 W0h[HT > 0 ? HT : 1], emh[HT > 0 ? HT : 1];
+  if constexpr (HT > 0) {
+#pragma unroll
+    for (int g = 0; g < HT; ++g) lif_state_part(s[g], lc, W0h[g], emh[g]);
+  }
   for (int j0 = 0; j0 < a.B; j0 += CH) {
     const int cn = min(CH, a.B - j0);
     __syncthreads();                         // previous chunk: every wave is past its last xs read / os write
@@ -470,6 +556,9 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
       xs[jj][d] = xbase[(size_t)(j0 + jj) * a.n_sig + d];
     }
     __syncthreads();
+    if constexpr (PIPE) {                    // the chunk's first input (every later one is assembled in the tail of the timestep before it)
+      assemble_x(*(const float4*)xs[0]);
+    }
 
     for (int jj = 0; jj < cn; ++jj) {
       SSN_BSTAMP(bt0);
@@ -480,22 +569,13 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           asm volatile("global_store_dword %0, %1, off sc0 sc1" :: "v"(rst), "v"(sent) : "memory");
         }
       }
-      T xin[XP];
-      if constexpr (sizeof(T) == 4) *(float4*)xin = *(const float4*)xs[jj];
-      else { *(double2*)xin = *(const double2*)xs[jj]; *(double2*)(xin + 2) = *(const double2*)(xs[jj] + 2); }
-      T x[DIN];
-      if constexpr (F32) {
-        // the filter states the inputs read: row xr[d] of the lane-distributed registers (uniform lane index)
-        float f1 = 0.0f;
-        if constexpr (DOUT > 4) f1 = bits_f(__builtin_amdgcn_readlane(f_bits(F1), 0));
-#pragma unroll
-        for (int d = 0; d < DIN; ++d) {
-          const float f0 = bits_f(__builtin_amdgcn_readlane(f_bits(F0), (xr[d] & 3) << 4));
-          float st = f0;                                            // (a v_cndmask costs five issue slots: only where a fifth row exists)
-          if constexpr (DOUT > 4) st = xr[d] >= 4 ? f1 : f0;
-          x[d] = __builtin_fmaf(xa[d], st, xin[d]);                 // (xa = 0 where no state feeds the input)
-        }
+      if constexpr (PIPE) {
+        // (x was assembled in the tail of the timestep before)
+      } else if constexpr (F32) {
+        assemble_x(*(const float4*)xs[jj]);
       } else {
+        T xin[XP];
+        *(double2*)xin = *(const double2*)xs[jj]; *(double2*)(xin + 2) = *(const double2*)(xs[jj] + 2);
 #pragma unroll
         for (int d = 0; d < DIN; ++d) {
           T st = T(0);
@@ -540,9 +620,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
             for (int d = 0; d < LDSW; ++d) en[u][d] = *lds_group(d, gn);
           }
         }
-#ifndef SSN_BLOCK_SKIP
-#define SSN_BLOCK_SKIP 0      // (1 and 2 were measured slower than the plain loop in round 4: see the comments below and DESIGN.md section 3.1)
-#endif
+        // (SSN_BLOCK_SKIP 1 and 2 were measured slower than the plain loop in round 4: see the comments below and DESIGN.md section 3.1)
         // f32: a wave's neurons of this round are often ALL silent - the host deals neurons to (wave, round) slots by the part
         // of the oscillator's cycle in which they can fire (Sim::reorder_block_neurons), so that whole slots fall silent together -
         // and a silent slot needs neither the spike time (two v_rcp, two v_log and two packed operations per neuron pair) nor
@@ -606,7 +684,8 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
             // (stepped above)
           } else if constexpr (F32) {
             f32x2 W0, em;
-            lif_state_part(s[g], lc, W0, em);
+            if (g < HT) { W0 = W0h[g < HT ? g : 0]; em = emh[g < HT ? g : 0]; }      // (computed in the tail of the timestep before)
+            else lif_state_part(s[g], lc, W0, em);
             spk[u] = lif_input_part(J[u], s[g], W0, em, lc, big);
           } else {
             // packed state word -> nengo's LIF step, operation for operation k_ensarray's fast path
@@ -650,6 +729,12 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
       const int par = jj & 1;
       SSN_BSTAMP(bt2);
       if constexpr (F32) {
+        // pipelined: the next timestep's input row, requested HERE - in front of the wave reduction and the barrier, where its
+        // latency lies under the reduction (xs is written once per chunk and fenced by the chunk's own barriers; the compiler
+        // may not move an LDS read across s_barrier itself).  The chunk's last timestep reads its own row again: xs has CH rows.
+        float4 xnx = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (PIPE) xnx = *(const float4*)xs[jj + 1 < cn ? jj + 1 : jj];
+        (void)xnx;
         float acc[DOUT];
 #pragma unroll
         for (int r = 0; r < DOUT; ++r) acc[r] = accg[r].x + accg[r].y;
@@ -674,10 +759,59 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
             for (int r = 0; r < DOUT; ++r) red[par][r * 16 + wave] = acc[r];
           }
         }
+        if constexpr (HA > 0) {
+          // hoisted state halves, first place: behind the publication, in front of the barrier (delays the wave's arrival: few)
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int g = HC; g < HC + HA; ++g) lif_state_part(s[g], lc, W0h[g], emh[g]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
         SSN_BSTAMP(bt3);
         __syncthreads();
         SSN_BSTAMP(bt4);
-        v0 = row_sum_dpp(red[par][lane]);                          // row r of every wave: total of decoded row r
+        if constexpr (PIPE) {
+          const float rv = red[par][lane];
+          float rv1 = 0.0f;
+          if constexpr (DOUT > 4) rv1 = red[par][64 + lane];
+          if constexpr (HB > 0) {
+            // second place: between the LDS read of the wave sums and the wait for it - both waves of a SIMD fill it together
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int g = HC + HA; g < HT; ++g) lif_state_part(s[g], lc, W0h[g], emh[g]);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          // row r of every wave: total of decoded row r.  Third place: row_sum_dpp's four steps with the state halves of groups 0 and
+          // 1 between them, instruction by instruction - a DPP step may read its operand two wait states after the add before it
+          // wrote it, and two independent packed instructions are exactly that.  ONE asm statement: the compiler's hazard recognizer
+          // does not count the instructions of an asm statement as wait states (it would add its s_nop 1 to them), and its
+          // scheduler moves non-volatile asm statements across scheduling barriers.  Same operations as row_sum_dpp
+          // (v + dpp(v), all lanes valid) and lif_state_part.
+          if constexpr (HC == 2) {
+            f32x2 dl0, dl1, P0, P1;
+            v0 = rv;
+            asm volatile(
+                "v_pk_fma_f32 %1, %7, %9, %10 clamp\n\t"          // (first: whatever wrote v0 in front of the statement is two wait states away too)
+                "v_pk_fma_f32 %2, %8, %9, %10 clamp\n\t"
+                "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                "v_pk_fma_f32 %3, %1, %11, %12\n\t"
+                "v_pk_fma_f32 %4, %2, %11, %12\n\t"
+                "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                "v_pk_fma_f32 %3, %1, %3, %13\n\t"
+                "v_pk_fma_f32 %4, %2, %4, %13\n\t"
+                "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                "v_pk_mul_f32 %5, %1, %3\n\t"
+                "v_pk_mul_f32 %6, %2, %4\n\t"
+                "v_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                : "+v"(v0), "=&v"(dl0), "=&v"(dl1), "=&v"(P0), "=&v"(P1), "=&v"(emh[0]), "=&v"(emh[1])
+                : "v"(s[0]), "v"(s[1]), "s"(lc.na), "v"(lc.ca), "v"(lc.c3), "s"(lc.c2), "s"(lc.c1));
+          } else {
+            v0 = row_sum_dpp(rv);
+          }
+          if constexpr (DOUT > 4) v1 = rv1;
+        } else {
+          v0 = row_sum_dpp(red[par][lane]);                        // row r of every wave: total of decoded row r
+        }
+        SSN_BSTAMP(bt5);
         if constexpr (SPLIT != 0) {
           if (P > 1) {
             // Split ensemble: the members publish their four sums and read their partners' (tools/xcd_exchange.hip measured
@@ -707,17 +841,27 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           }
         }
         F0 = __builtin_fmaf(la0, F0, lb0 * v0);                    // rows without a filter: la = lb = 0
+        if constexpr (HC > 0) {
+          // (the last instruction of the HC groups' state halves: between the filter update and the v_readlane that reads it)
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int g = 0; g < HC; ++g) W0h[g] = pk_clamp01(s[g]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
         if constexpr (DOUT > 4) {
-          v1 = row_sum_dpp(red[par][64 + lane]);
+          if constexpr (PIPE) v1 = row_sum_dpp(v1); else v1 = row_sum_dpp(red[par][64 + lane]);
           F1 = __builtin_fmaf(la1, F1, lb1 * v1);
         }
+        // pipelined: the next timestep's input first, the hand-off to the post stage behind it (the row was read in front of the
+        // wave reduction: no LDS operation between the totals and the first encode FMA)
+        if constexpr (PIPE) assemble_x(xnx);
         if (wave == 0 && member == 0) {
           if ((lane & 15) == 0 && (lane >> 4) < DOUT) os[jj][lane >> 4] = v0;
           if (DOUT > 4 && lane == 0) os[jj][4] = v1;
         }
-        SSN_BSTAMP(bt5);
+        SSN_BSTAMP(bt6);
         SSN_BSTAMP_ADD(0, bt0, bt1); SSN_BSTAMP_ADD(1, bt1, bt2); SSN_BSTAMP_ADD(2, bt2, bt3); SSN_BSTAMP_ADD(3, bt3, bt4);
-        SSN_BSTAMP_ADD(4, bt4, bt5);
+        SSN_BSTAMP_ADD(4, bt4, bt6); SSN_BSTAMP_ADD(5, bt4, bt5);
       } else {
         T acc[DOUT];
 #pragma unroll
@@ -752,6 +896,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
     asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(bm1), "=s"(br1) :: "memory");
     if (lane == 0) {
       for (int i = 0; i < 5; ++i) atomicAdd(&g_block_stamps[i], bst[i]);
+      atomicAdd(&g_block_stamps[8], bst[5]);
       atomicAdd(&g_block_stamps[5], (unsigned long long)a.B);
       if (k == 0 && wave == 0) { atomicAdd(&g_block_stamps[6], bm1 - bm0); atomicAdd(&g_block_stamps[7], br1 - br0); }
     }
@@ -778,7 +923,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     const int i0 = (g * nthr + tid2) * PK;
-    if constexpr (F32) s[g] = (f32x2){lif_word_out(s[g].x, lc.K), lif_word_out(s[g].y, lc.K)};
+    if constexpr (F32) s[g] = (f32x2){lif_word_out(s[g].x, lcK), lif_word_out(s[g].y, lcK)};
     if (i0 < n_loc) *reinterpret_cast<G*>(Sp + i0) = s[g];         // (padding elements of the row are never read back)
   }
   if (a.B > 0 && member == 0) {

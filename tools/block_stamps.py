@@ -6,7 +6,9 @@ Needs the diagnostic build of the library (s_memtime stamps between the sections
     SSN_HIP_LIB=$PWD/semantic-spiking-neural-slam-2023_amd/libssn_hip_stamps.so python tools/block_stamps.py [ssp_dim n_per_vco steps]
 
 Prints, per kernel variant, the shader cycles one wave spends per timestep in each section (mean over all waves and
-timesteps of the launch) and the launch time; the stamps themselves cost ~5 x (s_memtime + s_waitcnt) per timestep, so
+timesteps of the launch) and the launch time; the tail behind the barrier is printed in two parts - from the LDS read of
+the wave sums to the totals, and from the totals to the next timestep's input (filter update, v_readlane, x, hand-off; in
+the pipelined loop the input assembly belongs to it and its own row is empty); the stamps themselves cost ~5 x (s_memtime + s_waitcnt) per timestep, so
 the launch time of the stamped build is printed next to the plain build's (SSN_HIP_LIB unset, same process impossible:
 run tools/bench_block.py for that figure).
 """
@@ -31,6 +33,7 @@ try:
 except AttributeError:
     sys.exit("this library has no block stamps: build it with F32_EXTRA=-DSSN_BLOCK_STAMPS and point SSN_HIP_LIB at it")
 fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_uint64), C.c_int]
+NST = 9                                            # words the library writes (a build without the totals stamp: 8, the ninth stays 0)
 
 s = H.make_ssp_space(2, d)
 path, vels = H.make_random_path(20.0, limit=0.1, seed=0)
@@ -46,7 +49,7 @@ for v in variants:
     os.environ.pop("SSN_BLOCK_VARIANT", None)
     sim.prepare(3 * steps)
     sim.run_steps(steps, collect=False)
-    out = (C.c_uint64 * 8)()
+    out = (C.c_uint64 * NST)()
     fn(out, 1)                                   # drop the warm-up launch's stamps
     sim.run_steps(steps, profile=True, collect=False)
     c0 = sim.counters()
@@ -61,5 +64,8 @@ for v in variants:
           "%.0f cycles per wave-timestep between the stamps" % (v, c["block_threads"], c["block_threads"] // 256, us, steps, clock, tot / wave_steps))
     for i, nm in enumerate(names):
         print("    %-40s %8.1f cycles per wave-timestep  %5.1f %%" % (nm, st[i] / wave_steps, 100.0 * st[i] / tot))
+    if st[8]:
+        print("      of it: LDS read of the wave sums -> totals ready         %8.1f" % (st[8] / wave_steps))
+        print("             totals ready -> end of the timestep              %8.1f" % ((st[4] - st[8]) / wave_steps))
     sys.stdout.flush()
     sim.close()

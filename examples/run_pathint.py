@@ -8,6 +8,11 @@
 Writes ``<save-dir>/pi_backend_<backend>..._sspdim_<d>_pinneurons_<n>_T_<T>_limit_<limit>_seed_<seed>.npz`` with the
 field names ``plot_trials_2d.py`` of the reference reads (ts, path, real_ssp, pi_sim_out, pi_sims, pi_path, pi_error,
 elapsed_time, ...).  Only plotting (``--plot``) and the Loihi back ends are not provided.
+
+``--spike-probes M`` adds the neuron probes of the reference's ``experiments/run_pathint_gif.py``
+(``nengo.Probe(pathintegrator.oscillators.ea_ensembles[k].neurons[:500], synapse=None, sample_every=100*dt)``) for the
+oscillators k = 1 .. M; with ``--save`` their samples go to ``<result file minus .npz>_spikes.npz`` as ``vco_n<k>``, with
+the sample times ``ts``.
 """
 import argparse
 import os
@@ -44,6 +49,8 @@ def parse(argv=None):
     p.add_argument("--save-name-extra", default="")
     p.add_argument("--n-eval-points", default=0, type=int,
                    help="decoder-solve evaluation points per ensemble; 0 = nengo's default max(1500, 2 n)")
+    p.add_argument("--spike-probes", default=0, type=int,
+                   help="probe neurons[:500] of the oscillators 1..M every 100 steps (run_pathint_gif.py probes 1, 2 and 3)")
     return p.parse_args(argv)
 
 
@@ -67,6 +74,14 @@ def main(argv=None):
         space = HexagonalSSPSpace(domain_dim, ssp_dim=args.ssp_dim, domain_bounds=bounds, length_scale=args.length_scale)
     neuron_type = {"lif": nengo.LIF, "lifrate": nengo.LIFRate, "relu": nengo.RectifiedLinear}[args.neuron_type]()
     pm = H.make_pathint_model(space, path, vels, args.pi_n_neurons, tau=tau, neuron_type=neuron_type, seed=args.seed, dt=dt)
+    skip = 100
+    spike_probes = {}
+    oscillators = pm.pathintegrator.oscillators.ea_ensembles
+    if not 0 <= args.spike_probes < len(oscillators):
+        raise SystemExit("--spike-probes %d: the path integrator has oscillators 1 .. %d" % (args.spike_probes, len(oscillators) - 1))
+    with pm.model:
+        for k in range(1, args.spike_probes + 1):
+            spike_probes[k] = nengo.Probe(oscillators[k].neurons[:500], synapse=None, sample_every=skip * dt)
     dtype = "f64" if args.backend.endswith("f64") else "f32"
     t0 = time.time()
     sim = Simulator(pm.model, dt=dt, dtype=dtype, n_eval_points=args.n_eval_points or None)
@@ -76,6 +91,7 @@ def main(argv=None):
         sim.run(T)
         elapsed_thread_time, elapsed_time = time.thread_time() - start, time.time() - start2
         out, ts = sim.data[pm.probe], sim.trange()
+        spikes, spike_ts = {k: np.array(sim.data[p]) for k, p in spike_probes.items()}, sim.trange(sample_every=skip * dt)
     n = out.shape[0]
     est, sims, err = H.pathint_metrics(space, out, pm.real_ssp[:n], path[:n])
     print("d = %d, %d VCOs x %d neurons, T = %.1f s: build %.1f s, run %.2f s (%.1f sim-s/wall-s); similarity to the true SSP "
@@ -88,6 +104,12 @@ def main(argv=None):
         H.save_pathint_results(os.path.join(args.save_dir, name), space, ts, path, pm.real_ssp, out, elapsed_time, args=args,
                                elapsed_thread_time=elapsed_thread_time)
         print("saved", os.path.join(args.save_dir, name))
+        if spikes:
+            spike_name = name[:-len(".npz")] + "_spikes.npz"
+            np.savez(os.path.join(args.save_dir, spike_name), ts=spike_ts, **{"vco_n%d" % k: v for k, v in spikes.items()})
+            print("saved", os.path.join(args.save_dir, spike_name))
+    for k, v in spikes.items():
+        print("oscillator %d: %d samples of %d neurons, %.1f %% of them spikes" % (k, v.shape[0], v.shape[1], 100.0 * (v != 0).mean()))
     return out
 
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSN_ABI_VERSION 8
+#define SSN_ABI_VERSION 9
 
 enum ssn_status {
   SSN_OK = 0,
@@ -38,7 +38,7 @@ enum ssn_status {
 };
 
 enum ssn_dtype { SSN_F32 = 0, SSN_F64 = 1 };           /* arithmetic + state type of a simulator   */
-enum ssn_buffer_kind { SSN_BUF_REAL = 0, SSN_BUF_I32 = 1 };
+enum ssn_buffer_kind { SSN_BUF_REAL = 0, SSN_BUF_I32 = 1, SSN_BUF_TAPS = 2 /* ssn_tap_desc records: ssn_model_desc.n_taps */ };
 enum ssn_neuron { SSN_LIF = 0, SSN_LIFRATE = 1, SSN_RELU = 2 };
 
 /* Operator kinds; field use per kind is listed next to ssn_op_desc. */
@@ -49,8 +49,8 @@ enum ssn_op_kind {
 };
 
 typedef struct ssn_buffer_desc {
-  const void* data;     /* float64 (SSN_BUF_REAL) or int32 (SSN_BUF_I32) host array, C order */
-  int64_t count;        /* number of elements                                               */
+  const void* data;     /* float64 (SSN_BUF_REAL) or int32 (SSN_BUF_I32) host array, C order; ssn_tap_desc records (SSN_BUF_TAPS) */
+  int64_t count;        /* number of elements (records)                                     */
   int32_t kind;         /* ssn_buffer_kind                                                  */
   int32_t reserved;
 } ssn_buffer_desc;
@@ -70,6 +70,7 @@ typedef struct ssn_buffer_desc {
  *  ENSARRAY i0 x    i1 K i2 n i3 din i4 dout i5 enc buf [K][din][n] i6 bias buf [K][n]
  *           i7 dec buf [K][dout][n] i8 dst_idx buf (int32 [K][dout]) i9 V buf i10 R buf
  *           i11 neuron                                      f0 tau_rc f1 tau_ref f2 min_voltage
+ *           (all twelve i[] slots are taken: the neuron taps of an array travel as ssn_tap_desc records, ssn_model_desc.n_taps)
  *  NEURONS  i0 J    i1 out   i2 n i3 V buf i4 R buf i5 neuron  f0 tau_rc f1 tau_ref f2 min_voltage f3 amp
  *  PES      i0 W buf i1 rows i2 cols i3 err i4 act          f0 kappa          W += kappa*outer(err,act)
  *  VOJA     i0 E buf i1 rows i2 cols i3 spk i4 key i5 learn i6 scale buf  f0 lr*dt
@@ -99,6 +100,20 @@ typedef struct ssn_probe_desc {
 } ssn_probe_desc;
 
 typedef struct ssn_range { int64_t lo, hi; } ssn_range;   /* signal range [lo, hi) */
+
+/* Neuron tap of an ENSARRAY operator (ABI 9): after the neuron step of every timestep
+ *   sig[dst + j] = amp * a[k][first + j],  j = 0 .. count - 1
+ * with a the unit-amplitude neuron output of ensemble k (spike 0 / 1, or the rate): what Probe(member.neurons[first:first+count])
+ * samples.  At most one tap per ensemble; the tap signals overlap neither each other nor the operator's decoded rows.
+ * The records travel as the LAST entry of ssn_model_desc.buffers, kind SSN_BUF_TAPS, count = ssn_model_desc.n_taps (the
+ * descriptor keeps its size and field offsets: n_taps took its spare word, and no operator refers to that buffer). */
+typedef struct ssn_tap_desc {
+  int32_t op;           /* index into ops[]: an SSN_OP_ENSARRAY of the per-timestep core */
+  int32_t k;            /* ensemble of that array, 0 .. K - 1 */
+  int64_t first, count; /* neurons [first, first + count) of it, inside 0 .. n */
+  int64_t dst;          /* signal offset of the tap's first element */
+  double amp;           /* amplitude / dt for spiking LIF, amplitude for the rate neurons */
+} ssn_tap_desc;
 
 /* Plan switches: the bits of ssn_model_desc.flags.  Debug / A-B switches, default 0; tests check that every alternative
  * plan gives the same results.  ssn_create refuses a value with any other bit set.
@@ -162,7 +177,7 @@ enum ssn_plan_flag {
   /* split ensembles in the whole-block kernel (f32, at most 4 decoded rows): an array with fewer ensembles than the GPU
    * has CUs (a 4- or 8-GPU shard of config 2) is stepped by 2 or 4 member workgroups per ensemble that exchange their
    * partial sums every timestep; needs every workgroup of the launch resident at once, i.e. the GPU for this process
-   * alone */
+   * alone.  Not available for an array with neuron taps (ssn_create: SSN_EUNSUPPORTED) */
   SSN_PLAN_SPLIT_BLOCK = 1073741824
 };
 /* every bit that has a name */
@@ -198,7 +213,7 @@ typedef struct ssn_model_desc {
    * ranges are completed by an all-reduce between the two phases of every timestep.  The library does not communicate: the
    * caller steps with ssn_run_phase(0), exchanges (ssn_exchange_pack -> all-reduce -> ssn_exchange_unpack), ssn_run_phase(1). */
   int32_t n_exchange;
-  int32_t reserved;
+  int32_t n_taps;                     /* neuron taps of the ensemble arrays (ABI 9; 0: none): buffers[n_buffers - 1] then holds n_taps ssn_tap_desc records */
   const ssn_range* exchange;
   int32_t block_steps;                /* timesteps per time-batched block; 0 = library default (1024, or 256 for very wide models) */
   int32_t flags;                      /* plan switches: an OR of ssn_plan_flag values (default 0) */

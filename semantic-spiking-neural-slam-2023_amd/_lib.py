@@ -9,9 +9,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSN_HIP_LIB") or os.path.join(_HERE, "libssn_hip.so")     # override: A/B builds of the library
 
-SSN_ABI_VERSION = 8
+SSN_ABI_VERSION = 9
 SSN_F32, SSN_F64 = 0, 1
-SSN_BUF_REAL, SSN_BUF_I32 = 0, 1
+SSN_BUF_REAL, SSN_BUF_I32, SSN_BUF_TAPS = 0, 1, 2
 NEURON_CODE = {"lif": 0, "lifrate": 1, "relu": 2}
 OP_CODE = {"fill": 1, "table": 2, "axpy": 3, "matvec": 4, "lowpass": 5, "ensarray": 6, "neurons": 7,
            "pes": 8, "voja": 9, "cleanup": 10, "gate": 11, "lincomb": 12}
@@ -60,6 +60,11 @@ class Range(C.Structure):
     _fields_ = [("lo", C.c_int64), ("hi", C.c_int64)]
 
 
+class TapDesc(C.Structure):
+    _fields_ = [("op", C.c_int32), ("k", C.c_int32), ("first", C.c_int64), ("count", C.c_int64), ("dst", C.c_int64),
+                ("amp", C.c_double)]
+
+
 class ModelDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32), ("n_tables", C.c_int32),
                 ("dt", C.c_double), ("n_signals", C.c_int64), ("signal_init", C.POINTER(C.c_double)),
@@ -67,7 +72,7 @@ class ModelDesc(C.Structure):
                 ("steps_per_graph", C.c_int32), ("buffers", C.POINTER(BufferDesc)), ("ops", C.POINTER(OpDesc)),
                 ("probes", C.POINTER(ProbeDesc)), ("n_pre_to_core", C.c_int32), ("n_core_to_post", C.c_int32),
                 ("pre_to_core", C.POINTER(Range)), ("core_to_post", C.POINTER(Range)),
-                ("n_exchange", C.c_int32), ("reserved", C.c_int32), ("exchange", C.POINTER(Range)),
+                ("n_exchange", C.c_int32), ("n_taps", C.c_int32), ("exchange", C.POINTER(Range)),
                 ("block_steps", C.c_int32), ("flags", C.c_int32)]
 
 

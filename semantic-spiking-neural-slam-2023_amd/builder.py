@@ -19,6 +19,10 @@ Operator kinds (dict ``kind``):
   matvec    dst (+)= W[rows x cols] @ src                  (W is a buffer; mode "inc" | "set")
   lowpass   dst = a*dst + (1-a)*gain*src                   (Appendix A.6, an *update*)
   ensarray  K equal ensembles: J = bias + enc.x ; neuron step ; decoded rows -> sig[dst_idx]
+            optional ``taps`` [(k, first, count, dst)], k relative to ``k_lo``: after the neuron step
+            sig[dst + j] = tap_amp * a[k, first + j] (the neuron output ``Probe(member.neurons[...])`` samples; one tap
+            per member, the hull of its probed slices).  The device kernels write them; ``oracle.OracleSimulator`` is
+            frozen and does not know taps - its rows for such probes stay zero (``oracle.graphwalk`` is their reference)
   neurons   neuron step on a current vector J -> spike vector
   pes / voja / cleanup / gate                              (SLAM; Appendix A.7, A.8, slam.py:212-237)
 """
@@ -287,6 +291,8 @@ class Builder:
         conns = self._drop_dead_ends(conns, nodes, probes)
         for c in conns:
             self._lower_connection(c)
+        self.tap_hull = self._tap_hulls(probes)
+        self.tap_ref = {}
         for p in probes:
             self._lower_probe(p)
         for e in ensembles:
@@ -887,7 +893,10 @@ class Builder:
         m = self.model
         label = getattr(blk["net"], "label", None) or "ensarray"
         x = blk["x"].slice(lo * din, K * din)
-        self.op("ensarray", x=x, K=K, n=n, din=din, dout=dout,
+        taps = [(i - lo,) + self.tap_hull[id(ens[i])] + (self.tap_ref[id(ens[i])],)
+                for i in range(lo, hi) if id(ens[i]) in self.tap_ref]
+        extra = dict(taps=taps, tap_amp=amp) if taps else {}
+        self.op("ensarray", x=x, K=K, n=n, din=din, dout=dout, **extra,
                 enc=m.add_buffer(enc, f"{label}_enc"), bias=m.add_buffer(bias, f"{label}_bias"),
                 dec=m.add_buffer(dec, f"{label}_dec"), dst_refs=dst_idx,
                 v=m.add_buffer(np.zeros((K, n)), f"{label}_voltage", role="state"),
@@ -895,6 +904,21 @@ class Builder:
                 neuron=nd, label=label, k_lo=lo, k_total=K_all, partial_out=bool(self.neuron_shard is not None and K < K_all))
 
     # -- probes ----------------------------------------------------------------------------
+    def _tap_hulls(self, probes):
+        """id(member) -> (first, count): the hull of all probed neuron slices of an EnsembleArray member (one tap each)."""
+        hull = {}
+        for p in probes:
+            obj, start, length = _contig(p.target)
+            if _kind(obj) != "neurons" or id(obj.ensemble) not in self.block_of:
+                continue
+            e = obj.ensemble
+            lo, hi = (0, e.n_neurons) if length is None else (start, start + length)
+            if lo < 0 or hi > e.n_neurons:
+                raise fe.BuildError(f"slice [{lo}:{hi}] outside the {e.n_neurons} neurons of {e!r}")
+            a, b = hull.get(id(e), (lo, hi))
+            hull[id(e)] = (min(a, lo), max(b, hi))
+        return {k: (lo, hi - lo) for k, (lo, hi) in hull.items()}
+
     def _lower_probe(self, p):
         obj, start, length = _contig(p.target)
         k = _kind(obj)
@@ -929,10 +953,24 @@ class Builder:
         elif k == "neurons":
             e = obj.ensemble
             if id(e) in self.block_of:
-                raise fe.BuildError("probing neurons of an EnsembleArray member is not supported yet")
-            if self._is_sharded(e):
-                raise fe.BuildError("probing the neurons of a neuron-sharded ensemble is not supported")
-            full = self.ens_spk[id(e)]
+                # a member's spikes exist only inside the ensemble kernels: the array operator gets a tap that writes the
+                # probed range of the neuron output into a signal of its own (W arena) every timestep
+                if attr != "output":
+                    raise fe.BuildError(f"probing {attr!r} of the neurons of an EnsembleArray member is not supported "
+                                        "(only the neuron output)")
+                if self.vco_shard is not None:
+                    raise fe.BuildError("probing the neurons of an EnsembleArray member is not supported with sharding "
+                                        "(vco_shard / neuron_shard builds)")
+                first, count = self.tap_hull[id(e)]
+                if id(e) not in self.tap_ref:
+                    self.tap_ref[id(e)] = self.alloc("W", count)
+                full = self.tap_ref[id(e)]
+                start, length = (0, e.n_neurons) if length is None else (start, length)
+                start -= first
+            else:
+                if self._is_sharded(e):
+                    raise fe.BuildError("probing the neurons of a neuron-sharded ensemble is not supported")
+                full = self.ens_spk[id(e)]
         else:
             raise fe.BuildError(f"unsupported probe target {obj!r}")
         src = full if length is None else full.slice(start, length)
@@ -969,6 +1007,8 @@ class Builder:
                 refs = o.pop("dst_refs")
                 idx = np.array([[A(r) for r in row] for row in refs], dtype=np.int32)
                 o["dst_idx"] = m.add_buffer(idx, f"{o['label']}_dst_idx", role="index")
+                if "taps" in o:
+                    o["taps"] = [(k, first, count, A(r)) for k, first, count, r in o["taps"]]
             ops.append(o)
         for p in m.probes:
             if "src" in p:
@@ -1079,6 +1119,7 @@ def op_access(o, model):
                 start = v
             prev = v
         runs.append(S(start, prev - start + 1))
+        runs += [S(dst, count) for _, _, count, dst in o.get("taps", ())]
         return runs, [], [S(o["x"], o["K"] * o["din"])], [B(o["v"]), B(o["r"])]
     if k == "neurons":
         return [S(o["out"], o["n"])], [], [S(o["j"], o["n"])], [B(o["v"]), B(o["r"])]
@@ -1301,6 +1342,8 @@ def shard_phases(model, shard):
             need_full(o["x"], o["K"] * o["din"], "an ensemble array")
             idx = model.buffers[o["dst_idx"]].reshape(-1)
             full[idx], part[idx] = (not o.get("partial_out")), bool(o.get("partial_out"))
+            for _, _, count, dst in o.get("taps", ()):      # (refused for sharded builds: a member's own spikes would be local)
+                full[dst:dst + count], part[dst:dst + count] = True, False
         elif k == "neurons":
             need_full(o["j"], o["n"], "a neuron population")      # (a partial current must never reach the non-linearity)
             sl = slice(o["out"], o["out"] + o["n"])

@@ -352,8 +352,13 @@ constexpr BlockHoist block_hoist(bool pipe, int tpb, int ng) {
 //     (identical in all waves: deterministic).  The totals stay "lane-distributed" (row r of a register = decoded row
 //     r): the Lowpass update of the recurrent filter states is ONE v_fma on that register with per-lane constants, and
 //     only the (at most DIN) states the next input needs are broadcast with v_readlane.
-template <typename T, int DIN, int DOUT, int NPT, int TPB, int LDSW, int SPLIT = 0>      // LDSW: 0 all parameters in registers | DIN: the encoder rows in LDS
+// TAP: the tapped twin (neuron probes on members of the array, BlockArgs::tap_slot): the workgroup of a tapped ensemble also
+// stores amp * spike of the tapped neurons into the timestep's row of the block buffer - global stores inside the time loop
+// of those workgroups only (a wave-uniform test; every other workgroup of the launch runs the plain loop's instructions).
+// Its own instantiation, as SPLIT: an array without taps launches the kernel it always launched.
+template <typename T, int DIN, int DOUT, int NPT, int TPB, int LDSW, int SPLIT = 0, int TAP = 0>      // LDSW: 0 all parameters in registers | DIN: the encoder rows in LDS
 __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT: an ensemble over a.P member workgroups (own instantiation: the plain kernel's loop stays as it is)
+  static_assert(!(SPLIT && TAP), "the split kernel has no tapped form");
   constexpr bool ENC_LDS = LDSW == DIN;
   // (Encoders AND bias in LDS - rows as long as the padded neuron count, 160 000 of the CU's 163 840 bytes at n = 10 000 -
   //  were built and measured in round 2: (768, 14) 3.68 ms and (1024, 10) 3.64 ms per 1000 timesteps of config 2 against
@@ -387,6 +392,12 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
   T* __restrict__ Sp = a.S + (size_t)k * row + noff;
   const NeuronParams<T> np = a.np;
   const LifMath<T> lm(np);
+  // tapped twin: this ensemble's row of destination signals per device column (workgroup-uniform; nullptr: no tap here)
+  const int* tcol = nullptr;
+  if constexpr (TAP != 0) {
+    const int tslot = a.tap_slot[k];
+    if (tslot >= 0) tcol = a.tap_col + (size_t)tslot * row;
+  }
   // (uniform values: readfirstlane moves them to scalar registers, where the packed instructions of the time loop can take
   //  them as their one constant-bus operand)
   auto uni = [](float v) { return bits_f(__builtin_amdgcn_readfirstlane(f_bits(v))); };
@@ -714,6 +725,25 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           // the state word is final HERE: without this the compiler sinks the rcp / log half of every group's step to the
           // end of the timestep and keeps its operands live until then
           if constexpr (F32) asm volatile("" : "+v"(s[g]));
+          if constexpr (TAP != 0) {
+            // spk is 0 or 1: amp * spk is exact.  The row of the block buffer, addressed as the hand-off of the decoded rows
+            // addresses it; the destinations are looked up here, not kept in registers across the time loop
+            if (tcol) {
+              const int i0 = (g * nthr + tid) * PK;
+              T* const trow = a.bsig + (size_t)(a.row0 + j0 + jj) * a.n_sig;
+              if (i0 < n_loc) {
+                if constexpr (F32) {
+                  const int2 d = *reinterpret_cast<const int2*>(tcol + i0);
+                  const f32x2 val = spk[u] * a.tap_amp;
+                  if (d.x >= 0) trow[d.x] = val.x;
+                  if (d.y >= 0) trow[d.y] = val.y;
+                } else {
+                  const int d = tcol[i0];
+                  if (d >= 0) trow[d] = spk[u] * a.tap_amp;
+                }
+              }
+            }
+          }
           if constexpr (F32 && SSN_BLOCK_SKIP == 1) continue;      // (decoded inside the spiking branch above)
 #pragma unroll
           for (int r = 0; r < DOUT; ++r) {           // spk is 0 or 1: exact add
@@ -926,6 +956,23 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
     if constexpr (F32) s[g] = (f32x2){lif_word_out(s[g].x, lcK), lif_word_out(s[g].y, lcK)};
     if (i0 < n_loc) *reinterpret_cast<G*>(Sp + i0) = s[g];         // (padding elements of the row are never read back)
   }
+  if constexpr (TAP != 0) {
+    // the last timestep's tap values also go to the signal vector, like the decoded values below: every thread copies what it
+    // wrote itself to the launch's last row
+    if (tcol && a.B > 0) {
+      const T* const lrow = a.bsig + (size_t)(a.row0 + a.B - 1) * a.n_sig;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const int i0 = (g * nthr + tid2) * PK;
+        if (i0 >= n_loc) continue;
+#pragma unroll
+        for (int c = 0; c < PK; ++c) {
+          const int d = tcol[i0 + c];
+          if (d >= 0) a.sig_w[d] = lrow[d];
+        }
+      }
+    }
+  }
   if (a.B > 0 && member == 0) {
     if constexpr (F32) {
       if (wave == 0 && (lane & 15) == 0 && (lane >> 4) < DOUT) {
@@ -952,22 +999,26 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
 
 constexpr int BLOCK_LDS_BYTES = 160 * 1024, BLOCK_STATIC_LDS = 2560;     // CU capacity; bound on the kernel's static arrays
 
-template <typename T, int DIN, int DOUT, int NPT, int TPB, int LDSW, int SPLIT>
+template <typename T, int DIN, int DOUT, int NPT, int TPB, int LDSW, int SPLIT, int TAP = 0>
 static hipError_t launch_block_variant_s(hipStream_t s, const BlockArgs<T>& a) {
   const int lds = LDSW * a.threads * NPT * (int)sizeof(T);
   static std::atomic<uint64_t> configured{0};
   if (LDSW > 0) {
-    hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(&k_ens_block<T, DIN, DOUT, NPT, TPB, LDSW, SPLIT>),
+    hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(&k_ens_block<T, DIN, DOUT, NPT, TPB, LDSW, SPLIT, TAP>),
                                             BLOCK_LDS_BYTES - BLOCK_STATIC_LDS, configured);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((k_ens_block<T, DIN, DOUT, NPT, TPB, LDSW, SPLIT>), dim3((unsigned)(a.K * (SPLIT ? a.P : 1))), dim3((unsigned)a.threads), lds, s, a);
+  hipLaunchKernelGGL((k_ens_block<T, DIN, DOUT, NPT, TPB, LDSW, SPLIT, TAP>), dim3((unsigned)(a.K * (SPLIT ? a.P : 1))), dim3((unsigned)a.threads), lds, s, a);
   return hipGetLastError();
 }
 template <typename T, int DIN, int DOUT, int NPT, int TPB, int LDSW>
 static hipError_t launch_block_variant(hipStream_t s, const BlockArgs<T>& a) {
   if (a.P > 1) {
     if constexpr (sizeof(T) == 4 && DOUT <= 4) return launch_block_variant_s<T, DIN, DOUT, NPT, TPB, LDSW, 1>(s, a);
+    else return hipErrorInvalidValue;
+  }
+  if (a.tap_slot) {      // the tapped twin (never a silent drop: a build whose time loop leaves slots out has none)
+    if constexpr (SSN_BLOCK_SKIP == 0) return launch_block_variant_s<T, DIN, DOUT, NPT, TPB, LDSW, 0, 1>(s, a);
     else return hipErrorInvalidValue;
   }
   return launch_block_variant_s<T, DIN, DOUT, NPT, TPB, LDSW, 0>(s, a);

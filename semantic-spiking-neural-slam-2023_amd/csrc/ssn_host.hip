@@ -253,6 +253,11 @@ struct Sim final : ssn_sim {
   bool fused_block = false;                   // ... stepped a whole block per launch: [k_ens_block] (ssn_block.hpp)
   ssn::BlockArgs<T> blk;
   std::vector<void*> fused_bufs;
+  // neuron taps of the ensemble arrays (ssn_model_desc.taps, ABI 9): per tapped operator the table its kernels read -
+  // [K][4] = first neuron, count (0: ensemble without a tap), destination signal, index among the operator's taps
+  struct TapSet { std::vector<ssn_tap_desc> list; int* d_tab = nullptr; double amp = 0.0; };
+  std::map<int, TapSet> tap_sets;             // operator index -> its taps
+  const ssn_op_desc* ops_base = nullptr;      // (the model's operator array: valid during ssn_create only)
   std::set<int> sparse_w;                     // decoder buffers multiplied with a LIF spike vector
   std::set<int> learned_w;                    // matrices a learning rule (PES, Voja) updates
   std::vector<std::pair<int64_t, std::pair<int*, int*>>> spike_lists;   // spike signal offset -> (list, count)
@@ -577,6 +582,75 @@ struct Sim final : ssn_sim {
     return SSN_OK;
   }
 
+  // Taps (ABI 9): every range inside its array and inside the signal vector, one tap per ensemble, tap signals disjoint
+  // from each other and from every decoded row of an array.
+  int read_taps(const ssn_model_desc* m) {
+    ops_base = m->ops;
+    for (int i = 0; i < m->n_buffers; ++i)
+      if (m->buffers[i].kind == SSN_BUF_TAPS && (m->n_taps <= 0 || i != m->n_buffers - 1))
+        return fail(SSN_EINVAL, "buffer %d: tap records belong in the last buffer of a model with n_taps > 0", i);
+    if (m->n_taps < 0) return fail(SSN_EINVAL, "n_taps = %d", m->n_taps);
+    if (m->n_taps == 0) return SSN_OK;
+    const ssn_buffer_desc& tb = m->buffers[m->n_buffers > 0 ? m->n_buffers - 1 : 0];
+    if (m->n_buffers < 1 || tb.kind != SSN_BUF_TAPS || tb.count != m->n_taps || !tb.data)
+      return fail(SSN_EINVAL, "n_taps = %d: the last buffer must hold that many ssn_tap_desc records (SSN_BUF_TAPS)", m->n_taps);
+    const ssn_tap_desc* const tap_list = (const ssn_tap_desc*)tb.data;
+    if (opt.has(SSN_PLAN_SPLIT_BLOCK))
+      return fail(SSN_EUNSUPPORTED, "SSN_PLAN_SPLIT_BLOCK does not go with neuron taps (the split whole-block kernel has no tapped form)");
+    std::vector<unsigned char> mark((size_t)n_sig, 0);
+    for (int i = 0; i < m->n_taps; ++i) {
+      const ssn_tap_desc& t = tap_list[i];
+      if (t.op < 0 || t.op >= m->n_ops || m->ops[t.op].kind != SSN_OP_ENSARRAY || m->ops[t.op].stage != 1)
+        return fail(SSN_EINVAL, "tap %d: operator %d is not an ensemble array of the per-timestep core", i, t.op);
+      const ssn_op_desc& o = m->ops[t.op];
+      if (t.k < 0 || t.k >= o.i[1]) return fail(SSN_EINVAL, "tap %d: ensemble %d outside the array's %lld", i, t.k, (long long)o.i[1]);
+      if (t.first < 0 || t.count < 1 || t.first + t.count > o.i[2])
+        return fail(SSN_EINVAL, "tap %d: neurons [%lld,+%lld) outside the ensemble's %lld", i, (long long)t.first, (long long)t.count, (long long)o.i[2]);
+      CHK(check_range(t.dst, t.count, "tap"));
+      TapSet& ts = tap_sets[t.op];
+      for (const ssn_tap_desc& q : ts.list)
+        if (q.k == t.k) return fail(SSN_EINVAL, "tap %d: ensemble %d of operator %d already has a tap", i, t.k, t.op);
+      if (!ts.list.empty() && ts.amp != t.amp) return fail(SSN_EINVAL, "tap %d: the taps of one array share one amplitude", i);
+      ts.amp = t.amp;
+      ts.list.push_back(t);
+      for (int64_t e = t.dst; e < t.dst + t.count; ++e) {
+        if (mark[(size_t)e]) return fail(SSN_EINVAL, "tap %d: its signal range overlaps another tap's", i);
+        mark[(size_t)e] = 1;
+      }
+    }
+    for (int i = 0; i < m->n_ops; ++i) {
+      const ssn_op_desc& o = m->ops[i];
+      if (o.kind != SSN_OP_ENSARRAY) continue;
+      const int32_t* di = (const int32_t*)m->buffers[o.i[8]].data;
+      for (int64_t j = 0; j < o.i[1] * o.i[4]; ++j)
+        if (mark[(size_t)di[j]]) return fail(SSN_EINVAL, "a tap's signal range overlaps a decoded row of operator %d", i);
+    }
+    for (auto& kv : tap_sets) {
+      const int64_t K = m->ops[kv.first].i[1];
+      std::vector<int> tab((size_t)K * 4, 0);
+      for (size_t q = 0; q < kv.second.list.size(); ++q) {
+        const ssn_tap_desc& t = kv.second.list[q];
+        int* row = tab.data() + (size_t)t.k * 4;
+        row[0] = (int)t.first; row[1] = (int)t.count; row[2] = (int)t.dst; row[3] = (int)q;
+      }
+      CHK(dmalloc(&kv.second.d_tab, K * 16));
+      fused_bufs.push_back((void*)kv.second.d_tab);
+      HIPCHK(hipMemcpy(kv.second.d_tab, tab.data(), (size_t)K * 16, hipMemcpyHostToDevice));
+    }
+    return SSN_OK;
+  }
+  const TapSet* taps_of(const ssn_op_desc& o) const {
+    if (tap_sets.empty() || !ops_base) return nullptr;
+    auto it = tap_sets.find((int)(&o - ops_base));
+    return it == tap_sets.end() ? nullptr : &it->second;
+  }
+  // the signal ranges an ensemble array's taps write (data hazards of the item and round plans)
+  const TapSet* taps_of(const ssn::EnsArgs<T>& a) const {
+    if (!a.tap) return nullptr;
+    for (auto& kv : tap_sets) if (kv.second.d_tab == a.tap) return &kv.second;
+    return nullptr;
+  }
+
   int create(const ssn_model_desc* m) {
     device = m->device;
     dt = m->dt;
@@ -706,9 +780,11 @@ struct Sim final : ssn_sim {
         default: return fail(SSN_EINVAL, "unknown operator kind %d", o.kind);
       }
     }
+    CHK(read_taps(m));
     // uploads
     for (int i = 0; i < m->n_buffers; ++i) {
       Buf& b = bufs[i];
+      if (b.kind == SSN_BUF_TAPS) continue;       // (host-side records: read_taps)
       if (b.kind == SSN_BUF_I32) {
         CHK(dmalloc((int32_t**)&b.d, b.count * 4));
         HIPCHK(hipMemcpy(b.d, m->buffers[i].data, (size_t)b.count * 4, hipMemcpyHostToDevice));
@@ -801,6 +877,7 @@ struct Sim final : ssn_sim {
     a.xrows = nullptr; a.n_sig = n_sig; a.ctx = d_ctx; a.n_rec = 0;
     a.fast = ens_fast(o) ? (ens_sparse(o) ? 1 : 2) : 0;
     a.defer = 0; a.sub = 0; a.partials_stride = 0;
+    if (const TapSet* ts = taps_of(o)) { a.tap = ts->d_tab; a.tap_amp = (T)ts->amp; a.tap_sig = sig; a.tap_rows = nullptr; }
     ens_chunking(a);
   }
 
@@ -1102,6 +1179,34 @@ struct Sim final : ssn_sim {
     return SSN_OK;
   }
 
+  // Taps of the whole-block kernel: which workgroups have one (tap_slot[k], -1: none) and, per tapped ensemble, the
+  // destination signal of every column of its row in the DEVICE's neuron order (-1: not tapped) - the order may be a
+  // permutation of the caller's (reorder_block_neurons), so the kernel looks the destination up instead of computing it.
+  int block_taps(const ssn_op_desc& eo) {
+    const TapSet* ts = taps_of(eo);
+    if (!ts) return SSN_OK;
+    const int64_t K = eo.i[1], n = eo.i[2], row = blk.n_pad;
+    const Buf& eb = bufs[(size_t)eo.i[5]];
+    std::vector<int> slot((size_t)K, -1), col(ts->list.size() * (size_t)row, -1);
+    for (size_t q = 0; q < ts->list.size(); ++q) {
+      const ssn_tap_desc& t = ts->list[q];
+      slot[(size_t)t.k] = (int)q;
+      for (int64_t c = 0; c < n; ++c) {
+        const int64_t orig = eb.perm ? (*eb.perm)[(size_t)(t.k * n + c)] : c;
+        if (orig >= t.first && orig < t.first + t.count) col[q * (size_t)row + (size_t)c] = (int)(t.dst + orig - t.first);
+      }
+    }
+    int* d_slot = nullptr; int* d_col = nullptr;
+    CHK(dmalloc(&d_slot, K * 4));
+    fused_bufs.push_back((void*)d_slot);
+    CHK(dmalloc(&d_col, (int64_t)col.size() * 4));
+    fused_bufs.push_back((void*)d_col);
+    HIPCHK(hipMemcpy(d_slot, slot.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_col, col.data(), col.size() * 4, hipMemcpyHostToDevice));
+    blk.tap_slot = d_slot; blk.tap_col = d_col; blk.tap_amp = (T)ts->amp;
+    return SSN_OK;
+  }
+
   // Core stage == one recurrent ensemble array (the path integrator's VCO array): x assembled in the
   // kernel prologue, decoded rows / synapse update / hand-off / step counter in one barrier-free finish
   // kernel.  Returns false (and plans nothing) when the core does not have that shape.
@@ -1267,6 +1372,7 @@ struct Sim final : ssn_sim {
       //  so the neuron order is the caller's unless SSN_BLOCK_SORT=1 asks for the slot order)
       if (sizeof(T) == 4 && split_P == 1 && opt.block_sort)
         *rc = reorder_block_neurons(m, eo, blk_npt == 2 ? blk_threads : blk_tpb, blk_npt);
+      if (*rc == SSN_OK) *rc = block_taps(eo);
       return true;
     }
     // ---- plan B: [k_ensarray (fused prologue), k_ens_finish] ------------------------------------------
@@ -1274,6 +1380,7 @@ struct Sim final : ssn_sim {
     fill_ens_args(eo, it.ens);
     ssn::EnsArgs<T>& a = it.ens;
     a.xrows = bsig;
+    if (a.tap) a.tap_rows = bsig;      // (a fused core has no hand-off operator: the kernel writes the post stage's rows itself)
     // measured on MI355X (tools/bench_shard.py): 5080 workgroups (config 2 on one GPU) 35.4 us/step with the
     // separate finish kernel vs 37.4 deferred; 2540 / 1270 / 640 workgroups (2 / 4 / 8-GPU shards) 24.5 / 15.8 /
     // 13.1 vs 22.0 / 12.5 / 9.4 deferred
@@ -1859,7 +1966,8 @@ struct Sim final : ssn_sim {
 
   // k_round body of an ensemble array (-1: its variant has none, it is launched on its own)
   int ens_round_kind(const ssn::EnsArgs<T>& a) const {
-    if (a.defer || a.xrows || opt.has(SSN_PLAN_ENS_OWN_LAUNCH)) return -1;
+    // (a tapped array is launched on its own - k_ensarray's tapped twin: the bodies of the round grid do not know taps)
+    if (a.defer || a.xrows || a.tap || opt.has(SSN_PLAN_ENS_OWN_LAUNCH)) return -1;
     if (a.fast == 1 && a.din == 3 && a.dout == 4) return ssn::RK_ENS_3_4_S;
     if (a.fast == 1 && a.din == 3 && a.dout == 5) return ssn::RK_ENS_3_5_S;
     if (a.fast == 2 && a.din == 1 && a.dout == 1) {
@@ -2923,6 +3031,7 @@ struct Sim final : ssn_sim {
     switch (it.type) {
       case IT_ENS:
         if (it.ens.direct) acc_index_list(a, (const void*)it.ens.didx, true);
+        if (const TapSet* ts = taps_of(it.ens)) for (const ssn_tap_desc& t : ts->list) acc_sig(a, t.dst, t.count, true);
         acc_sig(a, it.ens.x_off, (int64_t)it.ens.K * it.ens.din, false);
         for (int j = 0; j < it.ens.n_rec; ++j) acc_sig(a, it.ens.rec_src[j], it.ens.rec_len[j], false);      // (folded input terms)
         acc_ptr(a, it.ens.partials, true); acc_ptr(a, it.ens.V, true); acc_ptr(a, it.ens.R, true);
@@ -4003,6 +4112,6 @@ int ssn_device_count(void) {
   return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 const char* ssn_last_error(void) { return g_err.c_str(); }
-const char* ssn_version(void) { return "libssn_hip 0.9 (gfx950, ABI 8)"; }
+const char* ssn_version(void) { return "libssn_hip 0.9 (gfx950, ABI 9)"; }
 
 }  // extern "C"

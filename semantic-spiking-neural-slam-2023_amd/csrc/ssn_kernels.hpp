@@ -117,7 +117,9 @@ __device__ inline T wave_sum(T v) {
 // ---------------------------------------------------------------------------------------------
 template <int DOUT> struct DecPitch { static constexpr int value = DOUT <= 4 ? 4 : 8; };
 
-template <typename T, int DIN, int DOUT, int MODE, bool RND = false>   // MODE 0 generic | 1 fast, spike-sparse decoders | 2 fast, dense decoders; RND: a body of the round grid
+// TAP: the array has neuron taps (EnsArgs::tap) - an instantiation of its own, so that an array without taps runs the code it
+// always ran; the bodies of the round grid have no tapped form (a tapped array is launched on its own: Sim::ens_round_kind)
+template <typename T, int DIN, int DOUT, int MODE, bool RND = false, bool TAP = false>   // MODE 0 generic | 1 fast, spike-sparse decoders | 2 fast, dense decoders; RND: a body of the round grid
 __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsigned char* smem) {   // smem: 4 * DOUT + DIN values of T
   if (bx >= a.K * a.P) return;          // (grid.x is sized for the larger array of a batch)
   using vec = typename VecT<T>::type;
@@ -157,6 +159,23 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
   T x[DIN];
   long long step = 0;
   if (a.xrows || a.defer) step = a.ctx->step + a.sub;
+  // neuron tap of this ensemble (workgroup-uniform; tp_cnt = 0 for an ensemble - or a whole array - without one)
+  int tp_first = 0, tp_cnt = 0;
+  T* tp_out = nullptr;
+  T* tp_row = nullptr;
+  if (TAP && a.tap) {
+    const int* t = a.tap + 4 * (size_t)k;
+    tp_first = t[0]; tp_cnt = t[1];
+    tp_out = a.tap_sig + t[2];
+    if (a.tap_rows) tp_row = a.tap_rows + (size_t)(step - a.ctx->block_start + 1) * a.n_sig + t[2];
+  }
+  auto tap_store = [&](int i, T val) {      // neuron i of the ensemble, val = amp * activity
+    const unsigned q = (unsigned)(i - tp_first);
+    if (q < (unsigned)tp_cnt) {
+      tp_out[q] = val;
+      if (tp_row) tp_row[q] = val;
+    }
+  };
   // (the self-finishing form exists in the round grid only: in the stand-alone kernel - config 4's - its branch cost 1 %)
   if (RND && a.defer == 2) {      // (no host path sets defer == 2 any more: the self-finishing array was removed from the planner)
     // Round plan (round 4): the array completes ITS OWN previous timestep.  Every workgroup of ensemble k sums the P partial
@@ -260,6 +279,7 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
 #pragma unroll
           for (int d = 0; d < DIN; ++d) J += e[d][j] * x[d];
           const T act = neuron_step(np, J, Vv[j], Rv[j]);
+          if (TAP && tp_cnt) tap_store((int)o + j, a.tap_amp * act);
 #pragma unroll
           for (int r = 0; r < DOUT; ++r) acc[r] += act * dd[r][j];
         }
@@ -291,6 +311,7 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
             V = T(0);
           }
           Vv[j] = R > np.dt ? -R : V;       // voltage is exactly 0 whenever R > dt
+          if (TAP && tp_cnt) tap_store((int)o + j, spiked[j] ? a.tap_amp : T(0));
         }
       }
       *(vec*)(Vp + o) = *(vec*)Vv;
@@ -398,10 +419,10 @@ __device__ __forceinline__ void ens_small_body(const EnsArgs<T>& a, const int bx
   }
 }
 
-template <typename T, int DIN, int DOUT, int MODE>
+template <typename T, int DIN, int DOUT, int MODE, bool TAP = false>
 __global__ __launch_bounds__(256) void k_ensarray(EnsBatch<T> batch) {
   __shared__ __align__(16) unsigned char smem[(4 * DOUT + DIN) * sizeof(T)];
-  ens_body<T, DIN, DOUT, MODE>(batch.a[blockIdx.y], (int)blockIdx.x, smem);
+  ens_body<T, DIN, DOUT, MODE, false, TAP>(batch.a[blockIdx.y], (int)blockIdx.x, smem);
 }
 
 // decoder re-layout [K][dout][n] (row-major, host order, ld = n_pad) <-> [K][n_pad][DP] (neuron-major)
@@ -483,9 +504,15 @@ static hipError_t launch_ens_dout(hipStream_t s, const EnsBatch<T>& b, int count
   const EnsArgs<T>& a = b.a[0];
   int wgs = 0;
   for (int i = 0; i < count; ++i) wgs = std::max(wgs, b.a[i].K * b.a[i].P);
+  bool tap = false;                     // any array of the batch with neuron taps: the tapped twin (it tests a.tap per array)
+  for (int i = 0; i < count; ++i) tap = tap || b.a[i].tap != nullptr;
   const dim3 grid((unsigned)wgs, (unsigned)count), block(256);
   switch (a.dout) {
-#define SSN_CASE(D) case D: hipLaunchKernelGGL((k_ensarray<T, DIN, D, MODE>), grid, block, 0, s, b); break;
+#define SSN_CASE(D)                                                                                  \
+  case D:                                                                                            \
+    if (tap) hipLaunchKernelGGL((k_ensarray<T, DIN, D, MODE, true>), grid, block, 0, s, b);          \
+    else hipLaunchKernelGGL((k_ensarray<T, DIN, D, MODE>), grid, block, 0, s, b);                    \
+    break;
     SSN_CASE(1) SSN_CASE(2) SSN_CASE(3) SSN_CASE(4) SSN_CASE(5) SSN_CASE(6) SSN_CASE(7) SSN_CASE(8)
 #undef SSN_CASE
     default: return hipErrorInvalidValue;

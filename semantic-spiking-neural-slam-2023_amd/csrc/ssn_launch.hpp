@@ -69,6 +69,13 @@ struct EnsArgs {
   const unsigned char* rowout;     // [K*dout] 1: decoded value also goes to the post stage's block row
   T* bsig;
   T* sig_w;
+  // neuron taps (Probe(member.neurons[...])): tap[4 k ...] = first neuron, count (0: ensemble k has no tap), destination signal,
+  // index among the array's taps; after the neuron step tap_sig[dst + i - first] = tap_amp * activity of neuron i.  tap_rows
+  // (fused cores, which have no hand-off operator): the block buffer - the value also goes to this timestep's row of it.
+  const int* tap;                  // nullptr: an array without taps
+  T tap_amp;
+  T* tap_sig;
+  T* tap_rows;
 };
 
 // Finish of a fused recurrent ensemble array: one thread per decoded row (k, r):
@@ -130,6 +137,10 @@ struct BlockArgs {
   unsigned int* xslots;   // [3 buffers][K][16 members][4 words], all words = the sentinel at launch (host memset)
   int* xerr;           // set to 1 by a member that waited too long for a partner (the launch then produced garbage)
   unsigned long long* slot_stats;   // [2]: (wave, round) slots stepped / silent among them (f32; one atomic pair per wave and launch)
+  // neuron taps (the tapped twin instantiation, k_ens_block<..., TAP = 1>; nullptr: the plain kernel is launched)
+  const int* tap_slot;     // [K] index of ensemble k's tap, or -1
+  const int* tap_col;      // [taps][n_pad] destination signal of every column of a tapped ensemble's row (device neuron order), or -1
+  T tap_amp;
 };
 constexpr unsigned int BLOCK_XCHG_SENTINEL = 0x7fc0deadu;      // a NaN payload no sum produces
 // neuron groups of a thread that k_ens_block steps side by side (ssn_block.hpp; the host deals neurons to (wave, round) slots

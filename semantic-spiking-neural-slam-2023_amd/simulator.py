@@ -57,7 +57,11 @@ def pack_model(model, dtype, device=0, steps_per_graph=0, block_steps=0, flags=0
     keep = []
     sig_init = np.ascontiguousarray(model.sig_init, dtype=np.float64)
     keep.append(sig_init)
-    bufs = (_lib.BufferDesc * max(1, len(model.buffers)))()
+    # neuron taps of the ensemble arrays (Probe(member.neurons[...])): ENSARRAY has no operator slot left for them - they travel
+    # as records in one more buffer, behind the model's own
+    tap_rows = [(j, k, first, count, dst, o["tap_amp"]) for j, o in enumerate(model.ops) if o["kind"] == "ensarray"
+                for k, first, count, dst in o.get("taps", ())]
+    bufs = (_lib.BufferDesc * max(1, len(model.buffers) + bool(tap_rows)))()
     for i, b in enumerate(model.buffers):
         if b.dtype.kind in "iu":
             arr = np.ascontiguousarray(b, dtype=np.int32)
@@ -159,7 +163,15 @@ def pack_model(model, dtype, device=0, steps_per_graph=0, block_steps=0, flags=0
     for j, (lo, hi) in enumerate(xr):
         r_x[j].lo, r_x[j].hi = int(lo), int(hi)
     desc.n_exchange, desc.exchange = len(xr), r_x
-    keep += [bufs, ops, probes, r_p2c, r_c2p, r_x]
+    taps = (_lib.TapDesc * max(1, len(tap_rows)))()
+    for t, (j, k, first, count, dst, amp) in zip(taps, tap_rows):
+        t.op, t.k, t.first, t.count, t.dst, t.amp = int(j), int(k), int(first), int(count), int(dst), float(amp)
+    if tap_rows:
+        tb = bufs[len(model.buffers)]
+        tb.data, tb.count, tb.kind = C.addressof(taps), len(tap_rows), _lib.SSN_BUF_TAPS
+        desc.n_buffers += 1
+    desc.n_taps = len(tap_rows)
+    keep += [bufs, ops, probes, r_p2c, r_c2p, r_x, taps]
     return desc, keep, sig_probes
 
 

@@ -288,12 +288,17 @@ def stage_ops(ops, model, r_allocs, schedule_ops, op_access, overlap, enable=Tru
     core_need = sig_ranges(lambda o: o["stage"] == CORE, (1, 2))
     post_need = sig_ranges(lambda o: o["stage"] == POST, (1, 2))
     probe_stage = []
+    tap_w = _merge_ranges([(dst, dst + count) for o in out if o["kind"] == "ensarray" for _, _, count, dst in o.get("taps", ())])
     for p in model.probes:
         if "src" not in p:
             probe_stage.append(CORE)
             continue
         rng = ("s", p["src"], p["src"] + p["width"])
         st = [o["stage"] for o, a in zip(out, acc_o) if any(overlap(x, rng) for cls in (0, 1, 3) for x in a[cls])]
+        if enable and any(lo <= p["src"] and p["src"] + p["width"] <= hi for lo, hi in tap_w):
+            # an unfiltered neuron probe of an ensemble-array member reads its tap: handed from core to post like a decoded row and
+            # sampled there, so that the array may still run a whole block per launch (a probe sampled by the core rules that out)
+            st = [POST]
         probe_stage.append(max(st) if st else POST)
     probe_need = _merge_ranges([(p["src"], p["src"] + p["width"]) for p, s in zip(model.probes, probe_stage)
                                 if "src" in p and s == POST])

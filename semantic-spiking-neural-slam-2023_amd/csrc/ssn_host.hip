@@ -171,6 +171,55 @@ struct PlanOptions {
   }
 };
 
+// A captured graph and its executable (Sim::capture_into fills it).
+struct Graph {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  Graph() = default;
+  Graph(Graph&& o) noexcept : graph(o.graph), exec(o.exec) { o.graph = nullptr; o.exec = nullptr; }
+  Graph(const Graph&) = delete;
+  Graph& operator=(const Graph&) = delete;
+  ~Graph() { reset(); }
+  void reset() {
+    if (exec) hipGraphExecDestroy(exec);
+    if (graph) hipGraphDestroy(graph);
+    exec = nullptr; graph = nullptr;
+  }
+};
+
+// Device memory with one owner: a buffer that grows at run time (table rows and indices, probe storage), or a
+// temporary.
+struct DevBuf {
+  void* p = nullptr;
+  int64_t cap = 0;                            // bytes
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) hipFree(p);
+    p = nullptr; cap = 0;
+  }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+  // a temporary of exactly `bytes` (not counted in ssn_counters.device_bytes)
+  hipError_t alloc(size_t bytes) {
+    reset();
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = (int64_t)bytes;
+    return e;
+  }
+  // at least `need_bytes`: a buffer that is too small is freed and replaced (its contents are not kept)
+  template <typename S>
+  int grow(S& sim, int64_t need_bytes) {
+    if (need_bytes <= cap) return SSN_OK;
+    reset();
+    CHK(sim.dmalloc(&p, need_bytes, false));
+    cap = need_bytes;
+    return SSN_OK;
+  }
+};
+
 }  // namespace
 
 struct ssn_sim {
@@ -241,7 +290,7 @@ struct Sim final : ssn_sim {
   std::vector<double> sig_init;
   std::vector<Buf> bufs;
   std::vector<Item> items;                   // one timestep of the core stage, unfused
-  std::vector<void*> scratch_bufs;
+  std::vector<void*> owned;                   // what ssn_create allocated (dmalloc): freed with the simulator
   // time-batched pre / post stages
   T* bsig = nullptr;                          // [block+1][n_sig]
   int block = 0;                              // timesteps per block (0: staging off)
@@ -252,7 +301,6 @@ struct Sim final : ssn_sim {
   ssn::FinishArgs<T> fin_begin, fin_flush;
   bool fused_block = false;                   // ... stepped a whole block per launch: [k_ens_block] (ssn_block.hpp)
   ssn::BlockArgs<T> blk;
-  std::vector<void*> fused_bufs;
   // neuron taps of the ensemble arrays (ssn_model_desc.taps, ABI 9): per tapped operator the table its kernels read -
   // [K][4] = first neuron, count (0: ensemble without a tap), destination signal, index among the operator's taps
   struct TapSet { std::vector<ssn_tap_desc> list; int* d_tab = nullptr; double amp = 0.0; };
@@ -285,19 +333,17 @@ struct Sim final : ssn_sim {
   struct Launch { int rl = -1; int item = -1; int phase = 0; };
   bool round_mode = false;
   std::vector<RoundLaunch> round_launches;
-  std::vector<Launch> launch_list;            // one timestep
+  std::vector<Launch> launch_list;            // one timestep (item plans: one entry per unmerged item)
   std::vector<Launch> graph_list;             // steps_per_graph timesteps, software-pipelined (empty: replay launch_list)
   // neuron-sharded models, pipelined (round 4): cycle_steps timesteps as cycle_steps + 1 launch segments; the caller's exchange of
   // timestep k sits between segments k and k + 1 (ssn_run_phase / ssn_phase_async with phase 3 = "the next segment")
   std::vector<std::vector<Launch>> cycle_segs;
   int cycle_steps = 0, next_seg = 0;
   int n_fused_populations = 0, n_serial_chains = 0;      // (counters of the round plan)
-  std::vector<hipGraph_t> cycle_graph;
-  std::vector<hipGraphExec_t> cycle_exec;
+  std::vector<Graph> cycle_graph;             // (stream-ordered stepping: one per segment)
   std::vector<Launch> phase2_list;            // neuron-sharded models: the updates of timestep s and timestep s + 1 up to its exchange,
                                               // planned as ONE set of rounds (empty: the two halves one after the other)
   int graph_rounds = 0;
-  std::vector<void*> round_bufs;
 
   ssn::StepCtx* d_ctx = nullptr;
   std::vector<ssn::TableSlot> tables;
@@ -307,23 +353,20 @@ struct Sim final : ssn_sim {
   std::vector<std::vector<int32_t>> table_idx_host;
   std::vector<std::pair<long long, long long>> table_dst;      // (signal offset, width) per table id; width 0: unknown
   ssn::TableSlot* d_tables = nullptr;
-  std::vector<void*> table_rows;
-  std::vector<int*> table_idx;
-  std::vector<int64_t> table_rows_cap, table_idx_cap;
+  std::vector<DevBuf> table_rows, table_idx;
   // staged tables (ssn_stage_table / ssn_commit_tables): the NEXT chunk's inputs arrive in a second set of buffers by DMA on the
   // copy stream while the compute stream still reads the current ones; commit swaps the sets between two runs
-  struct Staged { void* rows = nullptr; int* idx = nullptr; int64_t rows_cap = 0, idx_cap = 0; bool valid = false;
+  struct Staged { DevBuf rows, idx; bool valid = false;
                   int64_t n_rows = 0, width = 0, n_idx = 0, first_step = 0; std::vector<int32_t> idx_host; };
   std::vector<Staged> staged;
   std::mutex stage_mutex;
   std::vector<ssn_probe_desc> probes;
   std::vector<ssn::ProbeSlot> pslots;
   ssn::ProbeSlot* d_pslots = nullptr;
-  std::vector<int64_t> probe_cap_bytes;
+  std::vector<DevBuf> probe_store;            // pslots[p].data
   int64_t reserve_first = 0, reserve_n = 0;
   int steps_per_graph = 0;
-  hipGraphExec_t graph_exec = nullptr;
-  hipGraph_t graph = nullptr;
+  Graph step_graph;                           // steps_per_graph timesteps
   int64_t steps_done = 0;
   int64_t device_bytes = 0;
   // timing
@@ -338,12 +381,10 @@ struct Sim final : ssn_sim {
   std::vector<ssn_range> exchange;
   bool phased = false;
   int next_phase = 0;
-  hipGraphExec_t phase_exec[3] = {nullptr, nullptr, nullptr};      // [2]: phase 1 of a timestep followed by phase 0 of the next
-  hipGraph_t phase_graph[3] = {nullptr, nullptr, nullptr};
+  Graph phase_graph[3];                       // [2]: phase 1 of a timestep followed by phase 0 of the next
   // stream-ordered stepping (ssn_phase_async): the same halves with the exchange copies inside the graph, for one exchange
   // buffer of the caller; launched on the caller's stream, no host synchronisation per timestep
-  hipGraphExec_t async_exec[3] = {nullptr, nullptr, nullptr};
-  hipGraph_t async_graph[3] = {nullptr, nullptr, nullptr};
+  Graph async_graph[3];
   void* async_buf = nullptr;
   bool async_captured = false, async_active = false;
   hipStream_t async_stream = nullptr;         // the caller's stream a stream-ordered run is in flight on (while async_active)
@@ -359,45 +400,29 @@ struct Sim final : ssn_sim {
     hipSetDevice(device);
     if (async_active && async_stream) hipStreamSynchronize(async_stream);
     if (stream) hipStreamSynchronize(stream);
-    if (graph_exec) hipGraphExecDestroy(graph_exec);
-    if (graph) hipGraphDestroy(graph);
-    for (int h = 0; h < 3; ++h) {
-      if (phase_exec[h]) hipGraphExecDestroy(phase_exec[h]);
-      if (phase_graph[h]) hipGraphDestroy(phase_graph[h]);
-      if (async_exec[h]) hipGraphExecDestroy(async_exec[h]);
-      if (async_graph[h]) hipGraphDestroy(async_graph[h]);
-    }
-    drop_cycle_graphs();
-    for (auto& b : bufs) if (b.d) hipFree(b.d);
-    for (auto p : table_rows) if (p) hipFree(p);
-    for (auto p : table_idx) if (p) hipFree(p);
-    for (auto& g : staged) { if (g.rows) hipFree(g.rows); if (g.idx) hipFree(g.idx); }
-    for (auto& s : pslots) if (s.data) hipFree(s.data);
-    for (auto& it : items) if (it.type == IT_ENS && it.ens.partials) hipFree(it.ens.partials);
-    for (auto p : scratch_bufs) if (p) hipFree(p);
-    for (auto p : fused_bufs) if (p) hipFree(p);
-    for (auto p : round_bufs) if (p) hipFree(p);
+    // graphs, then device memory, then events; the copy stream and the staging it fills; the compute stream last
+    step_graph.reset();
+    for (int h = 0; h < 3; ++h) { phase_graph[h].reset(); async_graph[h].reset(); }
+    cycle_graph.clear();
+    table_rows.clear(); table_idx.clear(); staged.clear(); probe_store.clear();
+    for (void* p : owned) hipFree(p);
     for (auto e : ev_pool) hipEventDestroy(e);
     if (ev_run0) hipEventDestroy(ev_run0);
     if (ev_run1) hipEventDestroy(ev_run1);
-    if (sig) hipFree(sig);
-    if (bsig) hipFree(bsig);
-    if (d_mops) hipFree(d_mops);
-    if (d_progs) hipFree(d_progs);
-    if (d_ctx) hipFree(d_ctx);
-    if (d_tables) hipFree(d_tables);
-    if (d_pslots) hipFree(d_pslots);
     if (copy_stream) { hipStreamSynchronize(copy_stream); hipStreamDestroy(copy_stream); }
     if (dl_stage) hipHostFree(dl_stage);
     if (up_stage) hipFree(up_stage);
     if (stream) hipStreamDestroy(stream);
   }
 
+  // Device memory, counted in ssn_counters.device_bytes.  Owned: the simulator frees it when it is destroyed - every
+  // allocation of ssn_create, the only writer of `owned`.  Not owned (DevBuf::grow): the caller frees it.
   template <typename P>
-  int dmalloc(P** p, int64_t bytes) {
+  int dmalloc(P** p, int64_t bytes, bool own = true) {
     if (bytes <= 0) bytes = 16;
     HIPCHK(hipMalloc((void**)p, (size_t)bytes));
     device_bytes += bytes;
+    if (own) owned.push_back((void*)*p);
     return SSN_OK;
   }
 
@@ -410,7 +435,7 @@ struct Sim final : ssn_sim {
     // (weight matrices at build time, config 5's 14 GB clean-up table) take and release their own
     constexpr int64_t KEEP = (int64_t)8 << 20;                 // elements
     double* stage = nullptr;
-    bool own = false;
+    DevBuf own;
     if (n <= KEEP) {
       if (n > up_cap) {
         if (up_stage) { hipFree(up_stage); up_stage = nullptr; up_cap = 0; }
@@ -420,13 +445,12 @@ struct Sim final : ssn_sim {
       }
       stage = up_stage;
     } else {
-      HIPCHK(hipMalloc((void**)&stage, (size_t)n * sizeof(double)));
-      own = true;
+      HIPCHK(own.alloc((size_t)n * sizeof(double)));
+      stage = (double*)own.p;
     }
     hipError_t e = hipMemcpyAsync(stage, src, (size_t)n * sizeof(double), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = ssn::launch_convert_in<T>(stream, stage, dst, rows, cols, ld);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (own) hipFree(stage);
     HIPCHK(e);
     return SSN_OK;
   }
@@ -483,26 +507,26 @@ struct Sim final : ssn_sim {
       src = ordered.data();
     }
     if (b.transposed) {
-      T* tmp = nullptr;
-      HIPCHK(hipMalloc((void**)&tmp, (size_t)(b.rows * b.ld) * sizeof(T)));
+      DevBuf own;
+      HIPCHK(own.alloc((size_t)(b.rows * b.ld) * sizeof(T)));
+      T* tmp = (T*)own.p;
       int rc = upload(src, tmp, b.rows, b.cols, b.ld);
       hipError_t e = hipSuccess;
       if (rc == SSN_OK) e = hipMemsetAsync(b.d, 0, (size_t)(b.cols * b.ldt) * sizeof(T), stream);
       if (rc == SSN_OK && e == hipSuccess) e = ssn::launch_transpose<T>(stream, tmp, (T*)b.d, (int)b.rows, (int)b.cols, (int)b.ld, (int)b.ldt);
       if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      hipFree(tmp);
       CHK(rc);
       HIPCHK(e);
       return SSN_OK;
     }
     if (!b.dec_DP) return upload(src, (T*)b.d, b.rows, b.cols, b.ld);
-    T* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, (size_t)(b.rows * b.ld) * sizeof(T)));
+    DevBuf own;
+    HIPCHK(own.alloc((size_t)(b.rows * b.ld) * sizeof(T)));
+    T* tmp = (T*)own.p;
     int rc = upload(src, tmp, b.rows, b.cols, b.ld);
     hipError_t e = hipSuccess;
     if (rc == SSN_OK) e = ssn::launch_dec_pack<T>(stream, tmp, (T*)b.d, b.dec_K, b.dec_dout, b.dec_n, (int)b.ld, b.dec_DP, 0);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    hipFree(tmp);
     CHK(rc);
     HIPCHK(e);
     return SSN_OK;
@@ -525,18 +549,19 @@ struct Sim final : ssn_sim {
       return SSN_OK;
     }
     if (b.transposed) {
-      T* tmp = nullptr;
-      HIPCHK(hipMalloc((void**)&tmp, (size_t)(b.rows * b.ld) * sizeof(T)));
+      DevBuf own;
+      HIPCHK(own.alloc((size_t)(b.rows * b.ld) * sizeof(T)));
+      T* tmp = (T*)own.p;
       hipError_t e = ssn::launch_transpose<T>(stream, (const T*)b.d, tmp, (int)b.cols, (int)b.rows, (int)b.ldt, (int)b.ld);
       if (e == hipSuccess) e = hipStreamSynchronize(stream);          // (download() copies on its own stream)
       int rc = e == hipSuccess ? download(tmp, dst, b.rows, b.cols, b.ld) : SSN_OK;
-      hipFree(tmp);
       HIPCHK(e);
       return rc;
     }
     if (!b.dec_DP && !b.packed) return download((const T*)b.d, dst, b.rows, b.cols, b.ld);
-    T* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, (size_t)(b.rows * b.ld) * sizeof(T)));
+    DevBuf own;
+    HIPCHK(own.alloc((size_t)(b.rows * b.ld) * sizeof(T)));
+    T* tmp = (T*)own.p;
     hipError_t e = hipSuccess;
     if (b.dec_DP) {
       e = hipMemsetAsync(tmp, 0, (size_t)(b.rows * b.ld) * sizeof(T), stream);
@@ -548,7 +573,6 @@ struct Sim final : ssn_sim {
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);            // (download() copies on its own stream)
     int rc = e == hipSuccess ? download(tmp, dst, b.rows, b.cols, b.ld) : SSN_OK;
-    hipFree(tmp);
     HIPCHK(e);
     return rc;
   }
@@ -634,7 +658,6 @@ struct Sim final : ssn_sim {
         row[0] = (int)t.first; row[1] = (int)t.count; row[2] = (int)t.dst; row[3] = (int)q;
       }
       CHK(dmalloc(&kv.second.d_tab, K * 16));
-      fused_bufs.push_back((void*)kv.second.d_tab);
       HIPCHK(hipMemcpy(kv.second.d_tab, tab.data(), (size_t)K * 16, hipMemcpyHostToDevice));
     }
     return SSN_OK;
@@ -800,10 +823,8 @@ struct Sim final : ssn_sim {
     HIPCHK(hipMemset(d_ctx, 0, sizeof(ssn::StepCtx)));
     // tables and probes
     tables.assign(m->n_tables, ssn::TableSlot{nullptr, nullptr, 0, 0, 0, 0});
-    table_rows.assign(m->n_tables, nullptr);
-    table_idx.assign(m->n_tables, nullptr);
-    table_rows_cap.assign(m->n_tables, 0);
-    table_idx_cap.assign(m->n_tables, 0);
+    table_rows.resize((size_t)m->n_tables);
+    table_idx.resize((size_t)m->n_tables);
     staged.resize((size_t)m->n_tables);
     CHK(dmalloc(&d_tables, std::max<int64_t>(1, m->n_tables) * (int64_t)sizeof(ssn::TableSlot)));
     if (m->n_tables) HIPCHK(hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(ssn::TableSlot), hipMemcpyHostToDevice));
@@ -813,7 +834,7 @@ struct Sim final : ssn_sim {
       CHK(check_range(p.src, p.width, "probe"));
     }
     pslots.assign(m->n_probes, ssn::ProbeSlot{nullptr, 1, 0, 0});
-    probe_cap_bytes.assign(m->n_probes, 0);
+    probe_store.resize((size_t)m->n_probes);
     for (int i = 0; i < m->n_probes; ++i) pslots[i].every = probes[i].every;
     CHK(dmalloc(&d_pslots, std::max<int64_t>(1, m->n_probes) * (int64_t)sizeof(ssn::ProbeSlot)));
     if (m->n_probes) HIPCHK(hipMemcpy(d_pslots, pslots.data(), pslots.size() * sizeof(ssn::ProbeSlot), hipMemcpyHostToDevice));
@@ -821,12 +842,12 @@ struct Sim final : ssn_sim {
     phased = !exchange.empty();
     for (auto& r : exchange) CHK(check_range(r.lo, r.hi - r.lo, "exchange"));
     // time-batched stages
-    bool staged = false;
-    for (int i = 0; i < m->n_ops; ++i) staged = staged || m->ops[i].stage != 1;
-    for (auto& p : probes) staged = staged || p.stage != 1;
+    bool has_batched_stage = false;
+    for (int i = 0; i < m->n_ops; ++i) has_batched_stage = has_batched_stage || m->ops[i].stage != 1;
+    for (auto& p : probes) has_batched_stage = has_batched_stage || p.stage != 1;
     batched_mask.assign((size_t)n_sig, 0);
-    if (staged && phased) return fail(SSN_EINVAL, "a neuron-sharded model is stepped whole (build it unstaged)");
-    if (staged) {
+    if (has_batched_stage && phased) return fail(SSN_EINVAL, "a neuron-sharded model is stepped whole (build it unstaged)");
+    if (has_batched_stage) {
       // default: 1024 timesteps per block while the block buffer stays under 256 MiB, else 256
       block = m->block_steps > 0 ? m->block_steps : ((int64_t)1025 * n_sig * (int64_t)sizeof(T) <= (256ll << 20) ? 1024 : 256);
       CHK(dmalloc(&bsig, (int64_t)(block + 1) * n_sig * (int64_t)sizeof(T)));
@@ -926,7 +947,6 @@ struct Sim final : ssn_sim {
     float2* d = nullptr;
     CHK(dmalloc(&d, (int64_t)h.size() * (int64_t)sizeof(float2)));
     HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-    scratch_bufs.push_back(d);
     dft_tables.push_back({key, d});
     *out = d;
     return SSN_OK;
@@ -997,7 +1017,6 @@ struct Sim final : ssn_sim {
     CHK(dmalloc(&d2, (int64_t)g2.size() * 4));
     HIPCHK(hipMemcpy(d1, g1.data(), g1.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d2, g2.data(), g2.size() * 4, hipMemcpyHostToDevice));
-    scratch_bufs.push_back(d1); scratch_bufs.push_back(d2);
     dft_tables.push_back({key1, (float2*)d1}); dft_tables.push_back({key2, (float2*)d2});
     *g1_out = d1; *g2_out = d2;
     return SSN_OK;
@@ -1198,9 +1217,7 @@ struct Sim final : ssn_sim {
     }
     int* d_slot = nullptr; int* d_col = nullptr;
     CHK(dmalloc(&d_slot, K * 4));
-    fused_bufs.push_back((void*)d_slot);
     CHK(dmalloc(&d_col, (int64_t)col.size() * 4));
-    fused_bufs.push_back((void*)d_col);
     HIPCHK(hipMemcpy(d_slot, slot.data(), (size_t)K * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_col, col.data(), col.size() * 4, hipMemcpyHostToDevice));
     blk.tap_slot = d_slot; blk.tap_col = d_col; blk.tap_amp = (T)ts->amp;
@@ -1330,7 +1347,6 @@ struct Sim final : ssn_sim {
       if ((*rc = dmalloc(&d_ro, nr)) != SSN_OK) return true;
       if ((*rc = dmalloc(&d_xrow, (int64_t)K * din * 4)) != SSN_OK) return true;
       if ((*rc = dmalloc(&d_xalpha, (int64_t)K * din * (int64_t)sizeof(T))) != SSN_OK) return true;
-      fused_bufs.insert(fused_bufs.end(), {(void*)d_lp, (void*)d_a, (void*)d_b, (void*)d_ro, (void*)d_xrow, (void*)d_xalpha});
       hipMemcpy(d_lp, lp_state.data(), (size_t)nr * 4, hipMemcpyHostToDevice);
       hipMemcpy(d_ro, rowout.data(), (size_t)nr, hipMemcpyHostToDevice);
       hipMemcpy(d_xrow, xrow.data(), (size_t)(K * din) * 4, hipMemcpyHostToDevice);
@@ -1353,7 +1369,6 @@ struct Sim final : ssn_sim {
       {
         unsigned long long* d_ss = nullptr;
         if ((*rc = dmalloc(&d_ss, 16)) != SSN_OK) return true;
-        fused_bufs.push_back((void*)d_ss);
         hipMemset(d_ss, 0, 16);
         blk.slot_stats = d_ss;
       }
@@ -1361,7 +1376,6 @@ struct Sim final : ssn_sim {
         unsigned int* d_x = nullptr; int* d_e = nullptr;
         if ((*rc = dmalloc(&d_x, (int64_t)3 * K * 64 * 4)) != SSN_OK) return true;
         if ((*rc = dmalloc(&d_e, 16)) != SSN_OK) return true;
-        fused_bufs.insert(fused_bufs.end(), {(void*)d_x, (void*)d_e});
         hipMemset(d_e, 0, 16);
         blk.xslots = d_x; blk.xerr = d_e;
       }
@@ -1406,7 +1420,6 @@ struct Sim final : ssn_sim {
     if ((*rc = dmalloc(&d_b, nr * (int64_t)sizeof(T))) != SSN_OK) return true;
     if ((*rc = dmalloc(&d_ro, nr)) != SSN_OK) return true;
     if ((*rc = dmalloc(&d_ticket, 64)) != SSN_OK) return true;
-    fused_bufs.insert(fused_bufs.end(), {(void*)d_lp, (void*)d_a, (void*)d_b, (void*)d_ro, (void*)d_ticket});
     hipMemcpy(d_lp, lp_state.data(), (size_t)nr * 4, hipMemcpyHostToDevice);
     hipMemcpy(d_ro, rowout.data(), (size_t)nr, hipMemcpyHostToDevice);
     hipMemset(d_ticket, 0, 64);
@@ -1422,7 +1435,6 @@ struct Sim final : ssn_sim {
       if ((*rc = dmalloc(&d_xrow, (int64_t)K * din * 4)) != SSN_OK) return true;
       if ((*rc = dmalloc(&d_xalpha, (int64_t)K * din * (int64_t)sizeof(T))) != SSN_OK) return true;
       if ((*rc = dmalloc(&d_fstate, 2 * nr * (int64_t)sizeof(T))) != SSN_OK) return true;
-      fused_bufs.insert(fused_bufs.end(), {(void*)d_has, (void*)d_xrow, (void*)d_xalpha, (void*)d_fstate});
       hipMemcpy(d_has, lp_has.data(), (size_t)nr * 4, hipMemcpyHostToDevice);
       hipMemcpy(d_xrow, xrow.data(), (size_t)(K * din) * 4, hipMemcpyHostToDevice);
       hipMemset(d_fstate, 0, (size_t)(2 * nr) * sizeof(T));
@@ -1573,7 +1585,6 @@ struct Sim final : ssn_sim {
             terms[(size_t)q] = ssn::LinTerm<T>{(long long)((const int32_t*)m->buffers[o.i[3]].data)[q], (T)((const double*)m->buffers[o.i[4]].data)[q]};
           ssn::LinTerm<T>* d_terms = nullptr;
           CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, terms.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
-          scratch_bufs.push_back(d_terms);
           if (!terms.empty()) HIPCHK(hipMemcpy(d_terms, terms.data(), terms.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
           lin_terms[(const void*)d_terms] = terms;
           op.kind = ssn::M_LINCOMB; op.dst = o.i[0]; op.len = o.i[1]; op.i0 = o.i[2]; op.p0 = d_terms;
@@ -1617,7 +1628,6 @@ struct Sim final : ssn_sim {
             }
             T* partial = nullptr;
             CHK(dmalloc(&partial, (int64_t)chunks * rows_pad * (int64_t)sizeof(T)));
-            scratch_bufs.push_back(partial);
             Item it; it.type = IT_SPMV; it.Wm = (T*)w.d; it.src = sig + o.i[1]; it.dst = partial;
             it.rows = (int)o.i[2]; it.cols = (int)o.i[3]; it.ld = (int)w.ldt; it.n = chunks; it.seg = seg;
             for (auto& sl : spike_lists) if (sl.first == o.i[1]) { it.list = sl.second.first; it.count = sl.second.second; }
@@ -1678,7 +1688,6 @@ struct Sim final : ssn_sim {
             CHK(dmalloc(&it.list, (int64_t)n_seg * 256 * 4));
             CHK(dmalloc(&it.count, (int64_t)n_seg * 4 + 64));
             HIPCHK(hipMemset(it.count, 0, (size_t)n_seg * 4 + 64));
-            scratch_bufs.push_back(it.list); scratch_bufs.push_back(it.count);
             spike_lists.push_back({o.i[1], {it.list, it.count}});
             seg_spikes.push_back(o.i[1]);
           }
@@ -1727,7 +1736,6 @@ struct Sim final : ssn_sim {
           }
           T* scratch = nullptr;
           CHK(dmalloc(&scratch, o.i[2] * gsplit * (int64_t)sizeof(T)));
-          scratch_bufs.push_back(scratch);
           Item it; it.type = IT_MATVEC; it.Wm = (T*)w.d; it.src = sig + o.i[1]; it.dst = scratch;
           it.rows = (int)o.i[2]; it.cols = (int)o.i[3]; it.ld = (int)w.ld; it.set = 1;
           if (grid_route) {
@@ -1738,9 +1746,7 @@ struct Sim final : ssn_sim {
             const int na = (int)o.i[8], nn = (int)o.i[9], k2 = (int)o.i[10];
             T* X = nullptr; T* A = nullptr;
             CHK(dmalloc(&X, k2 * (int64_t)sizeof(T)));
-            scratch_bufs.push_back(X);
             CHK(dmalloc(&A, (int64_t)na * k2 * (int64_t)sizeof(T)));
-            scratch_bufs.push_back(A);
             Item sx; sx.type = IT_MATVEC; sx.Wm = (T*)fd.d; sx.src = sig + o.i[1]; sx.dst = X;
             sx.rows = k2; sx.cols = (int)o.i[3]; sx.ld = (int)fd.ld; sx.set = 1;
             items.push_back(sx);
@@ -1755,7 +1761,6 @@ struct Sim final : ssn_sim {
             const int ldt = ((int)o.i[2] + VW - 1) / VW * VW;
             T* wt = nullptr;
             CHK(dmalloc(&wt, (int64_t)o.i[3] * ldt * (int64_t)sizeof(T)));
-            scratch_bufs.push_back(wt);
             HIPCHK(ssn::launch_transpose<T>(stream, (const T*)w.d, wt, (int)o.i[2], (int)o.i[3], (int)w.ld, ldt));
             it.type = IT_MATVEC_ORDERED; it.Wm = wt; it.ld = ldt;
           }
@@ -1767,7 +1772,6 @@ struct Sim final : ssn_sim {
             const int P = (int)std::min<int64_t>(1024, (o.i[2] + 1023) / 1024);      // ~4 workgroups per CU at 10^6 rows
             T* part = nullptr;
             CHK(dmalloc(&part, P * (int64_t)(sizeof(T) + sizeof(int))));
-            scratch_bufs.push_back(part);
             Item ap; ap.type = IT_ARGMAX_PART; ap.src = scratch; ap.dst = part; ap.rows = (int)o.i[2]; ap.n = P; ap.seg = gsplit;
             items.push_back(ap);
             g.p1 = part; g.src = P;
@@ -1939,6 +1943,8 @@ struct Sim final : ssn_sim {
     if (core_empty) launches_per_step = 0;
     if (!fused) analyse_dependencies(programs, item_prog);
     if (!fused && !opt.has(SSN_PLAN_NO_ITEM_BATCH)) merge_adjacent_items();
+    for (size_t i = 0; i < items.size(); ++i)        // the timestep as a launch sequence, like the round plan's
+      if (!items[i].merged) launch_list.push_back(Launch{-1, (int)i, items[i].phase});
     if (opt.debug_plan) {
       int pj = 0;
       for (size_t i = 0; i < items.size(); ++i) {
@@ -2193,7 +2199,6 @@ struct Sim final : ssn_sim {
         const int n_small = (N.n + 15) / 16;
         CHK(dmalloc(&cnt, (int64_t)n_small * 4 + 64));
         HIPCHK(hipMemset(cnt, 0, (size_t)n_small * 4 + 64));
-        scratch_bufs.push_back(cnt);
         for (Item& sp : items) if (sp.type == IT_SPMV && sp.list == N.list) { sp.count = cnt; sp.seg_len = 16; }
         N.count = cnt;
       }
@@ -2247,7 +2252,6 @@ struct Sim final : ssn_sim {
         for (auto& t : tt) t.src += o;
         ssn::LinTerm<T>* d_terms = nullptr;
         CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, tt.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
-        scratch_bufs.push_back(d_terms);
         if (!tt.empty()) HIPCHK(hipMemcpy(d_terms, tt.data(), tt.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
         lin_terms[(const void*)d_terms] = tt;
         pc.p0 = d_terms;
@@ -2913,14 +2917,11 @@ struct Sim final : ssn_sim {
   int upload_round_tables(const RoundBuild& b) {
     T* d_arena = nullptr; ssn::GlueBlock* d_map = nullptr;
     CHK(dmalloc(&d_arena, (int64_t)b.arena.size() + 16));
-    round_bufs.push_back(d_arena);
     CHK(dmalloc(&d_map, (int64_t)(b.glue_map.size() + 1) * (int64_t)sizeof(ssn::GlueBlock)));
-    round_bufs.push_back(d_map);
     if (!b.arena.empty()) HIPCHK(hipMemcpy(d_arena, b.arena.data(), b.arena.size(), hipMemcpyHostToDevice));
     if (!b.glue_map.empty()) HIPCHK(hipMemcpy(d_map, b.glue_map.data(), b.glue_map.size() * sizeof(ssn::GlueBlock), hipMemcpyHostToDevice));
     int* d_chain = nullptr;
     CHK(dmalloc(&d_chain, (int64_t)(b.chain_tab.size() + 1) * 4));
-    round_bufs.push_back(d_chain);
     if (!b.chain_tab.empty()) HIPCHK(hipMemcpy(d_chain, b.chain_tab.data(), b.chain_tab.size() * 4, hipMemcpyHostToDevice));
     for (RoundLaunch& rl : round_launches) { rl.args.chain = d_chain; rl.args.arena = (const unsigned char*)d_arena; }
     for (const Fix& f : b.fixes) {
@@ -2957,7 +2958,7 @@ struct Sim final : ssn_sim {
 
   hipError_t launch_one(const Launch& l) {
     if (l.rl >= 0) { const RoundLaunch& rl = round_launches[(size_t)l.rl]; return ssn::launch_round<T>(stream, rl.args, rl.n_blocks, rl.lds); }
-    return launch_item(items[(size_t)l.item], nullptr, nullptr);
+    return launch_item(items[(size_t)l.item]);
   }
 
   // Adjacent items of one kind with no data hazard between them share a launch (blockIdx.y selects the item).
@@ -3287,25 +3288,19 @@ struct Sim final : ssn_sim {
   }
 
   // ---- launching --------------------------------------------------------------------------
-  hipError_t launch_item(const Item& it, hipEvent_t e0, hipEvent_t e1) {
+  hipError_t launch_item(const Item& it) {
     if (it.merged) return hipSuccess;               // its batch leader launched it
     const Item* g = &it;                            // (batch members are adjacent in `items`)
     switch (it.type) {
       case IT_PROGRAM: return ssn::launch_program<T>(stream, d_mops, d_progs + it.op_begin, 1, sig, d_ctx);
       case IT_VECOPS: return ssn::launch_vecops<T>(stream, d_mops + it.op_begin, it.op_count, it.n, sig, d_ctx);
       case IT_ENS: {
-        if (e0) { hipError_t e = hipEventRecord(e0, stream); if (e != hipSuccess) return e; }
-        hipError_t e;
         if (it.batch > 1) {
           ssn::EnsBatch<T> b{};
           for (int q = 0; q < it.batch; ++q) b.a[q] = g[q].ens;
-          e = ssn::launch_ensarray_batch<T>(stream, b, it.batch);
-        } else {
-          e = ssn::launch_ensarray<T>(stream, it.ens);
+          return ssn::launch_ensarray_batch<T>(stream, b, it.batch);
         }
-        if (e != hipSuccess) return e;
-        if (e1) return hipEventRecord(e1, stream);
-        return hipSuccess;
+        return ssn::launch_ensarray<T>(stream, it.ens);
       }
       case IT_MATVEC: {
         ssn::MatvecBatch<T> b{};
@@ -3341,26 +3336,51 @@ struct Sim final : ssn_sim {
     return hipErrorInvalidValue;
   }
 
+  hipError_t advance_clock(long long n) {
+    hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, n);
+    return hipGetLastError();
+  }
+
+  // The event pairs of one profiled ssn_run_steps: pairs [0, used) of ev_pool are recorded; level 2 also notes the
+  // plan-item type / index each pair belongs to.
+  struct Timing { int level = 0; size_t used = 0; std::vector<int> types, items; };
+
+  // One launch sequence, in order.  With `tm`, a launch runs between an event pair of its own: every launch at level 2,
+  // the dominant kernel's at level 1.
+  hipError_t launch_seq(const std::vector<Launch>& seq, Timing* tm = nullptr) {
+    for (const Launch& l : seq) {
+      const bool timed = tm && tm->used + 2 <= ev_pool.size() && (tm->level == 2 || (l.rl < 0 && items[(size_t)l.item].dominant));
+      hipError_t e = timed ? hipEventRecord(ev_pool[tm->used], stream) : hipSuccess;
+      if (e == hipSuccess) e = launch_one(l);
+      if (e == hipSuccess && timed) e = hipEventRecord(ev_pool[tm->used + 1], stream);
+      if (e != hipSuccess) return e;
+      if (!timed) continue;
+      if (tm->level == 2) {
+        tm->types.push_back(l.rl >= 0 ? (int)IT_ROUND : items[(size_t)l.item].type);
+        tm->items.push_back(l.rl >= 0 ? (int)items.size() + l.rl : l.item);
+      }
+      tm->used += 2;
+    }
+    return hipSuccess;
+  }
+
   // `count` consecutive steps; fused = tail(s)+head(s+1) in one launch
   hipError_t launch_steps(int count, bool fused) {
     if (fused_defer) {                          // one k_ensarray per timestep; the clock advances once for the group
       for (int s = 0; s < count; ++s) {
         items[0].ens.sub = s;
-        hipError_t e = launch_item(items[0], nullptr, nullptr);
+        hipError_t e = launch_item(items[0]);
         if (e != hipSuccess) return e;
       }
       items[0].ens.sub = 0;
-      hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, (long long)count);
-      return hipGetLastError();
+      return advance_clock(count);
     }
     if (round_mode) {
       if (count == steps_per_graph && !graph_list.empty()) {
-        for (const Launch& l : graph_list) { hipError_t e = launch_one(l); if (e != hipSuccess) return e; }
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, (long long)count);
-        return hipGetLastError();
+        hipError_t e = launch_seq(graph_list);
+        return e == hipSuccess ? advance_clock(count) : e;
       }
-      for (int s = 0; s < count; ++s)
-        for (const Launch& l : launch_list) { hipError_t e = launch_one(l); if (e != hipSuccess) return e; }
+      for (int s = 0; s < count; ++s) { hipError_t e = launch_seq(launch_list); if (e != hipSuccess) return e; }
       return hipSuccess;
     }
     const int n_items = (int)items.size();
@@ -3372,110 +3392,109 @@ struct Sim final : ssn_sim {
         if (fused && can_fuse && i == n_items - 1 && s + 1 < count)
           e = ssn::launch_program<T>(stream, d_mops, d_progs + tail_begin, 2, sig, d_ctx);
         else
-          e = launch_item(it, nullptr, nullptr);
+          e = launch_item(it);
         if (e != hipSuccess) return e;
       }
     }
     return hipSuccess;
   }
 
-  void drop_cycle_graphs() {
-    for (auto e : cycle_exec) if (e) hipGraphExecDestroy(e);
-    for (auto g : cycle_graph) if (g) hipGraphDestroy(g);
-    cycle_exec.clear(); cycle_graph.clear();
-  }
   // segment k of the pipelined sharded cycle (k = 0 .. cycle_steps); the clock advances behind the last one
   hipError_t launch_segment(int k) {
-    for (const Launch& l : cycle_segs[(size_t)k]) { hipError_t e = launch_one(l); if (e != hipSuccess) return e; }
-    if (k == cycle_steps) {
-      hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, (long long)cycle_steps);
-      return hipGetLastError();
-    }
-    return hipSuccess;
+    hipError_t e = launch_seq(cycle_segs[(size_t)k]);
+    return e == hipSuccess && k == cycle_steps ? advance_clock(cycle_steps) : e;
   }
 
   hipError_t launch_phase(int phase) {
     if (phase == 2) {          // updates of timestep s + timestep s + 1 up to its exchange
       if (round_mode && !phase2_list.empty()) {
-        for (const Launch& l : phase2_list) { hipError_t e = launch_one(l); if (e != hipSuccess) return e; }
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, 1LL);
-        return hipGetLastError();
+        hipError_t e = launch_seq(phase2_list);
+        return e == hipSuccess ? advance_clock(1) : e;
       }
       hipError_t e = launch_phase(1);
       return e == hipSuccess ? launch_phase(0) : e;
     }
-    if (round_mode) {
-      for (const Launch& l : launch_list) {
-        if (l.phase != phase) continue;
-        hipError_t e = launch_one(l);
-        if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
-    }
-    for (const Item& it : items) {
-      if (it.phase != phase) continue;
-      hipError_t e = launch_item(it, nullptr, nullptr);
+    for (const Launch& l : launch_list) {
+      if (l.phase != phase) continue;
+      hipError_t e = launch_one(l);
       if (e != hipSuccess) return e;
     }
     return hipSuccess;
   }
 
+  // What `body` launches on the compute stream becomes the graph `g` (which replaces the one it held).
+  template <typename F>
+  int capture_into(Graph& g, F body) {
+    g.reset();
+    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+    const hipError_t e = body();
+    const hipError_t e2 = hipStreamEndCapture(stream, &g.graph);        // (always: the stream must leave capture mode)
+    HIPCHK(e);
+    HIPCHK(e2);
+    HIPCHK(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+    return SSN_OK;
+  }
+
   int capture() {
     if (phased) {             // one graph per half of the timestep
       if (fused_core || core_empty) return fail(SSN_EUNSUPPORTED, "neuron-sharded models run on the generic per-timestep plan");
-      for (int h = 0; h < 3; ++h) {        // [2]: phase 1 of a timestep + phase 0 of the next one in one launch
-        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        hipError_t e = launch_phase(h);
-        hipError_t e2 = hipStreamEndCapture(stream, &phase_graph[h]);
-        HIPCHK(e);
-        HIPCHK(e2);
-        HIPCHK(hipGraphInstantiate(&phase_exec[h], phase_graph[h], nullptr, nullptr, 0));
-      }
+      for (int h = 0; h < 3; ++h)          // [2]: phase 1 of a timestep + phase 0 of the next one in one launch
+        CHK(capture_into(phase_graph[h], [&] { return launch_phase(h); }));
       return SSN_OK;
     }
     if (steps_per_graph <= 1 || fused_block) return SSN_OK;
-    HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    hipError_t e = launch_steps(steps_per_graph, true);
-    hipError_t e2 = hipStreamEndCapture(stream, &graph);
-    HIPCHK(e);
-    HIPCHK(e2);
-    HIPCHK(hipGraphInstantiate(&graph_exec, graph, nullptr, nullptr, 0));
+    return capture_into(step_graph, [&] { return launch_steps(steps_per_graph, true); });
+  }
+
+  // The StepCtx the kernels kept against the host's count of timesteps; `before`: the call that reserves probe storage precedes.
+  int check_device_state(const char* before) {
+    ssn::StepCtx ctx;
+    HIPCHK(hipMemcpy(&ctx, d_ctx, sizeof ctx, hipMemcpyDeviceToHost));
+    if (ctx.step != steps_done) return fail(SSN_EHIP, "device step counter %lld != host %lld", (long long)ctx.step, (long long)steps_done);
+    if (ctx.probe_overflow) return fail(SSN_EINVAL, "probe storage overflow: call ssn_reserve_probes before %s", before);
     return SSN_OK;
+  }
+
+  // Is `phase` (0 .. 3) what the entry point `fn` (ssn_run_phase, ssn_phase_async) may run next?
+  int check_phase_order(const char* fn, int phase) {
+    if (phase == 3) {
+      if (!cycle_steps || !round_mode) return fail(SSN_EINVAL, "%s(3): this model has no pipelined cycle plan (ssn_cycle_steps() == 0)", fn);
+      if (next_seg == 0 && next_phase != 0) return fail(SSN_EINVAL, "%s(3): a cycle starts at a timestep boundary (phase %d is due)", fn, next_phase);
+      return SSN_OK;
+    }
+    if (next_seg != 0) return fail(SSN_EINVAL, "%s(%d): a pipelined cycle is under way (segment %d of %d is due)", fn, phase, next_seg, cycle_steps + 1);
+    if ((phase == 2 ? 1 : phase) != next_phase) return fail(SSN_EINVAL, "%s(%d): phase %d is due", fn, phase, next_phase);
+    return SSN_OK;
+  }
+
+  void advance_phase(int phase) {
+    next_phase = phase == 0 ? 1 : (phase == 1 ? 0 : 1);
+    if (phase >= 1) steps_done += 1;
+  }
+
+  // behind a segment of the pipelined cycle: true when it was the cycle's last one
+  bool advance_segment() {
+    if (++next_seg <= cycle_steps) return false;
+    next_seg = 0;
+    steps_done += cycle_steps;
+    return true;
   }
 
   int run_phase(int phase) override {
     HIPCHK(hipSetDevice(device));
     if (!phased) return fail(SSN_EINVAL, "ssn_run_phase: the model has no exchange ranges (use ssn_run_steps)");
+    if (next_seg == 0 && (phase < 0 || phase > 3)) return fail(SSN_EINVAL, "ssn_run_phase(%d): 0, 1 or 2 (= 1 followed by the next timestep's 0)", phase);
+    CHK(check_phase_order("ssn_run_phase", phase));
     if (phase == 3) {            // the next segment of a pipelined cycle (eager launches; the caller exchanges between two segments)
-      if (!cycle_steps || !round_mode) return fail(SSN_EINVAL, "ssn_run_phase(3): this model has no pipelined cycle plan (ssn_cycle_steps() == 0)");
-      if (next_seg == 0 && next_phase != 0) return fail(SSN_EINVAL, "ssn_run_phase(3): a cycle starts at a timestep boundary (phase %d is due)", next_phase);
       HIPCHK(launch_segment(next_seg));
       HIPCHK(hipStreamSynchronize(stream));
-      if (++next_seg > cycle_steps) {
-        next_seg = 0;
-        steps_done += cycle_steps;
-        ssn::StepCtx ctx;
-        HIPCHK(hipMemcpy(&ctx, d_ctx, sizeof ctx, hipMemcpyDeviceToHost));
-        if (ctx.step != steps_done) return fail(SSN_EHIP, "device step counter %lld != host %lld", (long long)ctx.step, (long long)steps_done);
-        if (ctx.probe_overflow) return fail(SSN_EINVAL, "probe storage overflow: call ssn_reserve_probes before stepping");
-      }
-      return SSN_OK;
+      return advance_segment() ? check_device_state("stepping") : SSN_OK;
     }
-    if (next_seg != 0) return fail(SSN_EINVAL, "ssn_run_phase(%d): a pipelined cycle is under way (segment %d of %d is due)", phase, next_seg, cycle_steps + 1);
-    if (phase < 0 || phase > 2) return fail(SSN_EINVAL, "ssn_run_phase(%d): 0, 1 or 2 (= 1 followed by the next timestep's 0)", phase);
-    if ((phase == 2 ? 1 : phase) != next_phase) return fail(SSN_EINVAL, "ssn_run_phase(%d): phase %d is due", phase, next_phase);
-    HIPCHK(hipGraphLaunch(phase_exec[phase], stream));
+    HIPCHK(hipGraphLaunch(phase_graph[phase].exec, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    next_phase = phase == 0 ? 1 : (phase == 1 ? 0 : 1);
-    if (phase >= 1) {
-      steps_done += 1;
-      if (steps_done % 64 == 0 || steps_done == reserve_first + reserve_n) {      // (a device -> host round trip: not on every timestep)
-        ssn::StepCtx ctx;
-        HIPCHK(hipMemcpy(&ctx, d_ctx, sizeof ctx, hipMemcpyDeviceToHost));
-        if (ctx.step != steps_done) return fail(SSN_EHIP, "device step counter %lld != host %lld", (long long)ctx.step, (long long)steps_done);
-        if (ctx.probe_overflow) return fail(SSN_EINVAL, "probe storage overflow: call ssn_reserve_probes before stepping");
-      }
-    }
+    advance_phase(phase);
+    if (phase >= 1 && (steps_done % 64 == 0 || steps_done == reserve_first + reserve_n))      // (a device -> host round trip: not on every timestep)
+      return check_device_state("stepping");
     return SSN_OK;
   }
 
@@ -3488,19 +3507,6 @@ struct Sim final : ssn_sim {
   }
 
   // signal ranges of the exchange <-> one contiguous device buffer (a handful of ranges: one device copy each)
-  int exchange_copy(void* buf, bool pack) override {
-    HIPCHK(hipSetDevice(device));
-    T* b = (T*)buf;
-    for (auto& r : exchange) {
-      const size_t bytes = (size_t)(r.hi - r.lo) * sizeof(T);
-      if (pack) HIPCHK(hipMemcpyAsync(b, sig + r.lo, bytes, hipMemcpyDeviceToDevice, stream));
-      else HIPCHK(hipMemcpyAsync(sig + r.lo, b, bytes, hipMemcpyDeviceToDevice, stream));
-      b += r.hi - r.lo;
-    }
-    HIPCHK(hipStreamSynchronize(stream));
-    return SSN_OK;
-  }
-
   hipError_t exchange_copy_async(void* buf, bool pack, hipStream_t st) {
     T* b = (T*)buf;
     for (auto& r : exchange) {
@@ -3513,38 +3519,28 @@ struct Sim final : ssn_sim {
     return hipSuccess;
   }
 
-  // (Re)capture the three phase graphs with the exchange copies of `buf` inside: [unpack] -> kernels -> [pack].
+  int exchange_copy(void* buf, bool pack) override {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(exchange_copy_async(buf, pack, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return SSN_OK;
+  }
+
+  // (Re)capture the graphs of stream-ordered stepping with the exchange copies of `buf` inside: [unpack] -> kernels -> [pack].
   int capture_async(void* buf) {
-    for (int h = 0; h < 3; ++h) {
-      if (async_exec[h]) { hipGraphExecDestroy(async_exec[h]); async_exec[h] = nullptr; }
-      if (async_graph[h]) { hipGraphDestroy(async_graph[h]); async_graph[h] = nullptr; }
-    }
-    for (int h = 0; h < 3; ++h) {
-      HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      hipError_t e = hipSuccess;
-      if (h >= 1 && buf) e = exchange_copy_async(buf, false, stream);
-      if (e == hipSuccess) e = launch_phase(h);
-      if (h != 1 && buf && e == hipSuccess) e = exchange_copy_async(buf, true, stream);
-      hipError_t e2 = hipStreamEndCapture(stream, &async_graph[h]);
-      HIPCHK(e);
-      HIPCHK(e2);
-      HIPCHK(hipGraphInstantiate(&async_exec[h], async_graph[h], nullptr, nullptr, 0));
-    }
-    drop_cycle_graphs();
+    auto with_exchange = [&](bool unpack, bool pack, auto launch) {
+      hipError_t e = unpack && buf ? exchange_copy_async(buf, false, stream) : hipSuccess;
+      if (e == hipSuccess) e = launch();
+      if (e == hipSuccess && pack && buf) e = exchange_copy_async(buf, true, stream);
+      return e;
+    };
+    for (int h = 0; h < 3; ++h)
+      CHK(capture_into(async_graph[h], [&] { return with_exchange(h >= 1, h != 1, [&] { return launch_phase(h); }); }));
+    cycle_graph.clear();
     if (cycle_steps && round_mode) {          // segment k: [unpack the sums of timestep k - 1] -> rounds -> [pack the partial sums of timestep k]
-      cycle_graph.assign((size_t)cycle_steps + 1, nullptr);
-      cycle_exec.assign((size_t)cycle_steps + 1, nullptr);
-      for (int k = 0; k <= cycle_steps; ++k) {
-        HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        hipError_t e = hipSuccess;
-        if (k >= 1 && buf) e = exchange_copy_async(buf, false, stream);
-        if (e == hipSuccess) e = launch_segment(k);
-        if (k < cycle_steps && buf && e == hipSuccess) e = exchange_copy_async(buf, true, stream);
-        hipError_t e2 = hipStreamEndCapture(stream, &cycle_graph[(size_t)k]);
-        HIPCHK(e);
-        HIPCHK(e2);
-        HIPCHK(hipGraphInstantiate(&cycle_exec[(size_t)k], cycle_graph[(size_t)k], nullptr, nullptr, 0));
-      }
+      cycle_graph.resize((size_t)cycle_steps + 1);
+      for (int k = 0; k <= cycle_steps; ++k)
+        CHK(capture_into(cycle_graph[(size_t)k], [&] { return with_exchange(k >= 1, k < cycle_steps, [&] { return launch_segment(k); }); }));
     }
     async_buf = buf;
     async_captured = true;
@@ -3560,14 +3556,8 @@ struct Sim final : ssn_sim {
       if (!async_captured || buf != async_buf) CHK(capture_async(buf));
       return SSN_OK;
     }
-    if (phase == 3) {
-      if (!cycle_steps || !round_mode) return fail(SSN_EINVAL, "ssn_phase_async(3): this model has no pipelined cycle plan (ssn_cycle_steps() == 0)");
-      if (next_seg == 0 && next_phase != 0) return fail(SSN_EINVAL, "ssn_phase_async(3): a cycle starts at a timestep boundary (phase %d is due)", next_phase);
-    } else {
-      if (next_seg != 0) return fail(SSN_EINVAL, "ssn_phase_async(%d): a pipelined cycle is under way (segment %d of %d is due)", phase, next_seg, cycle_steps + 1);
-      if (phase < 0 || phase > 2) return fail(SSN_EINVAL, "ssn_phase_async(%d): 0, 1, 2 (= 1 followed by the next timestep's 0) or 3 (next segment of a pipelined cycle)", phase);
-      if ((phase == 2 ? 1 : phase) != next_phase) return fail(SSN_EINVAL, "ssn_phase_async(%d): phase %d is due", phase, next_phase);
-    }
+    if (next_seg == 0 && (phase < 0 || phase > 3)) return fail(SSN_EINVAL, "ssn_phase_async(%d): 0, 1, 2 (= 1 followed by the next timestep's 0) or 3 (next segment of a pipelined cycle)", phase);
+    CHK(check_phase_order("ssn_phase_async", phase));
     if (!async_active) {
       HIPCHK(hipStreamSynchronize(stream));          // uploads / table updates issued on the simulator's own stream come first
       if (!async_captured || buf != async_buf) CHK(capture_async(buf));
@@ -3577,13 +3567,12 @@ struct Sim final : ssn_sim {
     }
     async_stream = ext ? ext : stream;
     if (phase == 3) {
-      HIPCHK(hipGraphLaunch(cycle_exec[(size_t)next_seg], ext ? ext : stream));
-      if (++next_seg > cycle_steps) { next_seg = 0; steps_done += cycle_steps; }
+      HIPCHK(hipGraphLaunch(cycle_graph[(size_t)next_seg].exec, async_stream));
+      advance_segment();
       return SSN_OK;
     }
-    HIPCHK(hipGraphLaunch(async_exec[phase], ext ? ext : stream));
-    next_phase = phase == 0 ? 1 : (phase == 1 ? 0 : 1);
-    if (phase >= 1) steps_done += 1;
+    HIPCHK(hipGraphLaunch(async_graph[phase].exec, async_stream));
+    advance_phase(phase);
     return SSN_OK;
   }
 
@@ -3593,11 +3582,37 @@ struct Sim final : ssn_sim {
     HIPCHK(hipStreamSynchronize(ext ? ext : stream));
     async_active = false;
     if (next_seg != 0) { const int due = next_seg; next_seg = 0; return fail(SSN_EINVAL, "ssn_phase_sync inside a pipelined cycle (segment %d of %d was due): the simulator's state is part-way through %d timesteps - reset it", due, cycle_steps + 1, cycle_steps); }
-    ssn::StepCtx ctx;
-    HIPCHK(hipMemcpy(&ctx, d_ctx, sizeof ctx, hipMemcpyDeviceToHost));
-    if (ctx.step != steps_done) return fail(SSN_EHIP, "device step counter %lld != host %lld", (long long)ctx.step, (long long)steps_done);
-    if (ctx.probe_overflow) return fail(SSN_EINVAL, "probe storage overflow: call ssn_reserve_probes before stepping");
-    return SSN_OK;
+    return check_device_state("stepping");
+  }
+
+  // SSN_DEBUG_PLAN after a profile = 2 run: what every plan item / round launch took
+  void print_profile() const {
+    // diagnostic build (F32_EXTRA=-DSSN_PROGRAM_STAMPS): shader cycles each operator of each program took in the last timestep
+    typedef int (*stamp_fn)(unsigned long long*, int);
+    if (stamp_fn fn = (stamp_fn)dlsym(RTLD_DEFAULT, "ssn_debug_program_stamps")) {
+      std::vector<unsigned long long> st(2048, 0);
+      if (fn(st.data(), 2048) == 0)
+        for (size_t p = 0; p < prog_descs.size(); ++p) {
+          const ssn::ProgDesc& pd = prog_descs[p];
+          if (pd.op_begin + pd.op_count > 1024) continue;
+          unsigned long long prev = st[(size_t)(1024 + pd.op_begin)];
+          fprintf(stderr, "[ssn] program %zu (%d ops) cycles per operator [kind/len:cycles]:", p, pd.op_count);
+          for (int o = 0; o < pd.op_count; ++o) {
+            const unsigned long long t = st[(size_t)(pd.op_begin + o)];
+            if (!t) { fprintf(stderr, " %d/%lld:-", mops[(size_t)(pd.op_begin + o)].kind, (long long)mops[(size_t)(pd.op_begin + o)].len); continue; }
+            fprintf(stderr, " %d/%lld:%lld", mops[(size_t)(pd.op_begin + o)].kind, (long long)mops[(size_t)(pd.op_begin + o)].len, (long long)(t - prev));
+            prev = t;
+          }
+          fprintf(stderr, "\n");
+        }
+    }
+    for (size_t i = 0; i < item_ms.size(); ++i)
+      if (item_n[i]) {
+        if (i < items.size()) fprintf(stderr, "[ssn] item %2zu type %2d batch %d: %8.2f us avg over %lld launches\n", i, items[i].type, items[i].batch,
+                                      1e3 * item_ms[i] / item_n[i], (long long)item_n[i]);
+        else fprintf(stderr, "[ssn] round launch %2zu (round %d, %d blocks): %8.2f us avg over %lld launches\n", i - items.size(),
+                     round_launches[i - items.size()].round, round_launches[i - items.size()].n_blocks, 1e3 * item_ms[i] / item_n[i], (long long)item_n[i]);
+      }
   }
 
   int run_steps(int64_t n, int profile) override {
@@ -3607,12 +3622,14 @@ struct Sim final : ssn_sim {
     if (n == 0) return SSN_OK;
     int n_dom = 0;
     for (auto& it : items) n_dom += it.dominant ? 1 : 0;
-    size_t ev_used = 0;
-    std::vector<int> ev_types, ev_items;        // profile = 2: plan-item type / index of each event pair
     if (profile == 2 && (fused_block || core_empty)) profile = 1;
+    Timing tm;
+    tm.level = profile;
     if (profile) {
-      const size_t need = fused_block ? (size_t)(2 * (n / std::max(1, block) + 2))
-                                      : (size_t)(2 * n * (profile == 2 ? (int)(items.size() + launch_list.size()) : std::max(1, n_dom)));
+      // (launch_seq times at most launch_list.size() launches per timestep, or graph_list.size() per group; the budget stays
+      //  what it was when item plans had no launch_list: all items, plus the round plan's launches)
+      const size_t per_step = profile == 2 ? items.size() + (round_mode ? launch_list.size() : 0) : (size_t)std::max(1, n_dom);
+      const size_t need = fused_block ? (size_t)(2 * (n / std::max(1, block) + 2)) : (size_t)(2 * n * (int)per_step);
       if (need > 400000) return fail(SSN_EINVAL, "profile run too long (%lld steps): at most 200000 timed launches", (long long)n);
       while (ev_pool.size() < need) {
         hipEvent_t ev;
@@ -3633,75 +3650,34 @@ struct Sim final : ssn_sim {
       }
       if (fused_defer) HIPCHK(ssn::launch_ens_finish<T>(stream, fin_begin));
       if (fused_block) {
-        const bool timed = profile && B == block && ev_used + 2 <= ev_pool.size();
+        const bool timed = profile && B == block && tm.used + 2 <= ev_pool.size();
         blk.B = (int)B;
         if (blk.P > 1)      // every exchange word back to the sentinel: the kernel boundary is the members' only common barrier
           HIPCHK(hipMemsetD32Async((hipDeviceptr_t)blk.xslots, (int)ssn::BLOCK_XCHG_SENTINEL, (size_t)3 * blk.K * 64, stream));
-        if (timed) HIPCHK(hipEventRecord(ev_pool[ev_used], stream));
+        if (timed) HIPCHK(hipEventRecord(ev_pool[tm.used], stream));
         HIPCHK(ssn::launch_ens_block<T>(stream, blk));
-        if (timed) { HIPCHK(hipEventRecord(ev_pool[ev_used + 1], stream)); ev_used += 2; }
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, (long long)B);
-        HIPCHK(hipGetLastError());
+        if (timed) { HIPCHK(hipEventRecord(ev_pool[tm.used + 1], stream)); tm.used += 2; }
+        HIPCHK(advance_clock(B));
       } else if (core_empty) {
         // nothing is stepped one timestep at a time (purely feed-forward model): just advance the clock
-        hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, (long long)B);
-        HIPCHK(hipGetLastError());
-      } else if (profile == 2) {
-        // every launch of every timestep between its own event pair (plain eager launches, no graph)
-        int64_t s_piped = 0;
-        for (; round_mode && !graph_list.empty() && s_piped + steps_per_graph <= B; s_piped += steps_per_graph) {
-          // the pipelined sequence a step graph replays, launch by launch
-          for (const Launch& l : graph_list) {
-            HIPCHK(hipEventRecord(ev_pool[ev_used], stream));
-            HIPCHK(launch_one(l));
-            HIPCHK(hipEventRecord(ev_pool[ev_used + 1], stream));
-            ev_types.push_back(l.rl >= 0 ? (int)IT_ROUND : items[(size_t)l.item].type);
-            ev_items.push_back(l.rl >= 0 ? (int)items.size() + l.rl : l.item);
-            ev_used += 2;
-          }
-          hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, (long long)steps_per_graph);
-          HIPCHK(hipGetLastError());
-        }
-        for (int64_t s = s_piped; s < B && round_mode; ++s)
-          for (const Launch& l : launch_list) {
-            if (l.rl < 0 && items[(size_t)l.item].merged) continue;
-            HIPCHK(hipEventRecord(ev_pool[ev_used], stream));
-            HIPCHK(launch_one(l));
-            HIPCHK(hipEventRecord(ev_pool[ev_used + 1], stream));
-            ev_types.push_back(l.rl >= 0 ? (int)IT_ROUND : items[(size_t)l.item].type);
-            ev_items.push_back(l.rl >= 0 ? (int)items.size() + l.rl : l.item);
-            ev_used += 2;
-          }
-        for (int64_t s = 0; s < B && !round_mode; ++s) {
-          for (auto& it : items) {
-            if (it.merged) continue;
-            HIPCHK(hipEventRecord(ev_pool[ev_used], stream));
-            HIPCHK(launch_item(it, nullptr, nullptr));
-            HIPCHK(hipEventRecord(ev_pool[ev_used + 1], stream));
-            ev_types.push_back(it.type);
-            ev_items.push_back((int)(&it - items.data()));
-            ev_used += 2;
-          }
-          if (fused_defer) { hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, 1LL); HIPCHK(hipGetLastError()); }
-        }
-      } else if (profile && round_mode) {
-        for (int64_t s = 0; s < B; ++s)
-          for (const Launch& l : launch_list) {
-            if (l.rl < 0 && items[(size_t)l.item].dominant) { HIPCHK(launch_item(items[(size_t)l.item], ev_pool[ev_used], ev_pool[ev_used + 1])); ev_used += 2; }
-            else HIPCHK(launch_one(l));
-          }
+        HIPCHK(advance_clock(B));
       } else if (profile) {
-        for (int64_t s = 0; s < B; ++s) {
-          for (auto& it : items) {
-            if (it.dominant) { HIPCHK(launch_item(it, ev_pool[ev_used], ev_pool[ev_used + 1])); ev_used += 2; }
-            else HIPCHK(launch_item(it, nullptr, nullptr));
+        // timed launches (2: every launch between its own event pair, 1: the dominant kernel's) - plain eager launches, no
+        // graph and no fused programs
+        int64_t s = 0;
+        if (profile == 2 && round_mode && !graph_list.empty())
+          for (; s + steps_per_graph <= B; s += steps_per_graph) {      // the pipelined sequence a step graph replays, launch by launch
+            HIPCHK(launch_seq(graph_list, &tm));
+            HIPCHK(advance_clock(steps_per_graph));
           }
-          if (fused_defer) { hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, stream, d_ctx, 1LL); HIPCHK(hipGetLastError()); }
+        for (; s < B; ++s) {
+          HIPCHK(launch_seq(launch_list, &tm));
+          if (fused_defer) HIPCHK(advance_clock(1));
         }
       } else {
         int64_t left = B;
-        if (graph_exec)
-          for (; left >= steps_per_graph; left -= steps_per_graph) HIPCHK(hipGraphLaunch(graph_exec, stream));
+        if (step_graph.exec)
+          for (; left >= steps_per_graph; left -= steps_per_graph) HIPCHK(hipGraphLaunch(step_graph.exec, stream));
         if (left > 0) HIPCHK(launch_steps((int)left, true));
       }
       if (fused_defer) HIPCHK(ssn::launch_ens_finish<T>(stream, fin_flush));
@@ -3713,57 +3689,26 @@ struct Sim final : ssn_sim {
     }
     HIPCHK(hipEventRecord(ev_run1, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    for (size_t j = 0; j < ev_used; j += 2) {
+    for (size_t j = 0; j < tm.used; j += 2) {
       float ms = 0.f;
       HIPCHK(hipEventElapsedTime(&ms, ev_pool[j], ev_pool[j + 1]));
       if (profile == 2) {
-        const int ty = ev_types[j / 2];
+        const int ty = tm.types[j / 2];
         type_ms[ty] += ms;
         type_launches[ty] += 1;
         if (item_ms.size() != items.size() + round_launches.size()) { item_ms.assign(items.size() + round_launches.size(), 0.0); item_n.assign(items.size() + round_launches.size(), 0); }
-        item_ms[(size_t)ev_items[j / 2]] += ms; item_n[(size_t)ev_items[j / 2]] += 1;
+        item_ms[(size_t)tm.items[j / 2]] += ms; item_n[(size_t)tm.items[j / 2]] += 1;
         continue;
       }
       dom_ms += ms;
       dom_launches += 1;
     }
-    if (profile == 2 && opt.debug_plan) {
-      // diagnostic build (F32_EXTRA=-DSSN_PROGRAM_STAMPS): shader cycles each operator of each program took in the last timestep
-      typedef int (*stamp_fn)(unsigned long long*, int);
-      if (stamp_fn fn = (stamp_fn)dlsym(RTLD_DEFAULT, "ssn_debug_program_stamps")) {
-        std::vector<unsigned long long> st(2048, 0);
-        if (fn(st.data(), 2048) == 0)
-          for (size_t p = 0; p < prog_descs.size(); ++p) {
-            const ssn::ProgDesc& pd = prog_descs[p];
-            if (pd.op_begin + pd.op_count > 1024) continue;
-            unsigned long long prev = st[(size_t)(1024 + pd.op_begin)];
-            fprintf(stderr, "[ssn] program %zu (%d ops) cycles per operator [kind/len:cycles]:", p, pd.op_count);
-            for (int o = 0; o < pd.op_count; ++o) {
-              const unsigned long long t = st[(size_t)(pd.op_begin + o)];
-              if (!t) { fprintf(stderr, " %d/%lld:-", mops[(size_t)(pd.op_begin + o)].kind, (long long)mops[(size_t)(pd.op_begin + o)].len); continue; }
-              fprintf(stderr, " %d/%lld:%lld", mops[(size_t)(pd.op_begin + o)].kind, (long long)mops[(size_t)(pd.op_begin + o)].len, (long long)(t - prev));
-              prev = t;
-            }
-            fprintf(stderr, "\n");
-          }
-      }
-    }
-    if (profile == 2 && opt.debug_plan)
-      for (size_t i = 0; i < item_ms.size(); ++i)
-        if (item_n[i]) {
-          if (i < items.size()) fprintf(stderr, "[ssn] item %2zu type %2d batch %d: %8.2f us avg over %lld launches\n", i, items[i].type, items[i].batch,
-                                        1e3 * item_ms[i] / item_n[i], (long long)item_n[i]);
-          else fprintf(stderr, "[ssn] round launch %2zu (round %d, %d blocks): %8.2f us avg over %lld launches\n", i - items.size(),
-                       round_launches[i - items.size()].round, round_launches[i - items.size()].n_blocks, 1e3 * item_ms[i] / item_n[i], (long long)item_n[i]);
-        }
+    if (profile == 2 && opt.debug_plan) print_profile();
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, ev_run0, ev_run1));
     last_run_ms = ms;
     steps_done += n;
-    ssn::StepCtx ctx;
-    HIPCHK(hipMemcpy(&ctx, d_ctx, sizeof ctx, hipMemcpyDeviceToHost));
-    if (ctx.step != steps_done) return fail(SSN_EHIP, "device step counter %lld != host %lld", (long long)ctx.step, (long long)steps_done);
-    if (ctx.probe_overflow) return fail(SSN_EINVAL, "probe storage overflow: call ssn_reserve_probes before ssn_run_steps");
+    CHK(check_device_state("ssn_run_steps"));
     if (fused_block && blk.P > 1) {
       int xe = 0;
       HIPCHK(hipMemcpy(&xe, blk.xerr, sizeof xe, hipMemcpyDeviceToHost));
@@ -3808,24 +3753,14 @@ struct Sim final : ssn_sim {
       if (idx[i] >= n_rows) return fail(SSN_EINVAL, "table row index %d >= n_rows %lld", idx[i], (long long)n_rows);
     HIPCHK(hipStreamSynchronize(stream));
     const int64_t need = std::max<int64_t>(1, n_rows * width);
-    if (need > table_rows_cap[id]) {
-      if (table_rows[id]) hipFree(table_rows[id]);
-      table_rows[id] = nullptr;
-      CHK(dmalloc((T**)&table_rows[id], need * (int64_t)sizeof(T)));
-      table_rows_cap[id] = need;
-    }
-    if (n_idx > table_idx_cap[id]) {
-      if (table_idx[id]) hipFree(table_idx[id]);
-      table_idx[id] = nullptr;
-      CHK(dmalloc(&table_idx[id], n_idx * 4));
-      table_idx_cap[id] = n_idx;
-    }
-    if (rows_dev) HIPCHK(hipMemcpy(table_rows[id], rows_dev, (size_t)(n_rows * width) * sizeof(T), hipMemcpyDeviceToDevice));
-    else if (n_rows) CHK(upload(rows, (T*)table_rows[id], n_rows, width, width));
-    if (n_idx) HIPCHK(hipMemcpy(table_idx[id], idx, (size_t)n_idx * 4, hipMemcpyHostToDevice));
+    CHK(table_rows[id].grow(*this, need * (int64_t)sizeof(T)));
+    CHK(table_idx[id].grow(*this, n_idx * 4));
+    if (rows_dev) HIPCHK(hipMemcpy(table_rows[id].p, rows_dev, (size_t)(n_rows * width) * sizeof(T), hipMemcpyDeviceToDevice));
+    else if (n_rows) CHK(upload(rows, (T*)table_rows[id].p, n_rows, width, width));
+    if (n_idx) HIPCHK(hipMemcpy(table_idx[id].p, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice));
     if (table_idx_host.size() < tables.size()) table_idx_host.resize(tables.size());
     table_idx_host[(size_t)id].assign(idx, idx + n_idx);
-    tables[id] = ssn::TableSlot{table_rows[id], table_idx[id], n_rows, width, n_idx, first_step};
+    tables[id] = ssn::TableSlot{table_rows[id].p, (int*)table_idx[id].p, n_rows, width, n_idx, first_step};
     HIPCHK(hipMemcpy(d_tables + id, &tables[id], sizeof(ssn::TableSlot), hipMemcpyHostToDevice));
     return SSN_OK;
   }
@@ -3844,20 +3779,10 @@ struct Sim final : ssn_sim {
     Staged& g = staged[(size_t)id];
     g.valid = false;
     const int64_t need = std::max<int64_t>(1, n_rows * width);
-    if (need > g.rows_cap) {
-      if (g.rows) hipFree(g.rows);
-      g.rows = nullptr;
-      CHK(dmalloc((T**)&g.rows, need * (int64_t)sizeof(T)));
-      g.rows_cap = need;
-    }
-    if (n_idx > g.idx_cap) {
-      if (g.idx) hipFree(g.idx);
-      g.idx = nullptr;
-      CHK(dmalloc(&g.idx, n_idx * 4));
-      g.idx_cap = n_idx;
-    }
-    if (n_rows) HIPCHK(hipMemcpyAsync(g.rows, rows_t, (size_t)(n_rows * width) * sizeof(T), hipMemcpyHostToDevice, copy_stream));
-    if (n_idx) HIPCHK(hipMemcpyAsync(g.idx, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice, copy_stream));
+    CHK(g.rows.grow(*this, need * (int64_t)sizeof(T)));
+    CHK(g.idx.grow(*this, n_idx * 4));
+    if (n_rows) HIPCHK(hipMemcpyAsync(g.rows.p, rows_t, (size_t)(n_rows * width) * sizeof(T), hipMemcpyHostToDevice, copy_stream));
+    if (n_idx) HIPCHK(hipMemcpyAsync(g.idx.p, idx, (size_t)n_idx * 4, hipMemcpyHostToDevice, copy_stream));
     HIPCHK(hipStreamSynchronize(copy_stream));          // (the host arrays are the caller's again)
     g.n_rows = n_rows; g.width = width; g.n_idx = n_idx; g.first_step = first_step;
     g.idx_host.assign(idx, idx + n_idx);
@@ -3877,10 +3802,9 @@ struct Sim final : ssn_sim {
     for (size_t id = 0; id < staged.size(); ++id) {
       Staged& g = staged[id];
       if (!g.valid) continue;
-      std::swap(g.rows, table_rows[id]); std::swap(g.idx, table_idx[id]);
-      std::swap(g.rows_cap, table_rows_cap[id]); std::swap(g.idx_cap, table_idx_cap[id]);
+      g.rows.swap(table_rows[id]); g.idx.swap(table_idx[id]);
       table_idx_host[id].swap(g.idx_host);
-      tables[id] = ssn::TableSlot{table_rows[id], table_idx[id], g.n_rows, g.width, g.n_idx, g.first_step};
+      tables[id] = ssn::TableSlot{table_rows[id].p, (int*)table_idx[id].p, g.n_rows, g.width, g.n_idx, g.first_step};
       g.valid = false;
     }
     HIPCHK(hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(ssn::TableSlot), hipMemcpyHostToDevice));
@@ -3898,12 +3822,8 @@ struct Sim final : ssn_sim {
       const int64_t base = steps_done / every;
       const int64_t cap = (steps_done + n) / every - base;
       const int64_t bytes = std::max<int64_t>(1, cap * probes[p].width) * (int64_t)sizeof(T);
-      if (bytes > probe_cap_bytes[p]) {
-        if (pslots[p].data) hipFree(pslots[p].data);
-        pslots[p].data = nullptr;
-        CHK(dmalloc((T**)&pslots[p].data, bytes));
-        probe_cap_bytes[p] = bytes;
-      }
+      CHK(probe_store[p].grow(*this, bytes));
+      pslots[p].data = probe_store[p].p;
       pslots[p].base_slot = base;
       pslots[p].capacity = cap;
     }

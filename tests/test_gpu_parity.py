@@ -115,7 +115,9 @@ def test_pathint_shapes_of_the_large_configurations(Simulator, shape):
 
 
 def test_steps_per_graph_and_chunked_runs_are_equivalent(Simulator):
-    """Graph replay (16 steps), eager remainder, profile mode and step-by-step runs give identical results."""
+    """Graph replay (16 steps), eager remainder, profile mode and step-by-step runs give identical results - on the default
+    plan, with one k_ensarray per timestep and on the generic item plan, each plain, with the dominant kernel timed
+    (profile 1) and with every launch timed (profile 2)."""
     pm = small_pathint(ssp_dim=55, n=100, T=10.0, limit=0.2)
     model = build(pm.model)
     outs = []
@@ -127,6 +129,28 @@ def test_steps_per_graph_and_chunked_runs_are_equivalent(Simulator):
             assert sim.n_steps == 100 and np.allclose(sim.trange(), 0.001 * np.arange(1, 101))
     for o in outs[1:]:
         np.testing.assert_array_equal(o, outs[0])
+    # every way run_steps walks a block, per plan (whole-block kernel / one k_ensarray per timestep / generic items) and per
+    # profile mode: blocks of 25, 25 | 25, 5 | 20 timesteps, with graph replays of 16 and eager remainders inside them.
+    # The whole-block kernel adds an ensemble's spike sums in another (fixed) order than the per-timestep kernels
+    # (test_fused_recurrent_core_equals_generic_path): its runs are bit-equal to the runs above, which use it too; the other
+    # two plans are bit-equal to each other and within 1e-13 of it - sums of 100 terms of magnitude <= 1 in another order
+    # differ by a few units of 2.2e-16, fed back over 100 timesteps (observed: 1.1e-16).
+    NO_BLOCK, NO_FUSED = PLAN.SSN_PLAN_NO_BLOCK_KERNEL, PLAN.SSN_PLAN_NO_FUSED_CORE
+    runs = {}
+    for flags in (0, NO_BLOCK, NO_FUSED):
+        for profile in (0, 1, 2):
+            with Simulator(None, model=model, dtype="f64", steps_per_graph=16, block_steps=25, flags=flags) as sim:
+                for c in (50, 30, 20):
+                    sim.run_steps(c, profile=profile)
+                assert sim.n_steps == 100
+                runs[flags, profile] = (np.array(sim.data[pm.probe]), sim.counters()["dominant_launches"],
+                                        {k: v[0] for k, v in sim.kernel_times().items()})
+    for (flags, profile), (out, _, _) in runs.items():
+        np.testing.assert_array_equal(out, outs[0] if flags == 0 else runs[NO_BLOCK, 0][0], err_msg=f"flags {flags} profile {profile}")
+        np.testing.assert_allclose(out, outs[0], atol=1e-13, rtol=0, err_msg=f"flags {flags} profile {profile}")
+    assert runs[0, 1][1] == 3, runs[0, 1][1:]                        # the block launch is timed where the block is a whole one
+    assert runs[NO_BLOCK, 1][1] == 100, runs[NO_BLOCK, 1][1:]
+    assert runs[NO_BLOCK, 2][2] == {"k_ensarray": 100}, runs[NO_BLOCK, 2][1:]
 
 
 def test_reset_and_state_access(Simulator):
@@ -501,6 +525,16 @@ def test_slam_optin_plans_equal_default(Simulator):
     np.testing.assert_allclose(outs[OLD], outs[0], atol=1e-12, rtol=0)       # (the gate's dot product sums 16 wave partials there, 4 here)
     np.testing.assert_array_equal(outs[OLD | PLAN.SSN_PLAN_NO_ITEM_BATCH], outs[OLD])      # one launch per operator vs batched neighbours
     assert launches[0] < launches[PLAN.SSN_PLAN_NO_PIPELINE] < launches[OLD]
+    # a profiled run computes what a plain one does: the pipelined sequence, one timestep's rounds at a time, generic items
+    for flags in (0, PLAN.SSN_PLAN_NO_PIPELINE, OLD):
+        for profile in (1, 2):
+            with Simulator(None, model=model, dtype="f64", flags=flags) as sim:
+                sim.run_steps(120, profile=profile)
+                np.testing.assert_array_equal(sim.data[sm.probe], outs[flags], err_msg=f"flags {flags} profile {profile}")
+                times = sim.kernel_times()
+            if profile == 2:
+                assert times and all(n > 0 for n, _ in times.values())
+                assert flags == OLD or "k_round" in times, (flags, sorted(times))
 
 
 def test_serial_chains_equal_plain_rounds(Simulator):

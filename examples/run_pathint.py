@@ -13,6 +13,10 @@ elapsed_time, ...).  Only plotting (``--plot``) and the Loihi back ends are not 
 (``nengo.Probe(pathintegrator.oscillators.ea_ensembles[k].neurons[:500], synapse=None, sample_every=100*dt)``) for the
 oscillators k = 1 .. M; with ``--save`` their samples go to ``<result file minus .npz>_spikes.npz`` as ``vco_n<k>``, with
 the sample times ``ts``.
+
+``--gate-oscillators T0 T1`` inhibits every oscillator for T0 < t <= T1 through ``oscillators.add_neuron_input()`` (a
+weight of -10 on every neuron, the gate of the reference's ``AdditiveInputGatedMemory``; at the oscillators' default
+rates of up to 400 Hz that thins their spikes out, it does not silence every neuron).
 """
 import argparse
 import os
@@ -51,6 +55,8 @@ def parse(argv=None):
                    help="decoder-solve evaluation points per ensemble; 0 = nengo's default max(1500, 2 n)")
     p.add_argument("--spike-probes", default=0, type=int,
                    help="probe neurons[:500] of the oscillators 1..M every 100 steps (run_pathint_gif.py probes 1, 2 and 3)")
+    p.add_argument("--gate-oscillators", default=None, type=float, nargs=2, metavar=("T0", "T1"),
+                   help="inhibit the oscillators' neurons (weight -10, through add_neuron_input()) for T0 < t <= T1")
     return p.parse_args(argv)
 
 
@@ -82,6 +88,12 @@ def main(argv=None):
     with pm.model:
         for k in range(1, args.spike_probes + 1):
             spike_probes[k] = nengo.Probe(oscillators[k].neurons[:500], synapse=None, sample_every=skip * dt)
+    if args.gate_oscillators is not None:
+        g0, g1 = args.gate_oscillators
+        array = pm.pathintegrator.oscillators
+        with pm.model:
+            gate = nengo.Node(lambda t: 1.0 if g0 < t <= g1 else 0.0, label="oscillator_gate")
+            nengo.Connection(gate, array.add_neuron_input(), transform=-10.0 * np.ones((array.n_neurons, 1)), synapse=None)
     dtype = "f64" if args.backend.endswith("f64") else "f32"
     t0 = time.time()
     sim = Simulator(pm.model, dt=dt, dtype=dtype, n_eval_points=args.n_eval_points or None)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSN_ABI_VERSION 9
+#define SSN_ABI_VERSION 10
 
 enum ssn_status {
   SSN_OK = 0,
@@ -38,7 +38,8 @@ enum ssn_status {
 };
 
 enum ssn_dtype { SSN_F32 = 0, SSN_F64 = 1 };           /* arithmetic + state type of a simulator   */
-enum ssn_buffer_kind { SSN_BUF_REAL = 0, SSN_BUF_I32 = 1, SSN_BUF_TAPS = 2 /* ssn_tap_desc records: ssn_model_desc.n_taps */ };
+enum ssn_buffer_kind { SSN_BUF_REAL = 0, SSN_BUF_I32 = 1, SSN_BUF_TAPS = 2 /* ssn_tap_desc records: ssn_model_desc.n_taps */,
+                       SSN_BUF_DRIVES = 3 /* ssn_drive_desc records (ABI 10): found by kind, count = number of records */ };
 enum ssn_neuron { SSN_LIF = 0, SSN_LIFRATE = 1, SSN_RELU = 2 };
 
 /* Operator kinds; field use per kind is listed next to ssn_op_desc. */
@@ -70,7 +71,8 @@ typedef struct ssn_buffer_desc {
  *  ENSARRAY i0 x    i1 K i2 n i3 din i4 dout i5 enc buf [K][din][n] i6 bias buf [K][n]
  *           i7 dec buf [K][dout][n] i8 dst_idx buf (int32 [K][dout]) i9 V buf i10 R buf
  *           i11 neuron                                      f0 tau_rc f1 tau_ref f2 min_voltage
- *           (all twelve i[] slots are taken: the neuron taps of an array travel as ssn_tap_desc records, ssn_model_desc.n_taps)
+ *           (all twelve i[] slots are taken: the neuron taps of an array travel as ssn_tap_desc records, ssn_model_desc.n_taps,
+ *            its neuron-input drive columns as ssn_drive_desc records, SSN_BUF_DRIVES)
  *  NEURONS  i0 J    i1 out   i2 n i3 V buf i4 R buf i5 neuron  f0 tau_rc f1 tau_ref f2 min_voltage f3 amp
  *  PES      i0 W buf i1 rows i2 cols i3 err i4 act          f0 kappa          W += kappa*outer(err,act)
  *  VOJA     i0 E buf i1 rows i2 cols i3 spk i4 key i5 learn i6 scale buf  f0 lr*dt
@@ -114,6 +116,19 @@ typedef struct ssn_tap_desc {
   int64_t dst;          /* signal offset of the tap's first element */
   double amp;           /* amplitude / dt for spiking LIF, amplitude for the rate neurons */
 } ssn_tap_desc;
+
+/* Direct neuron input of an ENSARRAY operator (ABI 10): m drive columns per ensemble,
+ *   J[k][i] = (bias[k][i] + enc[k][.][i] . x[k]) + sum_j w[k][j][i] * sig[src[k][j]],  j = 0 .. m - 1 in order
+ * src[k][j] = -1 marks an unused slot (its weights are ignored: the term is 0).  The sources are read when the inputs x are.
+ * The records travel as one buffer of kind SSN_BUF_DRIVES, found by its kind (at most one; count = number of records; no
+ * operator refers to it; the taps buffer, if any, stays the last entry).  A driven array is stepped by the per-timestep array
+ * kernel on a launch of its own; SSN_PLAN_SPLIT_BLOCK is refused with drives as it is with taps. */
+typedef struct ssn_drive_desc {
+  int32_t op;           /* index into ops[]: an SSN_OP_ENSARRAY of the per-timestep core; one record per operator at most */
+  int32_t m;            /* columns per ensemble, 1 .. 4 */
+  int32_t w_buf;        /* SSN_BUF_REAL [K][m][n] */
+  int32_t src_buf;      /* SSN_BUF_I32 [K][m]: signal offset of each column's scalar, or -1 */
+} ssn_drive_desc;
 
 /* Plan switches: the bits of ssn_model_desc.flags.  Debug / A-B switches, default 0; tests check that every alternative
  * plan gives the same results.  ssn_create refuses a value with any other bit set.
@@ -177,7 +192,7 @@ enum ssn_plan_flag {
   /* split ensembles in the whole-block kernel (f32, at most 4 decoded rows): an array with fewer ensembles than the GPU
    * has CUs (a 4- or 8-GPU shard of config 2) is stepped by 2 or 4 member workgroups per ensemble that exchange their
    * partial sums every timestep; needs every workgroup of the launch resident at once, i.e. the GPU for this process
-   * alone.  Not available for an array with neuron taps (ssn_create: SSN_EUNSUPPORTED) */
+   * alone.  Not available for an array with neuron taps or drive columns (ssn_create: SSN_EUNSUPPORTED) */
   SSN_PLAN_SPLIT_BLOCK = 1073741824
 };
 /* every bit that has a name */

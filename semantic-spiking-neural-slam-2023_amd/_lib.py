@@ -9,9 +9,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSN_HIP_LIB") or os.path.join(_HERE, "libssn_hip.so")     # override: A/B builds of the library
 
-SSN_ABI_VERSION = 9
+SSN_ABI_VERSION = 10
 SSN_F32, SSN_F64 = 0, 1
-SSN_BUF_REAL, SSN_BUF_I32, SSN_BUF_TAPS = 0, 1, 2
+SSN_BUF_REAL, SSN_BUF_I32, SSN_BUF_TAPS, SSN_BUF_DRIVES = 0, 1, 2, 3
 NEURON_CODE = {"lif": 0, "lifrate": 1, "relu": 2}
 OP_CODE = {"fill": 1, "table": 2, "axpy": 3, "matvec": 4, "lowpass": 5, "ensarray": 6, "neurons": 7,
            "pes": 8, "voja": 9, "cleanup": 10, "gate": 11, "lincomb": 12}
@@ -63,6 +63,10 @@ class Range(C.Structure):
 class TapDesc(C.Structure):
     _fields_ = [("op", C.c_int32), ("k", C.c_int32), ("first", C.c_int64), ("count", C.c_int64), ("dst", C.c_int64),
                 ("amp", C.c_double)]
+
+
+class DriveDesc(C.Structure):
+    _fields_ = [("op", C.c_int32), ("m", C.c_int32), ("w_buf", C.c_int32), ("src_buf", C.c_int32)]
 
 
 class ModelDesc(C.Structure):

@@ -23,6 +23,11 @@ Operator kinds (dict ``kind``):
             sig[dst + j] = tap_amp * a[k, first + j] (the neuron output ``Probe(member.neurons[...])`` samples; one tap
             per member, the hull of its probed slices).  The device kernels write them; ``oracle.OracleSimulator`` is
             frozen and does not know taps - its rows for such probes stay zero (``oracle.graphwalk`` is their reference)
+            optional ``drive`` {"m": m, "w": buffer [K][m][n], "src": buffer int32 [K][m]}: direct neuron input of the
+            members (``EnsembleArray.add_neuron_input()``, ``Connection(gate, member.neurons, transform=n x m_c)``):
+            J[k, i] = (bias + enc.x) + sum_j w[k, j, i] * sig[src[k, j]], the columns j in connection order; src = -1
+            marks an unused slot (its weights are zero); m <= 4.  Nothing K * n wide is a signal.  Like the taps, the
+            frozen stepper does not know drive columns (``oracle.graphwalk`` is their reference)
   neurons   neuron step on a current vector J -> spike vector
   pes / voja / cleanup / gate                              (SLAM; Appendix A.7, A.8, slam.py:212-237)
 """
@@ -244,6 +249,7 @@ class Builder:
         # ensemble-array blocks (equal ensembles stepped by one kernel)
         self.block_of = {}
         self.blocks = []
+        self.ninput_of = {}
         for sub in ([net] + list(net.all_networks)):
             eas = getattr(sub, "ea_ensembles", None)
             if not eas:
@@ -258,8 +264,12 @@ class Builder:
                 rank, world = self.vco_shard
                 per = -(-len(eas) // world)
                 lo, hi = min(len(eas), rank * per), min(len(eas), (rank + 1) * per)
-            blk = {"net": sub, "ens": list(eas), "rows": [[] for _ in eas], "range": (lo, hi)}
+            blk = {"net": sub, "ens": list(eas), "rows": [[] for _ in eas], "range": (lo, hi),
+                   "drive": [[] for _ in eas]}          # per member: [(weights (n,), Ref of one source element)]
             self.blocks.append(blk)
+            ni = getattr(sub, "neuron_input", None)
+            if ni is not None:
+                self.ninput_of[id(ni)] = blk             # (the builder sees through it: no signal of its own)
             for i, e in enumerate(eas):
                 self.block_of[id(e)] = (blk, i)
 
@@ -326,6 +336,8 @@ class Builder:
     # -- nodes -----------------------------------------------------------------------------
     def _alloc_node(self, n):
         out = getattr(n, "output", None)
+        if id(n) in self.ninput_of:
+            return
         if out is None:
             r = self.alloc("R", n.size_in)
             self.node_in[id(n)] = r
@@ -576,9 +588,7 @@ class Builder:
         elif k == "ensemble":
             full = self.ens_in[id(obj)]
         elif k == "neurons":
-            ens = obj.ensemble
-            if id(ens) in self.block_of:
-                raise fe.BuildError("direct neuron input into an EnsembleArray member is not supported")
+            ens = obj.ensemble          # (a plain ensemble: _lower_connection lowers the neurons of array members to drive columns)
             if self._is_sharded(ens) and length is not None:
                 raise fe.BuildError("slices of the neurons of a neuron-sharded ensemble are not supported")
             full = self.ens_J[id(ens)]
@@ -607,9 +617,115 @@ class Builder:
         self.op("lowpass", dst=state, src=src, len=size, a=_lowpass_coeff(tau, self.dt), gain=gain)
         self.op("axpy", dst=dst, src=state, len=size, alpha=1.0, mode="inc")
 
+    # -- direct neuron input of EnsembleArray members: drive columns -------------------------
+    def _drive_target(self, post):
+        """(block, [(member, first transform row, first neuron, count)]) when ``post`` is the neurons of an EnsembleArray
+        member, the array's ``neuron_input`` node or a contiguous slice of either; None otherwise."""
+        obj, start, length = _contig(post)
+        k = _kind(obj)
+        if k == "neurons" and id(obj.ensemble) in self.block_of:
+            blk, i = self.block_of[id(obj.ensemble)]
+            n = obj.ensemble.n_neurons
+            start, length = (0, n) if length is None else (start, length)
+            if start < 0 or start + length > n:
+                raise fe.BuildError(f"slice [{start}:{start + length}] outside the {n} neurons of {obj.ensemble!r}")
+            return blk, [(i, 0, start, length)]
+        if k == "node" and id(obj) in self.ninput_of:
+            blk = self.ninput_of[id(obj)]
+            n = blk["ens"][0].n_neurons
+            start, length = (0, obj.size_in) if length is None else (start, length)
+            parts = []
+            for i in range(start // n, -(-(start + length) // n)):
+                lo, hi = max(start, i * n), min(start + length, (i + 1) * n)
+                parts.append((i, lo - start, lo - i * n, hi - lo))
+            return blk, parts
+        return None
+
+    def _lower_drive(self, c, blk, parts):
+        """A connection into member neurons: ``m_c`` drive columns in every member whose rows it touches.  The columns read
+        the connection's ``m_c``-wide source - through a synapse its filter state (S arena), which the array reads before
+        the update: the one-step delay of a filtered connection."""
+        label = getattr(blk["net"], "label", None) or "ensarray"
+        if self.vco_shard is not None:
+            raise fe.BuildError(f"direct neuron input into the EnsembleArray {label!r} is not supported with sharding "
+                                f"({'neuron_shard' if self.neuron_shard is not None else 'vco_shard'} builds)")
+        pre_obj, pre_start, pre_len = _contig(c.pre)
+        pk = _kind(pre_obj)
+        T = np.asarray(c.transform, dtype=float)
+        rows = sum(p[3] for p in parts)
+        if getattr(c, "learning_rule_type", None) is not None:
+            raise fe.BuildError("learning rules on a connection into the neurons of an EnsembleArray member are not supported")
+        if T.ndim != 2:
+            raise fe.BuildError(f"{c!r}: a scalar (identity) transform from a {rows}-wide source into the neurons of the "
+                                f"EnsembleArray {label!r} is not a column form: pass a ({rows}, m) transform from an m-wide "
+                                "source, m <= 4")
+        m_c = T.shape[1]
+        if T.shape[0] != rows:
+            raise fe.BuildError(f"transform {T.shape} does not map onto the {rows} neurons of {c.post!r}")
+        if m_c > 4:
+            raise fe.BuildError(f"EnsembleArray {label!r}: {m_c} neuron-input columns on one member (at most 4)")
+        bc = BuiltConnection(weights=T, learned_buffer=None)
+        self.model.params[c] = bc
+        if pk == "node":            # (never a neuron_input node: _lower_connection has refused those)
+            if c.function is not None:
+                raise fe.BuildError("functions on connections from Nodes are not supported")
+            full = self.node_out[id(pre_obj)]
+            src = full if pre_len is None else full.slice(pre_start, pre_len)
+        elif pk == "ensemble":
+            e = pre_obj
+            if c.synapse is None and id(e) in self.block_of and self.block_of[id(e)][0] is blk:
+                # the array operator itself writes the decoded value: read without a synapse it would be a loop within one
+                # timestep inside one operator, which the scheduler (it orders operators) could not see
+                raise fe.BuildError(f"{c!r}: a neuron input without a synapse decoded from a member of the same EnsembleArray "
+                                    f"{label!r} is a loop without a synapse within one timestep: give the connection a synapse")
+            if pre_len is None:
+                pre_start, pre_len = 0, e.dimensions
+            src = self.alloc("W", c.size_mid)       # the decoded function value; the transform lives in the columns
+
+            def done(D, e=e, src=src, bc=bc, T=T):
+                bc.weights = T @ D
+                self._register_rows(e, D, src)
+            self._request_decoders(c, e, pre_start, pre_len, 1.0, done)
+        else:
+            raise fe.BuildError(f"cannot drive the neurons of an EnsembleArray member from {pre_obj!r}")
+        if src.len != m_c:
+            raise fe.BuildError(f"transform {T.shape} does not match the {src.len}-wide source of {c!r}")
+        if c.synapse is not None:
+            state = self.alloc("S", m_c)
+            self.op("lowpass", dst=state, src=src, len=m_c, a=_lowpass_coeff(float(c.synapse.tau), self.dt), gain=1.0)
+            src = state
+        n = blk["ens"][0].n_neurons
+        for i, r0, n0, cnt in parts:
+            for j in range(m_c):
+                w = np.zeros(n)
+                w[n0:n0 + cnt] = T[r0:r0 + cnt, j]          # rows outside a sliced target stay zero
+                blk["drive"][i].append((w, src.slice(j, 1)))
+
+    def _is_member_link(self, c):
+        """``neuron_input[i*n:(i+1)*n] -> ea_ensembles[i].neurons`` as ``add_neuron_input`` declares it."""
+        pre_obj, pre_start, pre_len = _contig(c.pre)
+        post_obj, post_start, post_len = _contig(c.post)
+        if _kind(post_obj) != "neurons" or id(post_obj.ensemble) not in self.block_of:
+            return False
+        blk, i = self.block_of[id(post_obj.ensemble)]
+        n = post_obj.ensemble.n_neurons
+        T = np.asarray(c.transform, dtype=float)
+        return (blk is self.ninput_of[id(pre_obj)] and post_len is None and (pre_start, pre_len) == (i * n, n)
+                and c.synapse is None and c.function is None and T.ndim == 0 and float(T) == 1.0)
+
     def _lower_connection(self, c):
         pre_obj, pre_start, pre_len = _contig(c.pre)
         pk = _kind(pre_obj)
+        if pk == "node" and id(pre_obj) in self.ninput_of:
+            if not self._is_member_link(c):
+                raise fe.BuildError(f"{c!r}: a connection out of the neuron_input node of an EnsembleArray other than its own "
+                                    "member links is not supported")
+            self.model.params[c] = BuiltConnection(weights=np.asarray(c.transform, dtype=float), learned_buffer=None)
+            return
+        drive = self._drive_target(c.post)
+        if drive is not None:
+            self._lower_drive(c, *drive)
+            return
         dst = self._target_ref(c.post)
         size_out = dst.len
         T = np.asarray(c.transform, dtype=float)
@@ -816,6 +932,9 @@ class Builder:
                 mark(r)
         for blk in self.blocks:
             mark(blk["x"])
+            for cols in blk["drive"]:
+                for _, ref in cols:
+                    mark(ref)
         for o in self.raw_ops:
             if o["kind"] == "cleanup":
                 mark(Ref(o["src"].arena, o["src"].off, o["cols"]))
@@ -896,6 +1015,16 @@ class Builder:
         taps = [(i - lo,) + self.tap_hull[id(ens[i])] + (self.tap_ref[id(ens[i])],)
                 for i in range(lo, hi) if id(ens[i]) in self.tap_ref]
         extra = dict(taps=taps, tap_amp=amp) if taps else {}
+        dm = max(len(blk["drive"][i]) for i in range(lo, hi))
+        if dm > 4:
+            raise fe.BuildError(f"EnsembleArray {label!r}: {dm} neuron-input columns on one member (at most 4)")
+        if dm:
+            dw = np.zeros((K, dm, n))
+            dsrc = np.full((K, dm), None, dtype=object)
+            for i in range(lo, hi):
+                for j, (w, ref) in enumerate(blk["drive"][i]):
+                    dw[i - lo, j], dsrc[i - lo, j] = w, ref
+            extra["drive"] = {"m": dm, "w": m.add_buffer(dw, f"{label}_drive"), "src_refs": dsrc}
         self.op("ensarray", x=x, K=K, n=n, din=din, dout=dout, **extra,
                 enc=m.add_buffer(enc, f"{label}_enc"), bias=m.add_buffer(bias, f"{label}_bias"),
                 dec=m.add_buffer(dec, f"{label}_dec"), dst_refs=dst_idx,
@@ -938,6 +1067,9 @@ class Builder:
                                       "shape": be.scaled_encoders.shape, "every": every, "ens": post})
             return
         if k == "node":
+            if id(obj) in self.ninput_of:
+                raise fe.BuildError(f"probing the neuron_input node of an EnsembleArray is not supported ({p!r}): the node has "
+                                    "no signal of its own, probe what drives it")
             full = self.node_out[id(obj)]
         elif k == "ensemble":
             if attr not in ("decoded_output", "output"):
@@ -1009,6 +1141,11 @@ class Builder:
                 o["dst_idx"] = m.add_buffer(idx, f"{o['label']}_dst_idx", role="index")
                 if "taps" in o:
                     o["taps"] = [(k, first, count, A(r)) for k, first, count, r in o["taps"]]
+                if "drive" in o:
+                    d = dict(o["drive"])
+                    src = np.array([[-1 if r is None else A(r) for r in row] for row in d.pop("src_refs")], dtype=np.int32)
+                    d["src"] = m.add_buffer(src, f"{o['label']}_drive_src", role="index")
+                    o["drive"] = d
             ops.append(o)
         for p in m.probes:
             if "src" in p:
@@ -1120,7 +1257,10 @@ def op_access(o, model):
             prev = v
         runs.append(S(start, prev - start + 1))
         runs += [S(dst, count) for _, _, count, dst in o.get("taps", ())]
-        return runs, [], [S(o["x"], o["K"] * o["din"])], [B(o["v"]), B(o["r"])]
+        reads = [S(o["x"], o["K"] * o["din"])]
+        if "drive" in o:         # the column sources: scheduling, stage partition, glue folding and the planner see them
+            reads += [S(int(v), 1) for v in np.unique(model.buffers[o["drive"]["src"]]) if v >= 0]
+        return runs, [], reads, [B(o["v"]), B(o["r"])]
     if k == "neurons":
         return [S(o["out"], o["n"])], [], [S(o["j"], o["n"])], [B(o["v"]), B(o["r"])]
     if k == "pes":
@@ -1435,7 +1575,11 @@ def schedule_ops(ops, model):
     """
     n = len(ops)
     acc = [op_access(o, model) for o in ops]
-    entries = [(res, cls, i) for i, a in enumerate(acc) for cls in range(4) for res in a[cls]]
+    for o, a in zip(ops, acc):      # (the edges below run between operators: an operator that reads what it sets has none)
+        if o["kind"] == "ensarray" and any(_overlap(r, w) for r in a[2] for w in a[0]):
+            raise fe.BuildError(f"EnsembleArray {o['label']!r} reads a signal that it writes in the same timestep "
+                                "(a loop without a synapse)")
+    entries =[(res, cls, i) for i, a in enumerate(acc) for cls in range(4) for res in a[cls]]
     succ = [set() for _ in range(n)]
     for x in range(len(entries)):
         rx, cx, ix = entries[x]

@@ -253,10 +253,12 @@ struct Sim final : ssn_sim {
   using MOp = ssn::MicroOp<T>;
   static constexpr int VW = 16 / sizeof(T);
 
+  struct DriveSet;
   struct Item {
     int type = IT_PROGRAM;
     int op_begin = 0, op_count = 0;          // program: range in d_mops
     ssn::EnsArgs<T> ens;
+    const DriveSet* drv = nullptr;           // IT_ENS: the operator's drive columns, if it has any (an entry of drive_sets)
     ssn::FinishArgs<T> fin;
     bool dominant = false;
     // matvec / pes / voja / neurons
@@ -305,6 +307,12 @@ struct Sim final : ssn_sim {
   // [K][4] = first neuron, count (0: ensemble without a tap), destination signal, index among the operator's taps
   struct TapSet { std::vector<ssn_tap_desc> list; int* d_tab = nullptr; double amp = 0.0; };
   std::map<int, TapSet> tap_sets;             // operator index -> its taps
+  // neuron-input drive columns of the ensemble arrays (ssn_drive_desc records, ABI 10): per driven operator its record, the
+  // host copy of the column sources and the tables its kernel reads - [K][m][2] = signal offset (-1: unused), 1 if read from
+  // the timestep's block row; d_tab reads everything from the signal vector, d_tab_rows (fused cores) the pre-stage signals
+  // from the row
+  struct DriveSet { ssn_drive_desc rec; std::vector<int32_t> src; int* d_tab = nullptr; int* d_tab_rows = nullptr; };
+  std::map<int, DriveSet> drive_sets;         // operator index -> its drive columns
   const ssn_op_desc* ops_base = nullptr;      // (the model's operator array: valid during ssn_create only)
   std::set<int> sparse_w;                     // decoder buffers multiplied with a LIF spike vector
   std::set<int> learned_w;                    // matrices a learning rule (PES, Voja) updates
@@ -662,6 +670,66 @@ struct Sim final : ssn_sim {
     }
     return SSN_OK;
   }
+  // Drive columns (ABI 10): the records are found by the buffer's kind; every record names a core ensemble array (one record per
+  // operator), 1 <= m <= 4, a real buffer of K * m * n weights and an int32 buffer of K * m sources inside the signal vector or -1.
+  int read_drives(const ssn_model_desc* m) {
+    ops_base = m->ops;
+    int at = -1;
+    for (int i = 0; i < m->n_buffers; ++i)
+      if (m->buffers[i].kind == SSN_BUF_DRIVES) {
+        if (at >= 0) return fail(SSN_EINVAL, "buffers %d and %d: at most one buffer of drive records (SSN_BUF_DRIVES)", at, i);
+        at = i;
+      }
+    if (at < 0) return SSN_OK;
+    const ssn_buffer_desc& db = m->buffers[at];
+    if (db.count < 1 || !db.data) return fail(SSN_EINVAL, "buffer %d: a drive buffer holds at least one ssn_drive_desc record", at);
+    if (opt.has(SSN_PLAN_SPLIT_BLOCK))
+      return fail(SSN_EUNSUPPORTED, "SSN_PLAN_SPLIT_BLOCK does not go with neuron-input drive columns (the whole-block kernel has no driven form)");
+    const ssn_drive_desc* const list = (const ssn_drive_desc*)db.data;
+    for (int64_t i = 0; i < db.count; ++i) {
+      const ssn_drive_desc& d = list[i];
+      if (d.op < 0 || d.op >= m->n_ops || m->ops[d.op].kind != SSN_OP_ENSARRAY || m->ops[d.op].stage != 1)
+        return fail(SSN_EINVAL, "drive %lld: operator %d is not an ensemble array of the per-timestep core", (long long)i, d.op);
+      if (drive_sets.count(d.op)) return fail(SSN_EINVAL, "drive %lld: operator %d already has a drive record", (long long)i, d.op);
+      if (d.m < 1 || d.m > ssn::ENS_DRIVE_MAX) return fail(SSN_EINVAL, "drive %lld: m = %d columns (1 .. %d)", (long long)i, d.m, ssn::ENS_DRIVE_MAX);
+      const ssn_op_desc& o = m->ops[d.op];
+      const int64_t K = o.i[1], n = o.i[2];
+      if (d.w_buf < 0 || d.w_buf >= m->n_buffers || m->buffers[d.w_buf].kind != SSN_BUF_REAL || m->buffers[d.w_buf].count != K * d.m * n)
+        return fail(SSN_EINVAL, "drive %lld: w_buf must be a real buffer of K * m * n = %lld weights", (long long)i, (long long)(K * d.m * n));
+      if (d.src_buf < 0 || d.src_buf >= m->n_buffers || m->buffers[d.src_buf].kind != SSN_BUF_I32 || m->buffers[d.src_buf].count != K * d.m)
+        return fail(SSN_EINVAL, "drive %lld: src_buf must be an int32 buffer of K * m = %lld sources", (long long)i, (long long)(K * d.m));
+      const int32_t* src = (const int32_t*)m->buffers[d.src_buf].data;
+      for (int64_t j = 0; j < K * d.m; ++j)
+        if (src[j] < -1 || src[j] >= n_sig) return fail(SSN_EINVAL, "drive %lld: source %lld = %d outside the %lld signals (-1: unused)", (long long)i, (long long)j, src[j], (long long)n_sig);
+      CHK(shape(d.w_buf, K * d.m, n, true, false));          // rows padded like enc's
+      if (bufs[d.w_buf].ld != bufs[o.i[5]].ld) return fail(SSN_EINVAL, "drive %lld: weight rows and encoder rows are padded differently", (long long)i);
+      DriveSet& ds = drive_sets[d.op];
+      ds.rec = d;
+      ds.src.assign(src, src + K * d.m);
+    }
+    return SSN_OK;
+  }
+  // the device tables of the drive columns (once the boundary ranges are known: before plan())
+  int drive_tables() {
+    for (auto& kv : drive_sets) {
+      DriveSet& ds = kv.second;
+      std::vector<int> tab(ds.src.size() * 2, 0), rows(ds.src.size() * 2, 0);
+      for (size_t j = 0; j < ds.src.size(); ++j) {
+        tab[2 * j] = rows[2 * j] = ds.src[j];
+        for (auto& r : pre_to_core) if (ds.src[j] >= r.lo && ds.src[j] < r.hi) rows[2 * j + 1] = 1;
+      }
+      CHK(dmalloc(&ds.d_tab, (int64_t)tab.size() * 4));
+      CHK(dmalloc(&ds.d_tab_rows, (int64_t)rows.size() * 4));
+      HIPCHK(hipMemcpy(ds.d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(ds.d_tab_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    }
+    return SSN_OK;
+  }
+  const DriveSet* drives_of(const ssn_op_desc& o) const {
+    if (drive_sets.empty() || !ops_base) return nullptr;
+    auto it = drive_sets.find((int)(&o - ops_base));
+    return it == drive_sets.end() ? nullptr : &it->second;
+  }
   const TapSet* taps_of(const ssn_op_desc& o) const {
     if (tap_sets.empty() || !ops_base) return nullptr;
     auto it = tap_sets.find((int)(&o - ops_base));
@@ -804,10 +872,11 @@ struct Sim final : ssn_sim {
       }
     }
     CHK(read_taps(m));
+    CHK(read_drives(m));
     // uploads
     for (int i = 0; i < m->n_buffers; ++i) {
       Buf& b = bufs[i];
-      if (b.kind == SSN_BUF_TAPS) continue;       // (host-side records: read_taps)
+      if (b.kind == SSN_BUF_TAPS || b.kind == SSN_BUF_DRIVES) continue;       // (host-side records: read_taps, read_drives)
       if (b.kind == SSN_BUF_I32) {
         CHK(dmalloc((int32_t**)&b.d, b.count * 4));
         HIPCHK(hipMemcpy(b.d, m->buffers[i].data, (size_t)b.count * 4, hipMemcpyHostToDevice));
@@ -861,6 +930,7 @@ struct Sim final : ssn_sim {
     // fills and drains once per graph: SLAM config 3 106.3 us per timestep at 16, 105.9 at 32, 104.5 at 64 - round 4), else 16
     steps_per_graph = m->steps_per_graph != 0 ? m->steps_per_graph : ((block == 0 || block % 64 == 0) ? 64 : 16);
     if (steps_per_graph > 128) return fail(SSN_EINVAL, "steps_per_graph %d: at most 128 (a glue block carries its timestep offset in 8 signed bits)", steps_per_graph);
+    CHK(drive_tables());
     CHK(plan(m));
     CHK(capture());
     HIPCHK(hipStreamSynchronize(stream));
@@ -899,6 +969,7 @@ struct Sim final : ssn_sim {
     a.fast = ens_fast(o) ? (ens_sparse(o) ? 1 : 2) : 0;
     a.defer = 0; a.sub = 0; a.partials_stride = 0;
     if (const TapSet* ts = taps_of(o)) { a.tap = ts->d_tab; a.tap_amp = (T)ts->amp; a.tap_sig = sig; a.tap_rows = nullptr; }
+    if (const DriveSet* ds = drives_of(o)) { a.drv_m = ds->rec.m; a.drv_w = (const T*)bufs[ds->rec.w_buf].d; a.drv_src = ds->d_tab; }
     ens_chunking(a);
   }
 
@@ -1254,6 +1325,16 @@ struct Sim final : ssn_sim {
       const ssn_op_desc& o = m->ops[i];
       if (!inside(o.i[0], o.i[0] + o.i[2], pre_to_core)) return false;
     }
+    // drive columns: the fused prologue reads their scalars from the timestep's block row - every source must be a pre-stage
+    // signal that no operator of the core adds to (the recurrent terms are folded into x only)
+    const DriveSet* const drv = drives_of(eo);
+    if (drv)
+      for (int32_t sx : drv->src) {
+        if (sx < 0) continue;
+        if (!inside(sx, sx + 1, pre_to_core)) return false;
+        for (int i : axpys) if (sx >= m->ops[i].i[0] && sx < m->ops[i].i[0] + m->ops[i].i[2]) return false;
+        for (int i : lows) if (sx >= m->ops[i].i[0] && sx < m->ops[i].i[0] + m->ops[i].i[2]) return false;
+      }
     const int32_t* didx = (const int32_t*)m->buffers[eo.i[8]].data;
     std::vector<int> row_of((size_t)n_sig, -1);
     for (int64_t j = 0; j < K * dout; ++j) row_of[(size_t)didx[j]] = (int)j;   // padded rows share a trash slot: harmless
@@ -1337,7 +1418,8 @@ struct Sim final : ssn_sim {
       { const int q = opt.block_split; if (q == 1 || q == 2 || q == 4 || q == 8) split_P = q; }
       if (split_P > 1) n_member = (int)(((n_ens + split_P - 1) / split_P + 3) / 4 * 4);
     }
-    if (defer && !opt.has(SSN_PLAN_NO_BLOCK_KERNEL) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt)) &&
+    // (a driven array is not eligible: k_ens_block has no drive columns)
+    if (defer && !drv && !opt.has(SSN_PLAN_NO_BLOCK_KERNEL) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt)) &&
         ssn::ens_block_supported<T>((int)din, (int)dout, split_P > 1 ? n_member : (int)eo.i[2], opt.block_variant.v, &blk_threads, &blk_tpb, &blk_npt, &blk_lds)) {
       const int64_t nr = K * dout;
       int* d_lp = nullptr; T* d_a = nullptr; T* d_b = nullptr; unsigned char* d_ro = nullptr; int* d_xrow = nullptr; T* d_xalpha = nullptr;
@@ -1392,9 +1474,11 @@ struct Sim final : ssn_sim {
     // ---- plan B: [k_ensarray (fused prologue), k_ens_finish] ------------------------------------------
     Item it; it.type = IT_ENS;
     fill_ens_args(eo, it.ens);
+    it.drv = drv;
     ssn::EnsArgs<T>& a = it.ens;
     a.xrows = bsig;
     if (a.tap) a.tap_rows = bsig;      // (a fused core has no hand-off operator: the kernel writes the post stage's rows itself)
+    if (drv) a.drv_src = drv->d_tab_rows;      // (no row-in operator either: pre-stage sources are read from the block row)
     // measured on MI355X (tools/bench_shard.py): 5080 workgroups (config 2 on one GPU) 35.4 us/step with the
     // separate finish kernel vs 37.4 deferred; 2540 / 1270 / 640 workgroups (2 / 4 / 8-GPU shards) 24.5 / 15.8 /
     // 13.1 vs 22.0 / 12.5 / 9.4 deferred
@@ -1653,6 +1737,7 @@ struct Sim final : ssn_sim {
           Item it; it.type = IT_ENS;
           ssn::EnsArgs<T>& a = it.ens;
           fill_ens_args(o, a);
+          it.drv = drives_of(o);
           ens_chunking(a, 2048);
           CHK(dmalloc(&a.partials, (int64_t)a.K * a.P * a.dout * (int64_t)sizeof(T)));
           const int64_t units = (int64_t)a.K * a.n;
@@ -1972,8 +2057,9 @@ struct Sim final : ssn_sim {
 
   // k_round body of an ensemble array (-1: its variant has none, it is launched on its own)
   int ens_round_kind(const ssn::EnsArgs<T>& a) const {
-    // (a tapped array is launched on its own - k_ensarray's tapped twin: the bodies of the round grid do not know taps)
-    if (a.defer || a.xrows || a.tap || opt.has(SSN_PLAN_ENS_OWN_LAUNCH)) return -1;
+    // (a tapped array is launched on its own - k_ensarray's tapped twin: the bodies of the round grid do not know taps - and so
+    //  is a driven one: k_ensarray_drv)
+    if (a.defer || a.xrows || a.tap || a.drv_m || opt.has(SSN_PLAN_ENS_OWN_LAUNCH)) return -1;
     if (a.fast == 1 && a.din == 3 && a.dout == 4) return ssn::RK_ENS_3_4_S;
     if (a.fast == 1 && a.din == 3 && a.dout == 5) return ssn::RK_ENS_3_5_S;
     if (a.fast == 2 && a.din == 1 && a.dout == 1) {
@@ -3034,6 +3120,10 @@ struct Sim final : ssn_sim {
         if (it.ens.direct) acc_index_list(a, (const void*)it.ens.didx, true);
         if (const TapSet* ts = taps_of(it.ens)) for (const ssn_tap_desc& t : ts->list) acc_sig(a, t.dst, t.count, true);
         acc_sig(a, it.ens.x_off, (int64_t)it.ens.K * it.ens.din, false);
+        if (const DriveSet* ds = it.drv) {
+          for (int32_t sx : ds->src) if (sx >= 0) acc_sig(a, sx, 1, false);
+          acc_ptr(a, it.ens.drv_w, false);
+        }
         for (int j = 0; j < it.ens.n_rec; ++j) acc_sig(a, it.ens.rec_src[j], it.ens.rec_len[j], false);      // (folded input terms)
         acc_ptr(a, it.ens.partials, true); acc_ptr(a, it.ens.V, true); acc_ptr(a, it.ens.R, true);
         acc_ptr(a, it.ens.enc, false); acc_ptr(a, it.ens.bias, false); acc_ptr(a, it.ens.dec, false);
@@ -4032,6 +4122,6 @@ int ssn_device_count(void) {
   return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 const char* ssn_last_error(void) { return g_err.c_str(); }
-const char* ssn_version(void) { return "libssn_hip 0.9 (gfx950, ABI 9)"; }
+const char* ssn_version(void) { return "libssn_hip 0.10 (gfx950, ABI 10)"; }
 
 }  // extern "C"

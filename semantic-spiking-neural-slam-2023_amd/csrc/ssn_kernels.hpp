@@ -119,7 +119,10 @@ template <int DOUT> struct DecPitch { static constexpr int value = DOUT <= 4 ? 4
 
 // TAP: the array has neuron taps (EnsArgs::tap) - an instantiation of its own, so that an array without taps runs the code it
 // always ran; the bodies of the round grid have no tapped form (a tapped array is launched on its own: Sim::ens_round_kind)
-template <typename T, int DIN, int DOUT, int MODE, bool RND = false, bool TAP = false>   // MODE 0 generic | 1 fast, spike-sparse decoders | 2 fast, dense decoders; RND: a body of the round grid
+// DRV: the array has neuron-input drive columns (EnsArgs::drv_m) - a third instantiation (it honours taps at run time too); up
+// to four weight vectors per neuron are streamed beside enc, their scalars read beside x.  A driven array is launched on its
+// own as a tapped one is.
+template <typename T, int DIN, int DOUT, int MODE, bool RND = false, bool TAP = false, bool DRV = false>   // MODE 0 generic | 1 fast, spike-sparse decoders | 2 fast, dense decoders; RND: a body of the round grid
 __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsigned char* smem) {   // smem: 4 * DOUT + DIN values of T
   if (bx >= a.K * a.P) return;          // (grid.x is sized for the larger array of a batch)
   using vec = typename VecT<T>::type;
@@ -145,11 +148,20 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
   // The streaming loads of the first sweep are issued before the (dependent, scalar) input assembly so
   // that its latency chain - step counter -> row address -> x - hides under them.
   T e[DIN][W], b[W], Vv[W], Rv[W];
+  constexpr int DM = DRV ? ENS_DRIVE_MAX : 1;
+  T dw[DM][W];                            // drive weights of this sweep (DRV)
+  const int drv_m = DRV ? a.drv_m : 0;
+  const T* __restrict__ drw = DRV ? a.drv_w + (size_t)k * drv_m * row : nullptr;
   int v = v_begin + (int)threadIdx.x;
   auto load_sweep = [&](int vv) {
     const size_t o = (size_t)vv * W;
 #pragma unroll
     for (int d = 0; d < DIN; ++d) *(vec*)e[d] = *(const vec*)(enc + d * row + o);
+    if constexpr (DRV) {
+#pragma unroll
+      for (int q = 0; q < DM; ++q)
+        if (q < drv_m) *(vec*)dw[q] = *(const vec*)(drw + q * row + o);
+    }
     *(vec*)b = *(const vec*)(bias + o);
     *(vec*)Vv = *(const vec*)(Vp + o);
     if constexpr (!FAST) *(vec*)Rv = *(const vec*)(Rp + o);
@@ -262,6 +274,28 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
     for (int d = 0; d < DIN; ++d) x[d] = s_x[d];
   }
 
+  // the scalars of the drive columns, read where x is: from this timestep's block row (a pre-stage signal of a fused core) or
+  // from the live signal vector; an unused slot contributes 0
+  T ds[DM];
+  if constexpr (DRV) {
+    const T* drow = a.xrows ? a.xrows + (size_t)(step - a.ctx->block_start + 1) * a.n_sig : a.sig;
+#pragma unroll
+    for (int q = 0; q < DM; ++q) {
+      ds[q] = T(0);
+      if (q < drv_m) {
+        const int* t = a.drv_src + ((size_t)k * drv_m + q) * 2;
+        if (t[0] >= 0) ds[q] = (t[1] ? drow : a.sig)[t[0]];
+      }
+    }
+  }
+  auto drive = [&](int j) {               // sum of the columns in order, added to bias + enc.x as one term (the graph walk's order)
+    T dr = T(0);
+#pragma unroll
+    for (int q = 0; q < DM; ++q)
+      if (q < drv_m) dr += dw[q][j] * ds[q];
+    return dr;
+  };
+
   T acc[DOUT];
 #pragma unroll
   for (int r = 0; r < DOUT; ++r) acc[r] = T(0);
@@ -278,6 +312,7 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
           T J = b[j];
 #pragma unroll
           for (int d = 0; d < DIN; ++d) J += e[d][j] * x[d];
+          if constexpr (DRV) J += drive(j);
           const T act = neuron_step(np, J, Vv[j], Rv[j]);
           if (TAP && tp_cnt) tap_store((int)o + j, a.tap_amp * act);
 #pragma unroll
@@ -295,6 +330,7 @@ __device__ __forceinline__ void ens_body(const EnsArgs<T>& a, const int bx, unsi
           T J = b[j];
 #pragma unroll
           for (int d = 0; d < DIN; ++d) J += e[d][j] * x[d];
+          if constexpr (DRV) J += drive(j);
           // unpack the state word, then nengo's LIF step operation for operation
           const T s = Vv[j];
           T V = s < T(0) ? T(0) : s;
@@ -424,6 +460,12 @@ __global__ __launch_bounds__(256) void k_ensarray(EnsBatch<T> batch) {
   __shared__ __align__(16) unsigned char smem[(4 * DOUT + DIN) * sizeof(T)];
   ens_body<T, DIN, DOUT, MODE, false, TAP>(batch.a[blockIdx.y], (int)blockIdx.x, smem);
 }
+// the driven form (a kernel of its own name: k_ensarray's instantiations keep theirs); taps are honoured at run time
+template <typename T, int DIN, int DOUT, int MODE>
+__global__ __launch_bounds__(256) void k_ensarray_drv(EnsBatch<T> batch) {
+  __shared__ __align__(16) unsigned char smem[(4 * DOUT + DIN) * sizeof(T)];
+  ens_body<T, DIN, DOUT, MODE, false, true, true>(batch.a[blockIdx.y], (int)blockIdx.x, smem);
+}
 
 // decoder re-layout [K][dout][n] (row-major, host order, ld = n_pad) <-> [K][n_pad][DP] (neuron-major)
 template <typename T>
@@ -506,11 +548,14 @@ static hipError_t launch_ens_dout(hipStream_t s, const EnsBatch<T>& b, int count
   for (int i = 0; i < count; ++i) wgs = std::max(wgs, b.a[i].K * b.a[i].P);
   bool tap = false;                     // any array of the batch with neuron taps: the tapped twin (it tests a.tap per array)
   for (int i = 0; i < count; ++i) tap = tap || b.a[i].tap != nullptr;
+  bool drv = false;                     // any array with drive columns: the driven kernel (it loops over a.drv_m per array)
+  for (int i = 0; i < count; ++i) drv = drv || b.a[i].drv_m > 0;
   const dim3 grid((unsigned)wgs, (unsigned)count), block(256);
   switch (a.dout) {
 #define SSN_CASE(D)                                                                                  \
   case D:                                                                                            \
-    if (tap) hipLaunchKernelGGL((k_ensarray<T, DIN, D, MODE, true>), grid, block, 0, s, b);          \
+    if (drv) hipLaunchKernelGGL((k_ensarray_drv<T, DIN, D, MODE>), grid, block, 0, s, b);            \
+    else if (tap) hipLaunchKernelGGL((k_ensarray<T, DIN, D, MODE, true>), grid, block, 0, s, b);          \
     else hipLaunchKernelGGL((k_ensarray<T, DIN, D, MODE>), grid, block, 0, s, b);                    \
     break;
     SSN_CASE(1) SSN_CASE(2) SSN_CASE(3) SSN_CASE(4) SSN_CASE(5) SSN_CASE(6) SSN_CASE(7) SSN_CASE(8)

@@ -76,6 +76,12 @@ struct EnsArgs {
   T tap_amp;
   T* tap_sig;
   T* tap_rows;
+  // neuron-input drive columns (EnsembleArray.add_neuron_input, Connection(gate, member.neurons)): drv_m columns per ensemble,
+  // J += sum_j drv_w[k][j][i] * scalar_j.  drv_src[(k * drv_m + j) * 2 ...] = signal offset of scalar j (-1: unused slot, 0),
+  // 1 if it is read from this timestep's row of the block buffer (a pre-stage signal of a fused core, xrows) and not from sig.
+  int drv_m;                       // 0: an array without drive columns
+  const T* drv_w;                  // [K][drv_m][n_pad], the layout of enc
+  const int* drv_src;              // [K][drv_m][2]
 };
 
 // Finish of a fused recurrent ensemble array: one thread per decoded row (k, r):
@@ -287,6 +293,7 @@ struct GlueBlock { int op; int chunk; };        // micro-operator index (into Ro
 // needs no barrier and no launch of its own when the same thread handles the same index in program order.
 struct RoundEntry { int kind; int first; int gx; int gy; const void* args; int lo; int cnt; };   // blocks [lo, lo + cnt) of the gx x gy grid
 constexpr int MAX_ROUND_ENTRIES = 96;
+constexpr int ENS_DRIVE_MAX = 4;              // neuron-input drive columns per ensemble (EnsArgs::drv_m; ssn_drive_desc.m)
 constexpr int ENS_SMALL_PER_WAVE = 4;         // small ensembles one wave of ens_small_body steps (16 per workgroup; 6: no gain - 98.3 vs 97.8 us per SLAM timestep; 8 costs k_round a 73rd VGPR)
 constexpr int VOJA_ROWS_PER_WAVE = 8;         // rows of the encoder matrix one wave of the Voja body looks at (32 per workgroup)
 constexpr int SOLO_MAX_MEMBERS = 24;         // members of a serial chain (their descriptors are staged in LDS)

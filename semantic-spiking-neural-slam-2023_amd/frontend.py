@@ -578,11 +578,25 @@ class EnsembleArray(Network):
                 ed = ens_dimensions
                 self._input_conns.append(Connection(self.input[i * ed:(i + 1) * ed], e, synapse=None))
                 self.ea_ensembles.append(e)
+        self.neuron_input = None
         self.output = self.add_output("output", function=None)
 
     @property
     def dimensions(self):
         return self.n_ensembles * self.dimensions_per_ensemble
+
+    def add_neuron_input(self):
+        """``nengo.networks.EnsembleArray.add_neuron_input``: a passthrough node as wide as all neurons of the array, linked
+        to each member's neurons without a synapse (the way nengo models gate, inhibit or reset an array).  The builder
+        sees through the node: what is connected into it becomes drive columns of the array operator."""
+        if self.neuron_input is not None:
+            return self.neuron_input
+        n = self.n_neurons_per_ensemble
+        with self:
+            self.neuron_input = Node(size_in=n * self.n_ensembles, label="neuron_input")
+            for i, e in enumerate(self.ea_ensembles):
+                Connection(self.neuron_input[i * n:(i + 1) * n], e.neurons, synapse=None)
+        return self.neuron_input
 
     def add_output(self, name, function, synapse=None, **conn_kwargs):
         ed = self.dimensions_per_ensemble

@@ -61,7 +61,11 @@ def pack_model(model, dtype, device=0, steps_per_graph=0, block_steps=0, flags=0
     # as records in one more buffer, behind the model's own
     tap_rows = [(j, k, first, count, dst, o["tap_amp"]) for j, o in enumerate(model.ops) if o["kind"] == "ensarray"
                 for k, first, count, dst in o.get("taps", ())]
-    bufs = (_lib.BufferDesc * max(1, len(model.buffers) + bool(tap_rows)))()
+    # their neuron-input drive columns likewise: one record per driven operator, in a buffer found by its kind (in front of the
+    # taps buffer, which stays the last entry)
+    drive_rows = [(j, o["drive"]["m"], o["drive"]["w"], o["drive"]["src"]) for j, o in enumerate(model.ops)
+                  if o["kind"] == "ensarray" and "drive" in o]
+    bufs = (_lib.BufferDesc * max(1, len(model.buffers) + bool(drive_rows) + bool(tap_rows)))()
     for i, b in enumerate(model.buffers):
         if b.dtype.kind in "iu":
             arr = np.ascontiguousarray(b, dtype=np.int32)
@@ -166,8 +170,16 @@ def pack_model(model, dtype, device=0, steps_per_graph=0, block_steps=0, flags=0
     taps = (_lib.TapDesc * max(1, len(tap_rows)))()
     for t, (j, k, first, count, dst, amp) in zip(taps, tap_rows):
         t.op, t.k, t.first, t.count, t.dst, t.amp = int(j), int(k), int(first), int(count), int(dst), float(amp)
+    drives = (_lib.DriveDesc * max(1, len(drive_rows)))()
+    for d, (j, dm, w_buf, src_buf) in zip(drives, drive_rows):
+        d.op, d.m, d.w_buf, d.src_buf = int(j), int(dm), int(w_buf), int(src_buf)
+    if drive_rows:
+        db = bufs[desc.n_buffers]
+        db.data, db.count, db.kind = C.addressof(drives), len(drive_rows), _lib.SSN_BUF_DRIVES
+        desc.n_buffers += 1
+    keep.append(drives)
     if tap_rows:
-        tb = bufs[len(model.buffers)]
+        tb = bufs[desc.n_buffers]
         tb.data, tb.count, tb.kind = C.addressof(taps), len(tap_rows), _lib.SSN_BUF_TAPS
         desc.n_buffers += 1
     desc.n_taps = len(tap_rows)

@@ -93,6 +93,42 @@ enum ItemType { IT_PROGRAM = 0, IT_ENS, IT_MATVEC, IT_NEURONS, IT_PES, IT_VOJA, 
                 IT_MATVEC_NEURONS,  // (round plan) a dense population's encoder product with the neuron update in its epilogue
                 IT_NONE };          // (round plan) an operator that was folded into another one
 
+// What the planner asks about a micro-operator kind (ssn::MicroKind): one row per kind, one flag per question.  What a kind
+// reads and writes is Sim::micro_access; every "is it one of these kinds" is a lookup here.
+enum MicroKindFlag {
+  MK_SAME_THREAD = 1,   // element-wise in a program, element p of a range on thread (p - origin) mod 1024: follows an operator it depends on
+                        // without a barrier when their origins agree (push_micro); a glue member of a serial chain (solo_lat)
+  MK_VECOPS = 2,        // may move into the grid-wide head of the item plan (k_vecops)
+  MK_CUT = 4,           // cut at the range endpoints of the other operators (split_micro)
+  MK_CHAIN = 8,         // may join a chain of element-aligned operators (chainable)
+  MK_GLUE_ROW = 16,     // a glue block takes GLUE_ROWS rows of it, not GLUE_CHUNK elements (emit)
+  MK_BATCH_EW = 32,     // time-batched stage: element-wise, shares a launch with its neighbours (batch_hazard, run_batch)
+  MK_BATCH_R = 64,      // time-batched stage: reads src
+  MK_BATCH_W = 128,     // time-batched stage: writes dst
+  MK_BATCH_PRODUCT = 256 // time-batched stage: a matrix product - reads `cols` elements of src, not `len` (batch_read_len, run_batch)
+};
+// (a kind appended to ssn::MicroKind needs its row below: without one it would read as "no flags")
+static_assert(ssn::M_LINCOMB == 17, "MICRO_KINDS has a row for every MicroKind up to M_LINCOMB: add the new kind's");
+struct MicroKindTable {
+  unsigned short f[ssn::M_LINCOMB + 1] = {};
+  constexpr MicroKindTable() {
+    f[ssn::M_FILL] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN | MK_BATCH_EW | MK_BATCH_W;
+    f[ssn::M_AXPY_INC] = f[ssn::M_AXPY_SET] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN | MK_BATCH_EW | MK_BATCH_R | MK_BATCH_W;
+    f[ssn::M_LOWPASS] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN | MK_BATCH_R | MK_BATCH_W;
+    f[ssn::M_TABLE] = MK_SAME_THREAD | MK_VECOPS | MK_CHAIN | MK_BATCH_EW | MK_BATCH_W;
+    f[ssn::M_ROW_IN] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN;
+    f[ssn::M_ROW_OUT] = MK_SAME_THREAD | MK_CUT | MK_CHAIN;
+    f[ssn::M_PROBE] = MK_SAME_THREAD | MK_CHAIN | MK_BATCH_EW | MK_BATCH_R;
+    f[ssn::M_LINCOMB] = MK_CUT | MK_CHAIN;
+    f[ssn::M_REDUCE_SET] = f[ssn::M_REDUCE_INC] = MK_CHAIN | MK_GLUE_ROW;
+    f[ssn::M_MATVEC_INC] = f[ssn::M_MATVEC_SET] = MK_GLUE_ROW | MK_BATCH_R | MK_BATCH_W | MK_BATCH_PRODUCT;
+    f[ssn::M_ENS_FINISH] = MK_GLUE_ROW;
+    // M_GATE, M_ARGMAX_GATHER, M_STEP_END: none
+  }
+};
+constexpr MicroKindTable MICRO_KINDS;
+constexpr bool kind_is(int kind, int flag) { return kind > 0 && kind <= ssn::M_LINCOMB && (MICRO_KINDS.f[kind] & flag) != 0; }
+
 // Plan options: ssn_model_desc.flags and the environment knobs, read once at ssn_create and constant for the simulator's
 // life.  PlanOptions::read is the only caller of getenv in the library.  One row per knob: how the variable is read, the
 // member, the variable, the default, the meaning ("Environment switches", lists the same rows).
@@ -253,11 +289,13 @@ struct Sim final : ssn_sim {
   using MOp = ssn::MicroOp<T>;
   static constexpr int VW = 16 / sizeof(T);
 
+  struct TapSet;
   struct DriveSet;
   struct Item {
     int type = IT_PROGRAM;
     int op_begin = 0, op_count = 0;          // program: range in d_mops
     ssn::EnsArgs<T> ens;
+    const TapSet* taps = nullptr;            // IT_ENS: the operator's neuron taps, if it has any (an entry of tap_sets)
     const DriveSet* drv = nullptr;           // IT_ENS: the operator's drive columns, if it has any (an entry of drive_sets)
     ssn::FinishArgs<T> fin;
     bool dominant = false;
@@ -313,7 +351,6 @@ struct Sim final : ssn_sim {
   // from the row
   struct DriveSet { ssn_drive_desc rec; std::vector<int32_t> src; int* d_tab = nullptr; int* d_tab_rows = nullptr; };
   std::map<int, DriveSet> drive_sets;         // operator index -> its drive columns
-  const ssn_op_desc* ops_base = nullptr;      // (the model's operator array: valid during ssn_create only)
   std::set<int> sparse_w;                     // decoder buffers multiplied with a LIF spike vector
   std::set<int> learned_w;                    // matrices a learning rule (PES, Voja) updates
   std::vector<std::pair<int64_t, std::pair<int*, int*>>> spike_lists;   // spike signal offset -> (list, count)
@@ -431,6 +468,21 @@ struct Sim final : ssn_sim {
     HIPCHK(hipMalloc((void**)p, (size_t)bytes));
     device_bytes += bytes;
     if (own) owned.push_back((void*)*p);
+    return SSN_OK;
+  }
+  // A host table on the device: owned memory for n elements of P, filled from `src` / with zeros (n = 0: dmalloc's 16 bytes).
+  template <typename P>
+  int dupload(P** p, const P* src, int64_t n) {
+    CHK(dmalloc(p, n * (int64_t)sizeof(P)));
+    if (n > 0) HIPCHK(hipMemcpy(*p, src, (size_t)n * sizeof(P), hipMemcpyHostToDevice));
+    return SSN_OK;
+  }
+  template <typename P>
+  int dupload(P** p, const std::vector<P>& v) { return dupload(p, v.data(), (int64_t)v.size()); }
+  template <typename P>
+  int dzeros(P** p, int64_t n) {
+    CHK(dmalloc(p, n * (int64_t)sizeof(P)));
+    if (n > 0) HIPCHK(hipMemset(*p, 0, (size_t)n * sizeof(P)));
     return SSN_OK;
   }
 
@@ -617,7 +669,6 @@ struct Sim final : ssn_sim {
   // Taps (ABI 9): every range inside its array and inside the signal vector, one tap per ensemble, tap signals disjoint
   // from each other and from every decoded row of an array.
   int read_taps(const ssn_model_desc* m) {
-    ops_base = m->ops;
     for (int i = 0; i < m->n_buffers; ++i)
       if (m->buffers[i].kind == SSN_BUF_TAPS && (m->n_taps <= 0 || i != m->n_buffers - 1))
         return fail(SSN_EINVAL, "buffer %d: tap records belong in the last buffer of a model with n_taps > 0", i);
@@ -665,15 +716,13 @@ struct Sim final : ssn_sim {
         int* row = tab.data() + (size_t)t.k * 4;
         row[0] = (int)t.first; row[1] = (int)t.count; row[2] = (int)t.dst; row[3] = (int)q;
       }
-      CHK(dmalloc(&kv.second.d_tab, K * 16));
-      HIPCHK(hipMemcpy(kv.second.d_tab, tab.data(), (size_t)K * 16, hipMemcpyHostToDevice));
+      CHK(dupload(&kv.second.d_tab, tab));
     }
     return SSN_OK;
   }
   // Drive columns (ABI 10): the records are found by the buffer's kind; every record names a core ensemble array (one record per
   // operator), 1 <= m <= 4, a real buffer of K * m * n weights and an int32 buffer of K * m sources inside the signal vector or -1.
   int read_drives(const ssn_model_desc* m) {
-    ops_base = m->ops;
     int at = -1;
     for (int i = 0; i < m->n_buffers; ++i)
       if (m->buffers[i].kind == SSN_BUF_DRIVES) {
@@ -718,28 +767,19 @@ struct Sim final : ssn_sim {
         tab[2 * j] = rows[2 * j] = ds.src[j];
         for (auto& r : pre_to_core) if (ds.src[j] >= r.lo && ds.src[j] < r.hi) rows[2 * j + 1] = 1;
       }
-      CHK(dmalloc(&ds.d_tab, (int64_t)tab.size() * 4));
-      CHK(dmalloc(&ds.d_tab_rows, (int64_t)rows.size() * 4));
-      HIPCHK(hipMemcpy(ds.d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(ds.d_tab_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+      CHK(dupload(&ds.d_tab, tab));
+      CHK(dupload(&ds.d_tab_rows, rows));
     }
     return SSN_OK;
   }
-  const DriveSet* drives_of(const ssn_op_desc& o) const {
-    if (drive_sets.empty() || !ops_base) return nullptr;
-    auto it = drive_sets.find((int)(&o - ops_base));
+  // the drive columns / the taps of operator `op` of the model (nullptr: it has none)
+  const DriveSet* drives_of(int op) const {
+    auto it = drive_sets.find(op);
     return it == drive_sets.end() ? nullptr : &it->second;
   }
-  const TapSet* taps_of(const ssn_op_desc& o) const {
-    if (tap_sets.empty() || !ops_base) return nullptr;
-    auto it = tap_sets.find((int)(&o - ops_base));
+  const TapSet* taps_of(int op) const {
+    auto it = tap_sets.find(op);
     return it == tap_sets.end() ? nullptr : &it->second;
-  }
-  // the signal ranges an ensemble array's taps write (data hazards of the item and round plans)
-  const TapSet* taps_of(const ssn::EnsArgs<T>& a) const {
-    if (!a.tap) return nullptr;
-    for (auto& kv : tap_sets) if (kv.second.d_tab == a.tap) return &kv.second;
-    return nullptr;
   }
 
   int create(const ssn_model_desc* m) {
@@ -878,8 +918,7 @@ struct Sim final : ssn_sim {
       Buf& b = bufs[i];
       if (b.kind == SSN_BUF_TAPS || b.kind == SSN_BUF_DRIVES) continue;       // (host-side records: read_taps, read_drives)
       if (b.kind == SSN_BUF_I32) {
-        CHK(dmalloc((int32_t**)&b.d, b.count * 4));
-        HIPCHK(hipMemcpy(b.d, m->buffers[i].data, (size_t)b.count * 4, hipMemcpyHostToDevice));
+        CHK(dupload((int32_t**)&b.d, (const int32_t*)m->buffers[i].data, b.count));
       } else {
         const int64_t elems = b.dec_DP ? (int64_t)b.dec_K * b.ld * b.dec_DP : (b.transposed ? b.cols * b.ldt : b.rows * b.ld);
         CHK(dmalloc((T**)&b.d, elems * (int64_t)sizeof(T)));
@@ -888,15 +927,13 @@ struct Sim final : ssn_sim {
       }
     }
     CHK(upload(sig_init.data(), sig, 1, n_sig, n_sig));
-    CHK(dmalloc(&d_ctx, sizeof(ssn::StepCtx)));
-    HIPCHK(hipMemset(d_ctx, 0, sizeof(ssn::StepCtx)));
+    CHK(dzeros(&d_ctx, 1));
     // tables and probes
     tables.assign(m->n_tables, ssn::TableSlot{nullptr, nullptr, 0, 0, 0, 0});
     table_rows.resize((size_t)m->n_tables);
     table_idx.resize((size_t)m->n_tables);
     staged.resize((size_t)m->n_tables);
-    CHK(dmalloc(&d_tables, std::max<int64_t>(1, m->n_tables) * (int64_t)sizeof(ssn::TableSlot)));
-    if (m->n_tables) HIPCHK(hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(ssn::TableSlot), hipMemcpyHostToDevice));
+    CHK(dupload(&d_tables, tables));
     probes.assign(m->probes, m->probes + m->n_probes);
     for (auto& p : probes) {
       if (p.every < 1) return fail(SSN_EINVAL, "probe 'every' must be >= 1");
@@ -905,8 +942,7 @@ struct Sim final : ssn_sim {
     pslots.assign(m->n_probes, ssn::ProbeSlot{nullptr, 1, 0, 0});
     probe_store.resize((size_t)m->n_probes);
     for (int i = 0; i < m->n_probes; ++i) pslots[i].every = probes[i].every;
-    CHK(dmalloc(&d_pslots, std::max<int64_t>(1, m->n_probes) * (int64_t)sizeof(ssn::ProbeSlot)));
-    if (m->n_probes) HIPCHK(hipMemcpy(d_pslots, pslots.data(), pslots.size() * sizeof(ssn::ProbeSlot), hipMemcpyHostToDevice));
+    CHK(dupload(&d_pslots, pslots));
     exchange.assign(m->exchange, m->exchange + (m->n_exchange > 0 ? m->n_exchange : 0));
     phased = !exchange.empty();
     for (auto& r : exchange) CHK(check_range(r.lo, r.hi - r.lo, "exchange"));
@@ -957,7 +993,7 @@ struct Sim final : ssn_sim {
     a.P = (n_vec + a.chunk_vec - 1) / a.chunk_vec;
   }
 
-  void fill_ens_args(const ssn_op_desc& o, ssn::EnsArgs<T>& a) {
+  void fill_ens_args(const ssn_op_desc& o, const TapSet* ts, const DriveSet* ds, ssn::EnsArgs<T>& a) {
     a = ssn::EnsArgs<T>{};
     a.K = (int)o.i[1]; a.n = (int)o.i[2]; a.din = (int)o.i[3]; a.dout = (int)o.i[4];
     a.n_pad = (int)bufs[o.i[5]].ld;
@@ -968,8 +1004,8 @@ struct Sim final : ssn_sim {
     a.xrows = nullptr; a.n_sig = n_sig; a.ctx = d_ctx; a.n_rec = 0;
     a.fast = ens_fast(o) ? (ens_sparse(o) ? 1 : 2) : 0;
     a.defer = 0; a.sub = 0; a.partials_stride = 0;
-    if (const TapSet* ts = taps_of(o)) { a.tap = ts->d_tab; a.tap_amp = (T)ts->amp; a.tap_sig = sig; a.tap_rows = nullptr; }
-    if (const DriveSet* ds = drives_of(o)) { a.drv_m = ds->rec.m; a.drv_w = (const T*)bufs[ds->rec.w_buf].d; a.drv_src = ds->d_tab; }
+    if (ts) { a.tap = ts->d_tab; a.tap_amp = (T)ts->amp; a.tap_sig = sig; a.tap_rows = nullptr; }
+    if (ds) { a.drv_m = ds->rec.m; a.drv_w = (const T*)bufs[ds->rec.w_buf].d; a.drv_src = ds->d_tab; }
     ens_chunking(a);
   }
 
@@ -1016,8 +1052,7 @@ struct Sim final : ssn_sim {
   int dft_table(int64_t key, const std::vector<float2>& h, float2** out) {
     for (auto& t : dft_tables) if (t.first == key) { *out = t.second; return SSN_OK; }
     float2* d = nullptr;
-    CHK(dmalloc(&d, (int64_t)h.size() * (int64_t)sizeof(float2)));
-    HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
+    CHK(dupload(&d, h));
     dft_tables.push_back({key, d});
     *out = d;
     return SSN_OK;
@@ -1084,10 +1119,8 @@ struct Sim final : ssn_sim {
             g2[(((size_t)q * 2 + part) * KS3 + ks) * 64 + l] = (float)v;
           }
     float* d1 = nullptr; float* d2 = nullptr;
-    CHK(dmalloc(&d1, (int64_t)g1.size() * 4));
-    CHK(dmalloc(&d2, (int64_t)g2.size() * 4));
-    HIPCHK(hipMemcpy(d1, g1.data(), g1.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d2, g2.data(), g2.size() * 4, hipMemcpyHostToDevice));
+    CHK(dupload(&d1, g1));
+    CHK(dupload(&d2, g2));
     dft_tables.push_back({key1, (float2*)d1}); dft_tables.push_back({key2, (float2*)d2});
     *g1_out = d1; *g2_out = d2;
     return SSN_OK;
@@ -1272,8 +1305,7 @@ struct Sim final : ssn_sim {
   // Taps of the whole-block kernel: which workgroups have one (tap_slot[k], -1: none) and, per tapped ensemble, the
   // destination signal of every column of its row in the DEVICE's neuron order (-1: not tapped) - the order may be a
   // permutation of the caller's (reorder_block_neurons), so the kernel looks the destination up instead of computing it.
-  int block_taps(const ssn_op_desc& eo) {
-    const TapSet* ts = taps_of(eo);
+  int block_taps(const ssn_op_desc& eo, const TapSet* ts) {
     if (!ts) return SSN_OK;
     const int64_t K = eo.i[1], n = eo.i[2], row = blk.n_pad;
     const Buf& eb = bufs[(size_t)eo.i[5]];
@@ -1287,32 +1319,30 @@ struct Sim final : ssn_sim {
       }
     }
     int* d_slot = nullptr; int* d_col = nullptr;
-    CHK(dmalloc(&d_slot, K * 4));
-    CHK(dmalloc(&d_col, (int64_t)col.size() * 4));
-    HIPCHK(hipMemcpy(d_slot, slot.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_col, col.data(), col.size() * 4, hipMemcpyHostToDevice));
+    CHK(dupload(&d_slot, slot));
+    CHK(dupload(&d_col, col));
     blk.tap_slot = d_slot; blk.tap_col = d_col; blk.tap_amp = (T)ts->amp;
     return SSN_OK;
   }
 
   // Core stage == one recurrent ensemble array (the path integrator's VCO array): x assembled in the
   // kernel prologue, decoded rows / synapse update / hand-off / step counter in one barrier-free finish
-  // kernel.  Returns false (and plans nothing) when the core does not have that shape.
-  bool try_fused_core(const ssn_model_desc* m, int* rc) {
-    *rc = SSN_OK;
-    if (!bsig) return false;
-    for (auto& p : probes) if (p.stage == 1) return false;
+  // kernel.  *fused stays false (and nothing is planned) when the core does not have that shape.
+  int try_fused_core(const ssn_model_desc* m, bool* fused) {
+    *fused = false;
+    if (!bsig) return SSN_OK;
+    for (auto& p : probes) if (p.stage == 1) return SSN_OK;
     int ens_i = -1;
     std::vector<int> axpys, lows;
     for (int i = 0; i < m->n_ops; ++i) {
       const ssn_op_desc& o = m->ops[i];
       if (o.stage != 1) continue;
-      if (o.kind == SSN_OP_ENSARRAY) { if (ens_i >= 0) return false; ens_i = i; }
+      if (o.kind == SSN_OP_ENSARRAY) { if (ens_i >= 0) return SSN_OK; ens_i = i; }
       else if (o.kind == SSN_OP_AXPY && o.i[3] == 0) axpys.push_back(i);
       else if (o.kind == SSN_OP_LOWPASS) lows.push_back(i);
-      else return false;
+      else return SSN_OK;
     }
-    if (ens_i < 0 || axpys.size() > 4) return false;
+    if (ens_i < 0 || axpys.size() > 4) return SSN_OK;
     const ssn_op_desc& eo = m->ops[ens_i];
     const int64_t K = eo.i[1], din = eo.i[3], dout = eo.i[4];
     const int64_t x0 = eo.i[0], x1 = eo.i[0] + K * din;
@@ -1320,20 +1350,21 @@ struct Sim final : ssn_sim {
       for (auto& r : rs) if (lo >= r.lo && hi <= r.hi) return true;
       return false;
     };
-    if (!inside(x0, x1, pre_to_core)) return false;
+    if (!inside(x0, x1, pre_to_core)) return SSN_OK;
     for (int i : axpys) {                       // recurrent terms must land inside pre-stage-provided inputs
       const ssn_op_desc& o = m->ops[i];
-      if (!inside(o.i[0], o.i[0] + o.i[2], pre_to_core)) return false;
+      if (!inside(o.i[0], o.i[0] + o.i[2], pre_to_core)) return SSN_OK;
     }
     // drive columns: the fused prologue reads their scalars from the timestep's block row - every source must be a pre-stage
     // signal that no operator of the core adds to (the recurrent terms are folded into x only)
-    const DriveSet* const drv = drives_of(eo);
+    const TapSet* const taps = taps_of(ens_i);
+    const DriveSet* const drv = drives_of(ens_i);
     if (drv)
       for (int32_t sx : drv->src) {
         if (sx < 0) continue;
-        if (!inside(sx, sx + 1, pre_to_core)) return false;
-        for (int i : axpys) if (sx >= m->ops[i].i[0] && sx < m->ops[i].i[0] + m->ops[i].i[2]) return false;
-        for (int i : lows) if (sx >= m->ops[i].i[0] && sx < m->ops[i].i[0] + m->ops[i].i[2]) return false;
+        if (!inside(sx, sx + 1, pre_to_core)) return SSN_OK;
+        for (int i : axpys) if (sx >= m->ops[i].i[0] && sx < m->ops[i].i[0] + m->ops[i].i[2]) return SSN_OK;
+        for (int i : lows) if (sx >= m->ops[i].i[0] && sx < m->ops[i].i[0] + m->ops[i].i[2]) return SSN_OK;
       }
     const int32_t* didx = (const int32_t*)m->buffers[eo.i[8]].data;
     std::vector<int> row_of((size_t)n_sig, -1);
@@ -1348,10 +1379,10 @@ struct Sim final : ssn_sim {
         if (row < 0) {
           // no local row feeds this filter input (VCO owned by another rank): input and state stay 0,
           // provided nothing else writes that signal
-          if (inside(o.i[1] + e, o.i[1] + e + 1, pre_to_core) || sig_init[(size_t)(o.i[1] + e)] != 0.0) return false;
+          if (inside(o.i[1] + e, o.i[1] + e + 1, pre_to_core) || sig_init[(size_t)(o.i[1] + e)] != 0.0) return SSN_OK;
           continue;
         }
-        if (lp_state[(size_t)row] >= 0) return false;
+        if (lp_state[(size_t)row] >= 0) return SSN_OK;
         lp_state[(size_t)row] = (int)(o.i[0] + e);
         lp_a[(size_t)row] = o.f[0];
         lp_b[(size_t)row] = (1.0 - o.f[0]) * o.f[1];
@@ -1394,6 +1425,23 @@ struct Sim final : ssn_sim {
         }
       }
     }
+    // the filter tables of either plan: per decoded row its filter state, coefficients and hand-off flag; with_x: per input
+    // the row whose state feeds it back, and that term's gain
+    const int64_t nr = K * dout;
+    struct FilterTabs { int* lp = nullptr; T* a = nullptr; T* b = nullptr; unsigned char* ro = nullptr; int* xrow = nullptr; T* xalpha = nullptr; };
+    auto filter_tables = [&](FilterTabs& t, bool with_x) -> int {
+      CHK(dupload(&t.lp, lp_state));
+      CHK(dmalloc(&t.a, nr * (int64_t)sizeof(T)));
+      CHK(dmalloc(&t.b, nr * (int64_t)sizeof(T)));
+      CHK(dupload(&t.ro, rowout));
+      CHK(upload(lp_a.data(), t.a, 1, nr, nr));
+      CHK(upload(lp_b.data(), t.b, 1, nr, nr));
+      if (!with_x) return SSN_OK;
+      CHK(dupload(&t.xrow, xrow));
+      CHK(dmalloc(&t.xalpha, K * din * (int64_t)sizeof(T)));
+      CHK(upload(xalpha.data(), t.xalpha, 1, K * din, K * din));
+      return SSN_OK;
+    };
     // ---- plan A: the ensembles are independent inside a block -> one k_ens_block launch per block -----
     int blk_threads = 0, blk_tpb = 0, blk_npt = 0, blk_lds = 0;
     // (One workgroup steps one ensemble.  Splitting an ensemble over P workgroups that exchange partial sums through L2
@@ -1421,27 +1469,15 @@ struct Sim final : ssn_sim {
     // (a driven array is not eligible: k_ens_block has no drive columns)
     if (defer && !drv && !opt.has(SSN_PLAN_NO_BLOCK_KERNEL) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt)) &&
         ssn::ens_block_supported<T>((int)din, (int)dout, split_P > 1 ? n_member : (int)eo.i[2], opt.block_variant.v, &blk_threads, &blk_tpb, &blk_npt, &blk_lds)) {
-      const int64_t nr = K * dout;
-      int* d_lp = nullptr; T* d_a = nullptr; T* d_b = nullptr; unsigned char* d_ro = nullptr; int* d_xrow = nullptr; T* d_xalpha = nullptr;
-      if ((*rc = dmalloc(&d_lp, nr * 4)) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_a, nr * (int64_t)sizeof(T))) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_b, nr * (int64_t)sizeof(T))) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_ro, nr)) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_xrow, (int64_t)K * din * 4)) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_xalpha, (int64_t)K * din * (int64_t)sizeof(T))) != SSN_OK) return true;
-      hipMemcpy(d_lp, lp_state.data(), (size_t)nr * 4, hipMemcpyHostToDevice);
-      hipMemcpy(d_ro, rowout.data(), (size_t)nr, hipMemcpyHostToDevice);
-      hipMemcpy(d_xrow, xrow.data(), (size_t)(K * din) * 4, hipMemcpyHostToDevice);
-      if ((*rc = upload(lp_a.data(), d_a, 1, nr, nr)) != SSN_OK) return true;
-      if ((*rc = upload(lp_b.data(), d_b, 1, nr, nr)) != SSN_OK) return true;
-      if ((*rc = upload(xalpha.data(), d_xalpha, 1, K * din, K * din)) != SSN_OK) return true;
+      FilterTabs ft;
+      CHK(filter_tables(ft, true));
       ssn::EnsArgs<T> ea;
-      fill_ens_args(eo, ea);
+      fill_ens_args(eo, taps, drv, ea);
       blk = ssn::BlockArgs<T>{};
       blk.enc = ea.enc; blk.bias = ea.bias; blk.dec = ea.dec; blk.S = ea.V;
       blk.xrows = bsig; blk.bsig = bsig; blk.sig = sig; blk.sig_w = sig;
-      blk.didx = (const int*)bufs[eo.i[8]].d; blk.lp_state = d_lp; blk.lp_a = d_a; blk.lp_b = d_b;
-      blk.xrow = d_xrow; blk.xalpha = d_xalpha; blk.rowout = d_ro;
+      blk.didx = (const int*)bufs[eo.i[8]].d; blk.lp_state = ft.lp; blk.lp_a = ft.a; blk.lp_b = ft.b;
+      blk.xrow = ft.xrow; blk.xalpha = ft.xalpha; blk.rowout = ft.ro;
       blk.n_sig = n_sig; blk.x_off = eo.i[0];
       blk.K = ea.K; blk.n = ea.n; blk.n_pad = ea.n_pad; blk.din = ea.din; blk.dout = ea.dout;
       blk.B = 0; blk.row0 = 1; blk.threads = blk_threads; blk.tpb = blk_tpb; blk.npt = blk_npt; blk.enc_lds = blk_lds;
@@ -1450,31 +1486,28 @@ struct Sim final : ssn_sim {
       blk.P = split_P; blk.n_member = n_member; blk.xslots = nullptr; blk.xerr = nullptr;
       {
         unsigned long long* d_ss = nullptr;
-        if ((*rc = dmalloc(&d_ss, 16)) != SSN_OK) return true;
-        hipMemset(d_ss, 0, 16);
+        CHK(dzeros(&d_ss, 2));
         blk.slot_stats = d_ss;
       }
       if (split_P > 1) {
         unsigned int* d_x = nullptr; int* d_e = nullptr;
-        if ((*rc = dmalloc(&d_x, (int64_t)3 * K * 64 * 4)) != SSN_OK) return true;
-        if ((*rc = dmalloc(&d_e, 16)) != SSN_OK) return true;
-        hipMemset(d_e, 0, 16);
+        CHK(dmalloc(&d_x, (int64_t)3 * K * 64 * 4));
+        CHK(dzeros(&d_e, 4));
         blk.xslots = d_x; blk.xerr = d_e;
       }
       dom_units = (int64_t)ea.K * ea.n * block;
       dom_bytes = (double)dom_units * (ea.din + ea.dout + 5) * sizeof(T);
-      fused_core = fused_block = true;
+      *fused = fused_core = fused_block = true;
       // (only worth anything with a kernel built with SSN_BLOCK_SKIP = 1 or 2 - both measured slower than the plain loop, round 4 -
       //  so the neuron order is the caller's unless SSN_BLOCK_SORT=1 asks for the slot order)
       if (sizeof(T) == 4 && split_P == 1 && opt.block_sort)
-        *rc = reorder_block_neurons(m, eo, blk_npt == 2 ? blk_threads : blk_tpb, blk_npt);
-      if (*rc == SSN_OK) *rc = block_taps(eo);
-      return true;
+        CHK(reorder_block_neurons(m, eo, blk_npt == 2 ? blk_threads : blk_tpb, blk_npt));
+      return block_taps(eo, taps);
     }
     // ---- plan B: [k_ensarray (fused prologue), k_ens_finish] ------------------------------------------
     Item it; it.type = IT_ENS;
-    fill_ens_args(eo, it.ens);
-    it.drv = drv;
+    fill_ens_args(eo, taps, drv, it.ens);
+    it.taps = taps; it.drv = drv;
     ssn::EnsArgs<T>& a = it.ens;
     a.xrows = bsig;
     if (a.tap) a.tap_rows = bsig;      // (a fused core has no hand-off operator: the kernel writes the post stage's rows itself)
@@ -1489,60 +1522,44 @@ struct Sim final : ssn_sim {
       ++a.n_rec;
     }
     a.partials_stride = (int64_t)a.K * a.P * a.dout;
-    if ((*rc = dmalloc(&a.partials, 2 * a.partials_stride * (int64_t)sizeof(T))) != SSN_OK) return true;
-    hipMemset(a.partials, 0, (size_t)(2 * a.partials_stride) * sizeof(T));
+    CHK(dzeros(&a.partials, 2 * a.partials_stride));
     it.dominant = true;
     dom_units = (int64_t)a.K * a.n;
     dom_bytes = (double)dom_units * (a.din + a.dout + 5) * sizeof(T);
     Item fi; fi.type = IT_FINISH;
     ssn::FinishArgs<T>& f = fi.fin;
     f = ssn::FinishArgs<T>{};
-    const int64_t nr = K * dout;
-    int* d_lp = nullptr; T* d_a = nullptr; T* d_b = nullptr; unsigned char* d_ro = nullptr; unsigned int* d_ticket = nullptr;
-    if ((*rc = dmalloc(&d_lp, nr * 4)) != SSN_OK) return true;
-    if ((*rc = dmalloc(&d_a, nr * (int64_t)sizeof(T))) != SSN_OK) return true;
-    if ((*rc = dmalloc(&d_b, nr * (int64_t)sizeof(T))) != SSN_OK) return true;
-    if ((*rc = dmalloc(&d_ro, nr)) != SSN_OK) return true;
-    if ((*rc = dmalloc(&d_ticket, 64)) != SSN_OK) return true;
-    hipMemcpy(d_lp, lp_state.data(), (size_t)nr * 4, hipMemcpyHostToDevice);
-    hipMemcpy(d_ro, rowout.data(), (size_t)nr, hipMemcpyHostToDevice);
-    hipMemset(d_ticket, 0, 64);
-    if ((*rc = upload(lp_a.data(), d_a, 1, nr, nr)) != SSN_OK) return true;
-    if ((*rc = upload(lp_b.data(), d_b, 1, nr, nr)) != SSN_OK) return true;
-    f.partials = a.partials; f.didx = (const int*)bufs[eo.i[8]].d; f.lp_state = d_lp; f.lp_a = d_a; f.lp_b = d_b;
-    f.rowout = d_ro; f.sig = sig; f.bsig = bsig; f.n_sig = n_sig; f.ctx = d_ctx; f.ticket = d_ticket;
+    FilterTabs ft;                        // (the feedback rows: only the deferred finish reads them)
+    CHK(filter_tables(ft, defer));
+    unsigned int* d_ticket = nullptr;
+    CHK(dzeros(&d_ticket, 16));
+    f.partials = a.partials; f.didx = (const int*)bufs[eo.i[8]].d; f.lp_state = ft.lp; f.lp_a = ft.a; f.lp_b = ft.b;
+    f.rowout = ft.ro; f.sig = sig; f.bsig = bsig; f.n_sig = n_sig; f.ctx = d_ctx; f.ticket = d_ticket;
     f.K = a.K; f.P = a.P; f.dout = a.dout; f.n_blocks = (int)((nr + 255) / 256);
     f.mode = 0; f.fstate = nullptr; f.partials_stride = a.partials_stride; f.lp_has = nullptr;
     if (defer) {
-      int* d_has = nullptr; int* d_xrow = nullptr; T* d_xalpha = nullptr; T* d_fstate = nullptr;
-      if ((*rc = dmalloc(&d_has, nr * 4)) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_xrow, (int64_t)K * din * 4)) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_xalpha, (int64_t)K * din * (int64_t)sizeof(T))) != SSN_OK) return true;
-      if ((*rc = dmalloc(&d_fstate, 2 * nr * (int64_t)sizeof(T))) != SSN_OK) return true;
-      hipMemcpy(d_has, lp_has.data(), (size_t)nr * 4, hipMemcpyHostToDevice);
-      hipMemcpy(d_xrow, xrow.data(), (size_t)(K * din) * 4, hipMemcpyHostToDevice);
-      hipMemset(d_fstate, 0, (size_t)(2 * nr) * sizeof(T));
-      if ((*rc = upload(xalpha.data(), d_xalpha, 1, K * din, K * din)) != SSN_OK) return true;
-      a.defer = 1; a.sub = 0; a.didx = f.didx; a.lp_has = d_has; a.lp_a = d_a; a.lp_b = d_b; a.fstate = d_fstate;
-      a.xrow = d_xrow; a.xalpha = d_xalpha; a.rowout = d_ro; a.bsig = bsig; a.sig_w = sig;
+      int* d_has = nullptr; T* d_fstate = nullptr;
+      CHK(dupload(&d_has, lp_has));
+      CHK(dzeros(&d_fstate, 2 * nr));
+      a.defer = 1; a.sub = 0; a.didx = f.didx; a.lp_has = d_has; a.lp_a = ft.a; a.lp_b = ft.b; a.fstate = d_fstate;
+      a.xrow = ft.xrow; a.xalpha = ft.xalpha; a.rowout = ft.ro; a.bsig = bsig; a.sig_w = sig;
       f.fstate = d_fstate; f.lp_has = d_has;
       fin_flush = f; fin_flush.mode = 1;
       fin_begin = f; fin_begin.mode = 2;
       items.push_back(it);
-      fused_core = fused_defer = true;
-      return true;
+      *fused = fused_core = fused_defer = true;
+      return SSN_OK;
     }
     items.push_back(it);
     items.push_back(fi);
-    fused_core = true;
+    *fused = fused_core = true;
     // the batched stages are planned by plan(); nothing else runs per timestep
-    return true;
+    return SSN_OK;
   }
 
   int plan(const ssn_model_desc* m) {
-    int frc = SSN_OK;
-    const bool fused = !opt.has(SSN_PLAN_NO_FUSED_CORE) && try_fused_core(m, &frc);
-    CHK(frc);
+    bool fused = false;
+    if (!opt.has(SSN_PLAN_NO_FUSED_CORE)) CHK(try_fused_core(m, &fused));
     std::vector<std::vector<MOp>> programs;   // programs in step order
     std::vector<int> item_prog;               // for IT_PROGRAM items: index into programs
     std::vector<MOp> cur;
@@ -1551,25 +1568,18 @@ struct Sim final : ssn_sim {
     // Element-wise micro operators are executed with element p of a range starting at `base` on thread
     // (p - base) mod 1024.  A dependency between two of them therefore needs no workgroup barrier when both map every
     // shared element to the same thread (equal range starts modulo 1024): program order inside the thread suffices.
-    struct EwAcc { long long lo, len; bool w; };
-    auto ew_access = [&](const MOp& m, std::vector<EwAcc>& out) -> bool {
-      switch (m.kind) {
-        case ssn::M_FILL: case ssn::M_TABLE: case ssn::M_ROW_IN: out.push_back({m.dst, m.len, true}); return true;
-        case ssn::M_AXPY_SET: out.push_back({m.src, m.len, false}); out.push_back({m.dst, m.len, true}); return true;
-        case ssn::M_AXPY_INC: case ssn::M_LOWPASS: out.push_back({m.src, m.len, false}); out.push_back({m.dst, m.len, true}); return true;
-        case ssn::M_ROW_OUT: case ssn::M_PROBE: out.push_back({m.src, m.len, false}); return true;
-        default: return false;
-      }
-    };
+    // (Here and for the grid-wide head below, an empty range that lies inside another one counts as touching it: keep_empty.)
     auto level_change_needs_barrier = [&](const MOp& op) -> bool {
-      std::vector<EwAcc> mine;
-      if (!ew_access(op, mine)) return true;
+      if (!kind_is(op.kind, MK_SAME_THREAD)) return true;
+      std::vector<Rng> mine, theirs;
+      micro_access(mine, op, false, true);
       for (size_t q = cur.size(); q-- > 0;) {             // operators since the last barrier
-        std::vector<EwAcc> theirs;
-        if (!ew_access(cur[q], theirs)) return true;
-        for (const EwAcc& x : mine)
-          for (const EwAcc& y : theirs)
-            if ((x.w || y.w) && x.lo < y.lo + y.len && y.lo < x.lo + x.len && ((x.lo - y.lo) % 1024) != 0) return true;
+        if (!kind_is(cur[q].kind, MK_SAME_THREAD)) return true;
+        theirs.clear();
+        micro_access(theirs, cur[q], false, true);
+        for (const Rng& x : mine)
+          for (const Rng& y : theirs)
+            if ((x.w || y.w) && x.lo < y.hi && y.lo < x.hi && ((x.lo - y.lo) % 1024) != 0) return true;
         if (cur[q].barrier) break;
       }
       return false;
@@ -1668,8 +1678,7 @@ struct Sim final : ssn_sim {
           for (int64_t q = 0; q < o.i[2]; ++q)
             terms[(size_t)q] = ssn::LinTerm<T>{(long long)((const int32_t*)m->buffers[o.i[3]].data)[q], (T)((const double*)m->buffers[o.i[4]].data)[q]};
           ssn::LinTerm<T>* d_terms = nullptr;
-          CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, terms.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
-          if (!terms.empty()) HIPCHK(hipMemcpy(d_terms, terms.data(), terms.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
+          CHK(dupload(&d_terms, terms));
           lin_terms[(const void*)d_terms] = terms;
           op.kind = ssn::M_LINCOMB; op.dst = o.i[0]; op.len = o.i[1]; op.i0 = o.i[2]; op.p0 = d_terms;
           op.a = (T)o.f[0]; op.b = T(1); op.c = (T)o.f[1];
@@ -1736,8 +1745,8 @@ struct Sim final : ssn_sim {
           flush();
           Item it; it.type = IT_ENS;
           ssn::EnsArgs<T>& a = it.ens;
-          fill_ens_args(o, a);
-          it.drv = drives_of(o);
+          it.taps = taps_of(i); it.drv = drives_of(i);
+          fill_ens_args(o, it.taps, it.drv, a);
           ens_chunking(a, 2048);
           CHK(dmalloc(&a.partials, (int64_t)a.K * a.P * a.dout * (int64_t)sizeof(T)));
           const int64_t units = (int64_t)a.K * a.n;
@@ -1771,8 +1780,7 @@ struct Sim final : ssn_sim {
             // segmented spike list: every 256-neuron workgroup of k_neurons leaves its spikes as an ordered index list
             const int n_seg = ((int)o.i[2] + 255) / 256;
             CHK(dmalloc(&it.list, (int64_t)n_seg * 256 * 4));
-            CHK(dmalloc(&it.count, (int64_t)n_seg * 4 + 64));
-            HIPCHK(hipMemset(it.count, 0, (size_t)n_seg * 4 + 64));
+            CHK(dzeros(&it.count, (int64_t)n_seg + 16));
             spike_lists.push_back({o.i[1], {it.list, it.count}});
             seg_spikes.push_back(o.i[1]);
           }
@@ -1911,14 +1919,14 @@ struct Sim final : ssn_sim {
       dom_units = (int64_t)a.K * a.n;
       dom_bytes = (double)dom_units * (a.din + a.dout + 5) * sizeof(T);
     }
+    int n_core_ops = 0;
+    for (int i = 0; i < m->n_ops; ++i) n_core_ops += m->ops[i].stage == 1;
+    bool core_probe = false;
+    for (auto& p : probes) core_probe = core_probe || p.stage == 1;
+    core_empty = bsig && n_core_ops == 0 && !core_probe;      // (no launch per timestep then, however the plan below counts)
     round_mode = !fused && !opt.has(SSN_PLAN_NO_ROUNDS);
     if (round_mode) {
       CHK(build_rounds(programs, item_prog));
-      int n_core = 0;
-      for (int i = 0; i < m->n_ops; ++i) n_core += m->ops[i].stage == 1;
-      bool probe_in_core = false;
-      for (auto& p : probes) probe_in_core = probe_in_core || p.stage == 1;
-      core_empty = bsig && n_core == 0 && !probe_in_core;
       if (core_empty) launches_per_step = 0;
       return SSN_OK;
     }
@@ -1962,20 +1970,14 @@ struct Sim final : ssn_sim {
       // The prefix that moves: element-wise operators up to the first barrier that are INDEPENDENT of each other.  Inside
       // a program an operator may follow one it depends on without a barrier when both map every element to the same
       // thread (push_micro); k_vecops maps elements to threads of the whole grid, so such a chain must not move as one.
-      auto reads_src = [](const MOp& m) { return m.kind == ssn::M_AXPY_INC || m.kind == ssn::M_AXPY_SET || m.kind == ssn::M_LOWPASS; };
-      auto overlap = [](long long a, long long al, long long b, long long bl) { return a < b + bl && b < a + al; };
+      std::vector<Rng> moved, mine;                    // what the prefix so far reads and writes
       for (; lv < head.size() && (lv == 0 || !head[lv].barrier); ++lv) {
         const MOp& q = head[lv];
-        const int kd = q.kind;
-        if (!(kd == ssn::M_FILL || kd == ssn::M_ROW_IN || kd == ssn::M_TABLE || kd == ssn::M_AXPY_INC ||
-              kd == ssn::M_AXPY_SET || kd == ssn::M_LOWPASS)) break;
-        bool hazard = false;
-        for (size_t e = 0; e < lv && !hazard; ++e) {
-          const MOp& pr = head[e];
-          hazard = overlap(q.dst, q.len, pr.dst, pr.len) || (reads_src(pr) && overlap(q.dst, q.len, pr.src, pr.len)) ||
-                   (reads_src(q) && overlap(q.src, q.len, pr.dst, pr.len));
-        }
-        if (hazard) break;
+        if (!kind_is(q.kind, MK_VECOPS)) break;
+        mine.clear();
+        micro_access(mine, q, false, true);
+        if (hazard(mine, moved)) break;
+        moved.insert(moved.end(), mine.begin(), mine.end());
         elems += q.len;
       }
       if (elems >= 16384 && lv > 0 && lv < head.size()) {
@@ -2009,22 +2011,15 @@ struct Sim final : ssn_sim {
       prog_descs.push_back(hd);
       tail_begin = n_prog - 1;
     }
-    CHK(dmalloc(&d_progs, (int64_t)std::max<size_t>(1, prog_descs.size()) * (int64_t)sizeof(ssn::ProgDesc)));
-    if (!prog_descs.empty()) HIPCHK(hipMemcpy(d_progs, prog_descs.data(), prog_descs.size() * sizeof(ssn::ProgDesc), hipMemcpyHostToDevice));
+    CHK(dupload(&d_progs, prog_descs));
     if (!vec_ops.empty()) {
       items.front().op_begin = (int)mops.size(); items.front().op_count = (int)vec_ops.size();
       mops.insert(mops.end(), vec_ops.begin(), vec_ops.end());
     }
-    CHK(dmalloc(&d_mops, (int64_t)mops.size() * (int64_t)sizeof(MOp)));
-    HIPCHK(hipMemcpy(d_mops, mops.data(), mops.size() * sizeof(MOp), hipMemcpyHostToDevice));
+    CHK(dupload(&d_mops, mops));
     launches_per_step = (int)items.size() - (can_fuse ? 1 : 0);
     if (fused_defer) launches_per_step = 1;
     if (fused_block) launches_per_step = 0;      // one launch per block
-    int n_core_ops = 0;
-    for (int i = 0; i < m->n_ops; ++i) n_core_ops += m->ops[i].stage == 1;
-    bool core_probe = false;
-    for (auto& p : probes) core_probe = core_probe || p.stage == 1;
-    core_empty = bsig && n_core_ops == 0 && !core_probe;
     if (core_empty) launches_per_step = 0;
     if (!fused) analyse_dependencies(programs, item_prog);
     if (!fused && !opt.has(SSN_PLAN_NO_ITEM_BATCH)) merge_adjacent_items();
@@ -2051,10 +2046,6 @@ struct Sim final : ssn_sim {
   // hazards (RAW, WAR, WAW against every earlier unit of the sequential order) allow.  A round is launched as one k_round
   // grid (ssn_round.hpp) plus one plain launch for each operator whose kernel has no body there (ensemble arrays, the
   // ordered / factored clean-up products).
-  static bool glue_row_kind(int k) {
-    return k == ssn::M_MATVEC_INC || k == ssn::M_MATVEC_SET || k == ssn::M_ENS_FINISH || k == ssn::M_REDUCE_SET || k == ssn::M_REDUCE_INC;
-  }
-
   // k_round body of an ensemble array (-1: its variant has none, it is launched on its own)
   int ens_round_kind(const ssn::EnsArgs<T>& a) const {
     // (a tapped array is launched on its own - k_ensarray's tapped twin: the bodies of the round grid do not know taps - and so
@@ -2283,8 +2274,7 @@ struct Sim final : ssn_sim {
       if (N.list) {                        // spike list in 16-neuron segments: counts per small segment, the spans of the products stay
         int* cnt = nullptr;
         const int n_small = (N.n + 15) / 16;
-        CHK(dmalloc(&cnt, (int64_t)n_small * 4 + 64));
-        HIPCHK(hipMemset(cnt, 0, (size_t)n_small * 4 + 64));
+        CHK(dzeros(&cnt, (int64_t)n_small + 16));
         for (Item& sp : items) if (sp.type == IT_SPMV && sp.list == N.list) { sp.count = cnt; sp.seg_len = 16; }
         N.count = cnt;
       }
@@ -2310,16 +2300,14 @@ struct Sim final : ssn_sim {
     return cuts;
   }
   int split_micro(const MOp& op, const std::vector<int64_t>& cuts, std::vector<MOp>& out) {
-    const bool ew = op.kind == ssn::M_FILL || op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS ||
-                    op.kind == ssn::M_LINCOMB || op.kind == ssn::M_ROW_IN || op.kind == ssn::M_ROW_OUT;
-    if (!ew || op.len <= 1 || opt.has(SSN_PLAN_NO_CUTS)) { out.push_back(op); return SSN_OK; }
-    std::vector<int64_t> bases;                       // signal-space origins of the operator's operands
-    if (op.kind != ssn::M_ROW_OUT) bases.push_back(op.dst);
-    if (op.kind == ssn::M_AXPY_INC || op.kind == ssn::M_AXPY_SET || op.kind == ssn::M_LOWPASS || op.kind == ssn::M_ROW_OUT) bases.push_back(op.src);
+    if (!kind_is(op.kind, MK_CUT) || op.len <= 1 || opt.has(SSN_PLAN_NO_CUTS)) { out.push_back(op); return SSN_OK; }
+    std::vector<Rng> operands;                        // (their origins in signal space: every one is op.len long)
+    micro_access(operands, op);
     const std::vector<ssn::LinTerm<T>>* terms = nullptr;
-    if (op.kind == ssn::M_LINCOMB) { auto f = lin_terms.find(op.p0); if (f != lin_terms.end()) { terms = &f->second; for (auto& t : *terms) bases.push_back(t.src); } }
+    if (op.kind == ssn::M_LINCOMB) { auto f = lin_terms.find(op.p0); if (f != lin_terms.end()) terms = &f->second; }
     std::vector<int64_t> offs{0, op.len};
-    for (int64_t b : bases) {
+    for (const Rng& r : operands) {
+      const int64_t b = r.lo;
       auto lo = std::upper_bound(cuts.begin(), cuts.end(), b), hi = std::lower_bound(cuts.begin(), cuts.end(), b + op.len);
       for (auto it = lo; it < hi; ++it) offs.push_back(*it - b);
     }
@@ -2337,8 +2325,7 @@ struct Sim final : ssn_sim {
         std::vector<ssn::LinTerm<T>> tt = *terms;
         for (auto& t : tt) t.src += o;
         ssn::LinTerm<T>* d_terms = nullptr;
-        CHK(dmalloc(&d_terms, (int64_t)std::max<size_t>(1, tt.size()) * (int64_t)sizeof(ssn::LinTerm<T>)));
-        if (!tt.empty()) HIPCHK(hipMemcpy(d_terms, tt.data(), tt.size() * sizeof(ssn::LinTerm<T>), hipMemcpyHostToDevice));
+        CHK(dupload(&d_terms, tt));
         lin_terms[(const void*)d_terms] = tt;
         pc.p0 = d_terms;
       }
@@ -2374,8 +2361,7 @@ struct Sim final : ssn_sim {
     }
     for (Unit& u : b.units) for (const Rng& r : u.acc) u.writes = u.writes || r.w;
     b.unit_arg.assign(b.units.size(), -1);
-    CHK(dmalloc(&d_mops, (int64_t)std::max<size_t>(1, mops.size()) * (int64_t)sizeof(MOp)));
-    if (!mops.empty()) HIPCHK(hipMemcpy(d_mops, mops.data(), mops.size() * sizeof(MOp), hipMemcpyHostToDevice));
+    CHK(dupload(&d_mops, mops));
     return SSN_OK;
   }
 
@@ -2384,12 +2370,7 @@ struct Sim final : ssn_sim {
   // behind that update) joins their round - one block then runs the chain's operators back to back on 256 elements, the
   // same thread on the same index in program order, with no barrier and no launch between them.
   bool chainable(const Unit& u) const {
-    if (u.mop < 0 || opt.has(SSN_PLAN_NO_CHAINS)) return false;
-    switch (mops[(size_t)u.mop].kind) {
-      case ssn::M_FILL: case ssn::M_AXPY_INC: case ssn::M_AXPY_SET: case ssn::M_LOWPASS: case ssn::M_LINCOMB: case ssn::M_TABLE:
-      case ssn::M_ROW_IN: case ssn::M_ROW_OUT: case ssn::M_PROBE: case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC: return true;
-      default: return false;
-    }
+    return u.mop >= 0 && !opt.has(SSN_PLAN_NO_CHAINS) && kind_is(mops[(size_t)u.mop].kind, MK_CHAIN);
   }
   // Serial chains (round 4, second half).  The long loop of a SLAM timestep - clean-up -> binding -> memory -> unbinding -> gate ->
   // oscillator input, one synapse delay per hop - is partly made of operators that ONE workgroup executes: glue over 1 - 2
@@ -2423,13 +2404,12 @@ struct Sim final : ssn_sim {
     if (!solo_on) return -1.0;
     if (u.mop >= 0) {
       const MOp& op = mops[(size_t)u.mop];
+      // (measured on the chains of SLAM config 3: ~2 us per glue member - one trip for its data, one for the store to land
+      //  before the barrier - with its descriptor already in LDS; a transform ~9.5 us)
+      if (kind_is(op.kind, MK_SAME_THREAD))
+        return op.len <= opt.solo_max_len ? 1.7 + 0.5 * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
       switch (op.kind) {
-        // (measured on the chains of SLAM config 3: ~2 us per glue member - one trip for its data, one for the store to land
-        //  before the barrier - with its descriptor already in LDS; a transform ~9.5 us)
         case ssn::M_GATE: case ssn::M_ARGMAX_GATHER: return 3.5;
-        case ssn::M_FILL: case ssn::M_AXPY_INC: case ssn::M_AXPY_SET: case ssn::M_LOWPASS: case ssn::M_TABLE:
-        case ssn::M_ROW_IN: case ssn::M_ROW_OUT: case ssn::M_PROBE:
-          return op.len <= opt.solo_max_len ? 1.7 + 0.5 * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
         case ssn::M_LINCOMB:
           return op.len <= opt.solo_max_len ? 1.7 + (0.5 + 0.1 * (double)op.i0) * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
         case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC:
@@ -2733,7 +2713,7 @@ struct Sim final : ssn_sim {
           for (int c = 0; c < blocks; ++c) b.glue_map.push_back(ssn::GlueBlock{-(ofs + 1), c});
           continue;
         }
-        const long long per = glue_row_kind(op.kind) ? ssn::GLUE_ROWS : ssn::GLUE_CHUNK;
+        const long long per = kind_is(op.kind, MK_GLUE_ROW) ? ssn::GLUE_ROWS : ssn::GLUE_CHUNK;
         const int chunks = (int)std::max<long long>(1, (op.len + per - 1) / per);
         for (int c = 0; c < chunks; ++c) b.glue_map.push_back(ssn::GlueBlock{u.mop, c | (in->sub << 24)});
       }
@@ -3001,18 +2981,16 @@ struct Sim final : ssn_sim {
 
   // device copies of the arena, the glue map and the chain table; the round entries get their pointers
   int upload_round_tables(const RoundBuild& b) {
-    T* d_arena = nullptr; ssn::GlueBlock* d_map = nullptr;
-    CHK(dmalloc(&d_arena, (int64_t)b.arena.size() + 16));
-    CHK(dmalloc(&d_map, (int64_t)(b.glue_map.size() + 1) * (int64_t)sizeof(ssn::GlueBlock)));
-    if (!b.arena.empty()) HIPCHK(hipMemcpy(d_arena, b.arena.data(), b.arena.size(), hipMemcpyHostToDevice));
-    if (!b.glue_map.empty()) HIPCHK(hipMemcpy(d_map, b.glue_map.data(), b.glue_map.size() * sizeof(ssn::GlueBlock), hipMemcpyHostToDevice));
-    int* d_chain = nullptr;
-    CHK(dmalloc(&d_chain, (int64_t)(b.chain_tab.size() + 1) * 4));
-    if (!b.chain_tab.empty()) HIPCHK(hipMemcpy(d_chain, b.chain_tab.data(), b.chain_tab.size() * 4, hipMemcpyHostToDevice));
-    for (RoundLaunch& rl : round_launches) { rl.args.chain = d_chain; rl.args.arena = (const unsigned char*)d_arena; }
+    unsigned char* d_arena = nullptr; ssn::GlueBlock* d_map = nullptr; int* d_chain = nullptr;
+    std::vector<unsigned char> arena = b.arena;      // (16 spare bytes: the tail of a body's arguments may be loaded as part of a whole 16-byte word)
+    arena.resize(arena.size() + 16);
+    CHK(dupload(&d_arena, arena));
+    CHK(dupload(&d_map, b.glue_map));
+    CHK(dupload(&d_chain, b.chain_tab));
+    for (RoundLaunch& rl : round_launches) { rl.args.chain = d_chain; rl.args.arena = d_arena; }
     for (const Fix& f : b.fixes) {
       ssn::RoundEntry& e = round_launches[f.rl].args.e[f.entry];
-      if (f.what == 0) e.args = (const unsigned char*)d_arena + f.off;
+      if (f.what == 0) e.args = d_arena + f.off;
       else if (f.what == 1) e.args = d_map + f.off;
       else if (f.what == 3) e.args = d_chain + f.off;
       else e.args = d_mops + f.off;
@@ -3091,24 +3069,26 @@ struct Sim final : ssn_sim {
         }
       }
   }
-  void micro_access(std::vector<Rng>& a, const MOp& op, bool with_clock = false) const {
+  // (keep_empty: the operator's signal ranges of length 0 are listed too - hazard() then finds one inside another range)
+  void micro_access(std::vector<Rng>& a, const MOp& op, bool with_clock = false, bool keep_empty = false) const {
     const void* clock = (const void*)d_ctx;
+    auto range = [&](int64_t lo, int64_t len, bool w) { if (len > 0 || (keep_empty && len == 0)) a.push_back(Rng{(const void*)sig, lo, lo + len, w}); };
     switch (op.kind) {
-      case ssn::M_FILL: acc_sig(a, op.dst, op.len, true); break;
-      case ssn::M_TABLE: case ssn::M_ROW_IN: acc_sig(a, op.dst, op.len, true); if (with_clock) acc_ptr(a, clock, false); break;
-      case ssn::M_AXPY_INC: case ssn::M_LOWPASS: acc_sig(a, op.src, op.len, false); acc_sig(a, op.dst, op.len, true); break;
-      case ssn::M_AXPY_SET: acc_sig(a, op.src, op.len, false); acc_sig(a, op.dst, op.len, true); break;
+      case ssn::M_FILL: range(op.dst, op.len, true); break;
+      case ssn::M_TABLE: case ssn::M_ROW_IN: range(op.dst, op.len, true); if (with_clock) acc_ptr(a, clock, false); break;
+      case ssn::M_AXPY_INC: case ssn::M_LOWPASS: range(op.src, op.len, false); range(op.dst, op.len, true); break;
+      case ssn::M_AXPY_SET: range(op.src, op.len, false); range(op.dst, op.len, true); break;
       case ssn::M_LINCOMB: {
         auto it = lin_terms.find(op.p0);
-        if (it != lin_terms.end()) for (auto& t : it->second) acc_sig(a, t.src, op.len, false);
-        acc_sig(a, op.dst, op.len, true);
+        if (it != lin_terms.end()) for (auto& t : it->second) range(t.src, op.len, false);
+        range(op.dst, op.len, true);
         break;
       }
-      case ssn::M_MATVEC_INC: case ssn::M_MATVEC_SET: acc_sig(a, op.src, op.i0, false); acc_sig(a, op.dst, op.len, true); acc_ptr(a, op.p0, false); break;
-      case ssn::M_GATE: acc_sig(a, op.src, 2 * op.len + 1, false); acc_sig(a, op.dst, op.len, true); break;
-      case ssn::M_ARGMAX_GATHER: acc_ptr(a, op.p1, false); acc_ptr(a, op.p0, false); acc_sig(a, op.dst, op.len, true); break;
-      case ssn::M_PROBE: case ssn::M_ROW_OUT: acc_sig(a, op.src, op.len, false); if (with_clock) acc_ptr(a, clock, false); break;
-      case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC: acc_ptr(a, op.p0, false); acc_sig(a, op.dst, op.len, true); break;
+      case ssn::M_MATVEC_INC: case ssn::M_MATVEC_SET: range(op.src, op.i0, false); range(op.dst, op.len, true); acc_ptr(a, op.p0, false); break;
+      case ssn::M_GATE: range(op.src, 2 * op.len + 1, false); range(op.dst, op.len, true); break;
+      case ssn::M_ARGMAX_GATHER: acc_ptr(a, op.p1, false); acc_ptr(a, op.p0, false); range(op.dst, op.len, true); break;
+      case ssn::M_PROBE: case ssn::M_ROW_OUT: range(op.src, op.len, false); if (with_clock) acc_ptr(a, clock, false); break;
+      case ssn::M_REDUCE_SET: case ssn::M_REDUCE_INC: acc_ptr(a, op.p0, false); range(op.dst, op.len, true); break;
       case ssn::M_ENS_FINISH: acc_ptr(a, op.p0, false); acc_index_list(a, op.p1, true); break;
       case ssn::M_STEP_END: if (with_clock) acc_ptr(a, clock, true); break;      // (item plan: the tail program is a join point anyway)
       default: break;
@@ -3118,7 +3098,7 @@ struct Sim final : ssn_sim {
     switch (it.type) {
       case IT_ENS:
         if (it.ens.direct) acc_index_list(a, (const void*)it.ens.didx, true);
-        if (const TapSet* ts = taps_of(it.ens)) for (const ssn_tap_desc& t : ts->list) acc_sig(a, t.dst, t.count, true);
+        if (const TapSet* ts = it.taps) for (const ssn_tap_desc& t : ts->list) acc_sig(a, t.dst, t.count, true);
         acc_sig(a, it.ens.x_off, (int64_t)it.ens.K * it.ens.din, false);
         if (const DriveSet* ds = it.drv) {
           for (int32_t sx : ds->src) if (sx >= 0) acc_sig(a, sx, 1, false);
@@ -3206,15 +3186,10 @@ struct Sim final : ssn_sim {
   }
 
   // Element-wise operators of a time-batched stage: what they write / read (column ranges; rows are handled alike).
-  static bool batch_elementwise(const ssn::BatchOp<T>& o) {
-    return o.kind == ssn::M_FILL || o.kind == ssn::M_AXPY_INC || o.kind == ssn::M_AXPY_SET || o.kind == ssn::M_TABLE || o.kind == ssn::M_PROBE;
-  }
-  static bool batch_writes(const ssn::BatchOp<T>& o) { return o.kind != ssn::M_PROBE; }
-  static bool batch_reads(const ssn::BatchOp<T>& o) {
-    return o.kind == ssn::M_AXPY_INC || o.kind == ssn::M_AXPY_SET || o.kind == ssn::M_PROBE || o.kind == ssn::M_LOWPASS ||
-           o.kind == ssn::M_MATVEC_SET || o.kind == ssn::M_MATVEC_INC;
-  }
-  static long long batch_read_len(const ssn::BatchOp<T>& o) { return (o.kind == ssn::M_MATVEC_SET || o.kind == ssn::M_MATVEC_INC) ? o.cols : o.len; }
+  static bool batch_elementwise(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_EW); }
+  static bool batch_writes(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_W); }
+  static bool batch_reads(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_R); }
+  static long long batch_read_len(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_PRODUCT) ? o.cols : o.len; }
   // Hazard between two operators of a stage, `a` the earlier one.  0: none; 1: only on elements that both touch at the SAME
   // index of the same row (equal range origins, no previous-row read of what the other writes) - two element-wise operators
   // may then share a launch, the same thread runs them in order (kb_elementwise_multi); 2: anything else.
@@ -3348,7 +3323,7 @@ struct Sim final : ssn_sim {
           continue;
         }
       }
-      if (track && (ops[i].kind == ssn::M_MATVEC_SET || ops[i].kind == ssn::M_MATVEC_INC) && !ops[i].src_prev && all_zero(ops[i].src, ops[i].cols)) {
+      if (track && kind_is(ops[i].kind, MK_BATCH_PRODUCT) && !ops[i].src_prev && all_zero(ops[i].src, ops[i].cols)) {
         ++batch_skipped;
         if (ops[i].kind == ssn::M_MATVEC_SET) {        // W @ 0: the result rows of the block are zero (an increment adds nothing)
           hipError_t e = hipMemset2DAsync(bsig + n_sig + ops[i].dst, (size_t)n_sig * sizeof(T), 0, (size_t)ops[i].len * sizeof(T), (size_t)B, stream);

@@ -109,6 +109,41 @@ def test_f64_gated_array_equals_the_graph_walk(Simulator, form, flags):
         np.testing.assert_array_equal(runs[1][k], got[k])
 
 
+# ---- 1b. the drive on the second of two arrays --------------------------------------------------------------------------------
+@pytest.mark.parametrize("flags", [0, NO_ITEM_PLAN])
+def test_f64_drive_on_the_second_of_two_arrays(Simulator, flags):
+    """Two arrays of K = 2 members of 64 neurons, both tapped, the drive on the second one only (drive columns belong to an
+    operator by its index in the model, and the first array has none to be mistaken for); 20 steps, spike for spike.  Default
+    rates of up to 400 Hz: -10 thins the driven members' spikes out during timesteps 9 .. 14, it does not silence them."""
+    steps = 20
+    with nengo.Network(seed=14) as net:
+        stim = nengo.Node(lambda t: [0.8 * np.sin(40 * t), 0.6 * np.cos(30 * t)])
+        gate = nengo.Node(window(8, 14))
+        first = nengo.EnsembleArray(64, 2, seed=15)
+        second = nengo.EnsembleArray(64, 2, seed=16)
+        nengo.Connection(stim, first.input, synapse=0.005)
+        nengo.Connection(stim, second.input, synapse=0.005)
+        nengo.Connection(gate, second.add_neuron_input(), transform=np.ones((2 * 64, 1)) * -10, synapse=None)
+        probes = {"free": nengo.Probe(first.ea_ensembles[1].neurons), "driven": nengo.Probe(second.ea_ensembles[1].neurons)}
+        p_out = nengo.Probe(second.output, synapse=0.01)
+    model = build(net)
+    assert ["drive" in o for o in model.ops if o["kind"] == "ensarray"] == [False, True]
+    walk = GraphWalkSimulator(net, model)
+    walk.run_steps(steps)
+    want = {k: np.array(walk.probe_data(p)) for k, p in probes.items()}
+    spikes = want["driven"] != 0
+    assert spikes[:8].sum() > 20 and spikes[14:].sum() > 20 and 0 < spikes[8:14].sum() < 0.5 * spikes[:8].sum()
+    assert (want["free"][8:14] != 0).sum() > 20
+    with Simulator(None, model=model, dtype="f64", flags=flags) as sim:
+        sim.run_steps(steps)
+        no_block_kernel(sim.counters())
+        for k, p in probes.items():
+            got = np.array(sim.data[p])
+            print("flags %d %s: %d spikes, %d mismatches" % (flags, k, int((want[k] != 0).sum()), int((got != want[k]).sum())))
+            np.testing.assert_array_equal(got, want[k])
+        np.testing.assert_allclose(np.array(sim.data[p_out]), walk.probe_data(p_out), atol=1e-9, rtol=0)
+
+
 # ---- 2. the path integrator with two driven oscillators, every plan -----------------------------------------------------------
 _DRIVEN_PI = {}
 

@@ -156,6 +156,35 @@ def test_f64_slam_oscillator_and_product_member(Simulator, flags):
         np.testing.assert_allclose(np.array(sim.data[sm.probe]), want_out, atol=1e-9, rtol=0)
 
 
+@pytest.mark.parametrize("flags", [0, NO_ITEM_PLAN])
+def test_f64_tap_on_the_second_of_two_arrays(Simulator, flags):
+    """Two arrays of K = 2 members of 64 neurons, the tap on the second one only (taps belong to an operator by its index in the
+    model, and the first array has none to be mistaken for); 20 steps, spike for spike."""
+    steps = 20
+    with nengo.Network(seed=14) as net:
+        stim = nengo.Node(lambda t: [0.8 * np.sin(40 * t), 0.6 * np.cos(30 * t)])
+        first = nengo.EnsembleArray(64, 2, seed=15)
+        second = nengo.EnsembleArray(64, 2, seed=16)
+        nengo.Connection(stim, first.input, synapse=0.005)
+        nengo.Connection(stim, second.input, synapse=0.005)
+        p_first = nengo.Probe(first.output, synapse=0.01)
+        p_tap = nengo.Probe(second.ea_ensembles[1].neurons, synapse=None)
+        p_out = nengo.Probe(second.output, synapse=0.01)
+    model = build(net)
+    assert ["taps" in o for o in model.ops if o["kind"] == "ensarray"] == [False, True]
+    walk = GraphWalkSimulator(net, model)
+    walk.run_steps(steps)
+    want = np.array(walk.probe_data(p_tap))
+    assert want.shape == (steps, 64) and (want != 0).sum() > 50
+    with Simulator(None, model=model, dtype="f64", flags=flags) as sim:
+        sim.run_steps(steps)
+        got = np.array(sim.data[p_tap])
+        print("flags %d: %d spikes, %d mismatches" % (flags, int((want != 0).sum()), int((got != want).sum())))
+        np.testing.assert_array_equal(got, want)
+        for p in (p_first, p_out):
+            np.testing.assert_allclose(np.array(sim.data[p]), walk.probe_data(p), atol=1e-9, rtol=0)
+
+
 # ---- f32, exact by construction --------------------------------------------------------------------------------------
 def open_loop_with_taps(monkeypatch, n, slices):
     """``lif_open_loop.open_loop_pathint(n, ssp_dim=7)`` with neuron probes on the members ``slices`` names, added before its

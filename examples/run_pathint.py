@@ -57,6 +57,8 @@ def parse(argv=None):
                    help="probe neurons[:500] of the oscillators 1..M every 100 steps (run_pathint_gif.py probes 1, 2 and 3)")
     p.add_argument("--gate-oscillators", default=None, type=float, nargs=2, metavar=("T0", "T1"),
                    help="inhibit the oscillators' neurons (weight -10, through add_neuron_input()) for T0 < t <= T1")
+    p.add_argument("--decode-backend", default="numpy", choices=["numpy", "hip"],
+                   help="grid decode of the probed trajectory: NumPy on the host, or the GPU grid decoder (decoding.GridDecoder)")
     return p.parse_args(argv)
 
 
@@ -105,10 +107,13 @@ def main(argv=None):
         out, ts = sim.data[pm.probe], sim.trange()
         spikes, spike_ts = {k: np.array(sim.data[p]) for k, p in spike_probes.items()}, sim.trange(sample_every=skip * dt)
     n = out.shape[0]
-    est, sims, err = H.pathint_metrics(space, out, pm.real_ssp[:n], path[:n])
-    print("d = %d, %d VCOs x %d neurons, T = %.1f s: build %.1f s, run %.2f s (%.1f sim-s/wall-s); similarity to the true SSP "
-          "mean %.4f, final position error %.4f" % (space.ssp_dim, (space.ssp_dim + 1) // 2, args.pi_n_neurons, T, build_time,
-                                                   elapsed_time, T / elapsed_time, sims[min(200, n - 1):].mean(), err[-1]))
+    t0 = time.time()
+    est, sims, err = H.pathint_metrics(space, out, pm.real_ssp[:n], path[:n], backend=args.decode_backend)
+    decode_time = time.time() - t0
+    print("d = %d, %d VCOs x %d neurons, T = %.1f s: build %.1f s, run %.2f s (%.1f sim-s/wall-s), decode %.2f s (%s); similarity "
+          "to the true SSP mean %.4f, final position error %.4f" % (space.ssp_dim, (space.ssp_dim + 1) // 2, args.pi_n_neurons, T,
+                                                                   build_time, elapsed_time, T / elapsed_time, decode_time,
+                                                                   args.decode_backend, sims[min(200, n - 1):].mean(), err[-1]))
     if args.save:
         os.makedirs(args.save_dir, exist_ok=True)
         name = "pi_backend_%s%s_sspdim_%d_pinneurons_%d_T_%d_limit_%s_seed_%d.npz" % (

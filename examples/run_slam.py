@@ -45,6 +45,8 @@ def parse(argv=None):
     p.add_argument("--save-dir", default="data")
     p.add_argument("--save-name-extra", default="")
     p.add_argument("--n-eval-points", default=0, type=int, help="decoder-solve evaluation points; 0 = nengo's default")
+    p.add_argument("--decode-backend", default="numpy", choices=["numpy", "hip"],
+                   help="grid decodes of the trajectory and the recalled map: NumPy on the host, or the GPU grid decoder")
     return p.parse_args(argv)
 
 
@@ -75,12 +77,15 @@ def main(argv=None):
         decoders = sim.data[sm.weights_probe][-1]
         built_memory = sim.data[sm.slam.assomemory.memory]
     n = out.shape[0]
-    est, sims, err = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n])
-    lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders)
+    t0 = time.time()
+    est, sims, err = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n], backend=args.decode_backend)
+    lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend)
+    decode_time = time.time() - t0
     lm_err = np.linalg.norm(lm_locs - sm.obj_locs, axis=1)
-    print("d = %d, T = %.1f s: build %.1f s, run %.2f s (%.2f sim-s/wall-s); similarity to the true SSP mean %.4f, final position "
-          "error %.4f; recalled landmark positions: median error %.3f" % (space.ssp_dim, T, build_time, elapsed, T / elapsed,
-                                                                         sims[min(200, n - 1):].mean(), err[-1], float(np.median(lm_err))))
+    print("d = %d, T = %.1f s: build %.1f s, run %.2f s (%.2f sim-s/wall-s), decode %.2f s (%s); similarity to the true SSP mean "
+          "%.4f, final position error %.4f; recalled landmark positions: median error %.3f" % (
+              space.ssp_dim, T, build_time, elapsed, T / elapsed, decode_time, args.decode_backend, sims[min(200, n - 1):].mean(),
+              err[-1], float(np.median(lm_err))))
     if args.save:
         os.makedirs(args.save_dir, exist_ok=True)
         name = "slam_backend_%s%s_sspdim_%d_pinneurons_%d_memnneurons_%d_ccnneurons_%d_T_%d_limit_%s_seed_%d.npz" % (

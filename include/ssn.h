@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SSN_ABI_VERSION 10
+#define SSN_ABI_VERSION 11
 
 enum ssn_status {
   SSN_OK = 0,
@@ -359,6 +359,44 @@ enum ssn_probe_kind {
 };
 int ssn_probe_issue_rate(int32_t device, int32_t kind, int32_t waves_per_simd, int32_t iters,
                          double* ns_per_wave_instruction, double* shader_mhz);
+
+/* Grid decoding of SSP trajectories (ABI 11; csrc/ssn_decode.hip): SSPSpace.decode(rows, 'from-set', 'grid', n) on the device,
+ * reference run_pathint.py:171-179, run_slam.py:242-268.  A decoder holds a sample table (n_samples x width host doubles, C order,
+ * converted to `dtype` and uploaded once) and a scratch area whose size is fixed at creation (0 = 64 MB; at least one 128-row tile:
+ * ssn_decoder_info.min_scratch_bytes); it is independent of ssn_sim and may outlive or precede any simulator.  Every input row is
+ * scaled as the host scales it (divided by its norm when the norm is >= 1e-6, left as it is otherwise) and
+ *   best[t] = argmax_j sum_k row_t[k] table[j][k]      (lowest j on ties; sims[t], when not NULL, is that largest similarity)
+ * f32 runs on the f32-input matrix cores (each similarity an exact k-ordered fmaf chain), f64 is the parity mode.  The n_rows x
+ * n_samples similarity matrix is never stored; the results do not depend on the scratch size and are the same from run to run.
+ * Non-finite input is out of contract: best[] stays inside [0, n_samples).  best / sims are host arrays, filled when the call returns.
+ * SSN_EINVAL: null handle or argument, width 0, n_samples 0 or above 2^31 - 1, scratch too small for one tile;
+ * SSN_EHIP "no HIP device available (there is no CPU fallback)" without a GPU; n_rows == 0 succeeds and writes nothing. */
+typedef struct ssn_decoder ssn_decoder;
+typedef struct ssn_decoder_info {
+  int64_t row_chunk;          /* rows per chunk (whole tiles) for the n_rows asked about                         */
+  int64_t n_chunks;
+  int64_t n_strips;           /* column strips: workgroups per row tile, partials per row                        */
+  int64_t tiles_per_strip;    /* column tiles a workgroup walks                                                  */
+  int64_t tile;               /* rows and columns of a tile (128)                                                */
+  int64_t scratch_bytes;
+  int64_t min_scratch_bytes;  /* one row tile with one strip                                                     */
+  int64_t slot_bytes;         /* what one more strip of a row tile costs                                         */
+  int64_t padded_width;
+  int64_t last_launches;      /* kernel launches of the last ssn_decoder_rows* call                              */
+  double last_kernel_ms;      /* their device time (HIP events around the kernels of every chunk, copies outside) */
+} ssn_decoder_info;
+int ssn_decoder_create(int32_t dtype, int32_t device, const double* table, int64_t n_samples, int64_t width,
+                       int64_t scratch_bytes /* 0 = default */, ssn_decoder** out);
+void ssn_decoder_destroy(ssn_decoder* dec);
+int ssn_decoder_rows(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t* best, double* sims /* may be NULL */);
+/* rows already on the decoder's device: rows_dtype SSN_F32 / SSN_F64, leading dimension ld >= width (elements) */
+int ssn_decoder_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows,
+                            int32_t* best, double* sims);
+/* How a call with n_rows rows is cut into row chunks and column strips, and the device time of the last call. */
+int ssn_decoder_get_info(ssn_decoder* dec, int64_t n_rows, ssn_decoder_info* out);
+/* Measurement aid (tools/bench_decode.py): the same answer from the composition the fused kernel replaces - k_gemm_nt_mfma_f32 into
+ * an n_rows x n_samples buffer (at most 2 GB, allocated for the call), then k_argmax_partial; f32 decoders, one row chunk. */
+int ssn_decoder_rows_composed(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t* best);
 
 int ssn_get_counters(ssn_sim* sim, ssn_counters* out);
 /* Fills at most `capacity` entries; returns the number of kernels with timed launches (or a negative status). */

@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSN_HIP_LIB") or os.path.join(_HERE, "libssn_hip.so")     # override: A/B builds of the library
 
-SSN_ABI_VERSION = 10
+SSN_ABI_VERSION = 11
 SSN_F32, SSN_F64 = 0, 1
 SSN_BUF_REAL, SSN_BUF_I32, SSN_BUF_TAPS, SSN_BUF_DRIVES = 0, 1, 2, 3
 NEURON_CODE = {"lif": 0, "lifrate": 1, "relu": 2}
@@ -91,6 +91,12 @@ class Counters(C.Structure):
                 ("fused_populations", C.c_int32), ("serial_chains", C.c_int32)]
 
 
+class DecoderInfo(C.Structure):
+    _fields_ = [("row_chunk", C.c_int64), ("n_chunks", C.c_int64), ("n_strips", C.c_int64), ("tiles_per_strip", C.c_int64),
+                ("tile", C.c_int64), ("scratch_bytes", C.c_int64), ("min_scratch_bytes", C.c_int64), ("slot_bytes", C.c_int64),
+                ("padded_width", C.c_int64), ("last_launches", C.c_int64), ("last_kernel_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("ms_total", C.c_double)]
 
@@ -120,6 +126,12 @@ EXPORTS = {
     "ssn_phase_async": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ssn_phase_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ssn_probe_issue_rate": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ssn_decoder_create": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "ssn_decoder_destroy": (None, [C.c_void_p]),
+    "ssn_decoder_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ssn_decoder_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ssn_decoder_get_info": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(DecoderInfo)]),
+    "ssn_decoder_rows_composed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ssn_get_counters": (C.c_int, [C.c_void_p, C.POINTER(Counters)]),
     "ssn_get_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(KernelTime), C.c_int32]),
     "ssn_n_steps": (C.c_int64, [C.c_void_p]),

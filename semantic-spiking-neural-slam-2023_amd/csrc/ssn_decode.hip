@@ -1,0 +1,519 @@
+// ssn_decode.hip - grid decoding of SSP trajectories behind ssn_decoder_* (include/ssn.h).
+//
+// Not on the step path and independent of ssn_sim: for every input row u_t (normalised as SSPSpace.decode normalises) the index
+// of the table row with the largest similarity, best[t] = argmax_j sum_k u_t[k] table[j][k], lowest j on ties - the
+// 'from-set' grid decode that ends every experiment (reference run_pathint.py:171-179, run_slam.py:242-268).  The T x S
+// similarity matrix is never written: the product kernel's epilogue keeps one (value, column) pair per row.
+//
+//   k_decode_prepare   one wave per row: norm in f64 (fixed order), row / norm when norm >= 1e-6 else the row as it is, converted
+//                      to the decoder's dtype, zero-padded to Kp = 32 ceil(K / 32) columns and to whole 128-row tiles.
+//   k_decode_tiles     128 x 128 similarity tile per 256-thread workgroup (2 x 2 waves, 64 x 64 per wave), K in slabs through LDS
+//                      with the next slab prefetched into registers (as k_gemm_nt_mfma_f32).  A workgroup walks the
+//                      tiles_per_strip column tiles of its strip for its row tile; every thread keeps the running best of the
+//                      rows its accumulator registers belong to (columns ascend, so a strict > keeps the lowest column), and at
+//                      the end of the strip the 32 (16) lanes of a row and then the two waves beside each other are reduced with
+//                      the (value, lowest column) rule: one partial per row and strip, written with plain stores - no atomics, so
+//                      the answer is the same from run to run.  Both operands are padded, so no load is bounds-checked; padded
+//                      columns (>= S) never enter a comparison and padded rows (>= n_rows) are never written.
+//                      f32: v_mfma_f32_32x32x2_f32, 2 x 2 accumulators of 16 registers per wave, slabs of 32 - every similarity
+//                      is bit for bit the k-ordered fmaf chain over the whole K, whatever the chunking, so the results do not
+//                      depend on the scratch size.  f64 (parity mode): v_mfma_f64_16x16x4_f64, 4 x 4 accumulators, slabs of 16.
+//                      Tile and occupancy: 128 x 128 x 32 (f64: x 16) per workgroup of 4 waves, one wave per SIMD, two workgroups
+//                      per CU asked for with __launch_bounds__(256, 2) - the second hides the first's barriers and slab loads; a
+//                      wave's four accumulators are independent, which is what the 64-cycle MFMA needs to issue back to back.
+//                      tools/kernel_resources.py ssn_decode.hip k_decode_tiles:  f32 253 VGPR (64 accumulator, 64 running best,
+//                      32 prefetch), 0 AGPR, no scratch, LDS 35 840 B, occupancy 2;  f64 256 VGPR + 158 AGPR, LDS 37 888 B,
+//                      occupancy 1.  One k step of a wave is 4 LDS reads for 4 MFMAs (f64: 8 for 16).
+//   k_decode_finish    one wave per row: the partials of its strips in column order, same rule -> int32 best; the similarity to
+//                      that sample accumulated again in f64.
+//
+// Scratch (fixed at creation, default 64 MB): per row K doubles of upload staging, Kp converted values, one (value, column)
+// partial per strip slot and the (double similarity, best) result.  The host cuts n_rows into chunks of whole row tiles that fit and the
+// column walk into at most `slots` strips (decode_plan); the smallest scratch holds one row tile with one strip.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <memory>
+#include <vector>
+#include "../../include/ssn.h"
+#include "ssn_kernels.hpp"      // launch_gemm_nt / launch_argmax_partial: the materialising composition ssn_decoder_rows_composed times
+
+namespace {
+
+constexpr int TILE = 128;            // rows and columns of a workgroup's similarity tile
+constexpr int KPAD = 32;             // operands are padded to a multiple of this many columns
+constexpr int MAX_SLOTS = 64;        // strips per row chunk at most
+
+template <typename T> struct Mma;
+template <> struct Mma<float> {
+  static constexpr int MT = 32, KS = 2, AR = 16, BK = 32;
+  typedef float acc_t __attribute__((ext_vector_type(16)));
+  static __device__ __forceinline__ int lane_mn(int l) { return l & 31; }
+  static __device__ __forceinline__ int lane_k(int l) { return l >> 5; }
+  static __device__ __forceinline__ int acc_row(int v, int l) { return (v & 3) + 8 * (v >> 2) + 4 * (l >> 5); }
+  static __device__ __forceinline__ acc_t mma(float a, float b, acc_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+};
+template <> struct Mma<double> {
+  static constexpr int MT = 16, KS = 4, AR = 4, BK = 16;
+  typedef double acc_t __attribute__((ext_vector_type(4)));
+  static __device__ __forceinline__ int lane_mn(int l) { return l & 15; }
+  static __device__ __forceinline__ int lane_k(int l) { return l >> 4; }
+  static __device__ __forceinline__ int acc_row(int v, int l) { return (l >> 4) + 4 * v; }
+  static __device__ __forceinline__ acc_t mma(double a, double b, acc_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+};
+
+// (value, column) candidates: the larger value wins, the lower column on equal values
+template <typename T>
+__device__ __forceinline__ void take_better(T& bv, int& bc, T v, int c) {
+  if (v > bv || (v == bv && c < bc)) { bv = v; bc = c; }
+}
+
+template <typename TI, typename T>
+__global__ __launch_bounds__(256) void k_decode_prepare(const TI* __restrict__ src, long long ld, int n_rows, int n_pad_rows, int K, int Kp,
+                                                        T* __restrict__ dst) {
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_pad_rows) return;
+  T* d = dst + (size_t)row * Kp;
+  if (row >= n_rows) {
+    for (int k = lane; k < Kp; k += 64) d[k] = T(0);
+    return;
+  }
+  const TI* s = src + (size_t)row * ld;
+  double ss = 0.0;
+  for (int k = lane; k < K; k += 64) { const double x = (double)s[k]; ss += x * x; }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+  const double nrm = sqrt(ss);
+  const bool scale = nrm >= 1e-6;
+  for (int k = lane; k < Kp; k += 64) {
+    double x = 0.0;
+    if (k < K) { x = (double)s[k]; if (scale) x = x / nrm; }
+    d[k] = (T)x;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 1) void k_decode_tiles(const T* __restrict__ rows, const T* __restrict__ table, int Kp, int n_rows, unsigned S,
+                                                      int col_tiles, int tiles_per_strip, T* __restrict__ pval, int* __restrict__ pcol,
+                                                      int part_ld) {
+  using M = Mma<T>;
+  constexpr int BK = M::BK, LD = BK + 1, MT = M::MT, NI = 64 / MT, AR = M::AR, KS = M::KS;
+  constexpr int RS = 256 / BK, RPT = TILE / RS;      // this thread stages rows lr + RS i, column lc of a slab
+  __shared__ T As[TILE][LD];
+  __shared__ T Ws[TILE][LD];
+  __shared__ T red_v[2][TILE];
+  __shared__ int red_c[2][TILE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int t0 = blockIdx.x * TILE;
+  const int ct0 = blockIdx.y * tiles_per_strip, ct1 = min(ct0 + tiles_per_strip, col_tiles);
+  const int lr = tid / BK, lc = tid % BK;
+  // uniform tile bases + one 32-bit lane offset: the row offsets RS i Kp of the slab loads stay in scalar registers
+  const T* __restrict__ a0 = rows + (size_t)t0 * Kp;
+  const unsigned voff = (unsigned)lr * (unsigned)Kp + (unsigned)lc;      // < 128 Kp <= 2^27
+  T ra[RPT], rw[RPT];
+  auto fetch = [&](int ct, int k0) {
+    const T* a = a0 + k0;
+    const T* w = table + (size_t)ct * TILE * Kp + k0;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+      const unsigned o = (unsigned)(RS * i) * (unsigned)Kp;
+      ra[i] = (a + o)[voff];
+      rw[i] = (w + o)[voff];
+    }
+  };
+  T bv[NI * AR];
+  int bc[NI * AR];
+#pragma unroll
+  for (int s = 0; s < NI * AR; ++s) { bv[s] = T(-INFINITY); bc[s] = ct0 * TILE; }      // a real column, whatever the input holds
+  const int mn = M::lane_mn(lane);
+  const T* ap = &As[wm * 64 + mn][M::lane_k(lane)];
+  const T* wp = &Ws[wn * 64 + mn][M::lane_k(lane)];
+  fetch(ct0, 0);
+  for (int ct = ct0; ct < ct1; ++ct) {
+    typename M::acc_t acc[NI][NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j)
+#pragma unroll
+        for (int v = 0; v < AR; ++v) acc[i][j][v] = T(0);
+    for (int k0 = 0; k0 < Kp; k0 += BK) {
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) { As[lr + RS * i][lc] = ra[i]; Ws[lr + RS * i][lc] = rw[i]; }
+      __syncthreads();
+      if (k0 + BK < Kp) fetch(ct, k0 + BK);
+      else if (ct + 1 < ct1) fetch(ct + 1, 0);
+#pragma unroll 4
+      for (int kk = 0; kk < BK; kk += KS) {
+        T a[NI], b[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) { a[i] = ap[i * MT * LD + kk]; b[i] = wp[i * MT * LD + kk]; }
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int j = 0; j < NI; ++j) acc[i][j] = M::mma(a[i], b[j], acc[i][j]);
+      }
+      __syncthreads();
+    }
+    // epilogue of the tile: columns ascend with j and with ct, so a strict > keeps the lowest column of a tie
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const unsigned col = (unsigned)ct * TILE + wn * 64 + j * MT + mn;
+      if (col < S) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int v = 0; v < AR; ++v)
+            if (acc[i][j][v] > bv[i * AR + v]) { bv[i * AR + v] = acc[i][j][v]; bc[i * AR + v] = (int)col; }
+      }
+    }
+  }
+  // the MT lanes that hold one row, then the two waves side by side
+#pragma unroll
+  for (int s = 0; s < NI * AR; ++s) {
+#pragma unroll
+    for (int off = 1; off < MT; off <<= 1) {
+      const T ov = __shfl_xor(bv[s], off, 64);
+      const int oc = __shfl_xor(bc[s], off, 64);
+      take_better(bv[s], bc[s], ov, oc);
+    }
+  }
+  if (mn == 0) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int v = 0; v < AR; ++v) {
+        const int r = wm * 64 + i * MT + M::acc_row(v, lane);
+        red_v[wn][r] = bv[i * AR + v];
+        red_c[wn][r] = bc[i * AR + v];
+      }
+  }
+  __syncthreads();
+  if (tid < TILE && t0 + tid < n_rows) {
+    T v = red_v[0][tid];
+    int c = red_c[0][tid];
+    take_better(v, c, red_v[1][tid], red_c[1][tid]);
+    pval[(size_t)blockIdx.y * part_ld + t0 + tid] = v;
+    pcol[(size_t)blockIdx.y * part_ld + t0 + tid] = c;
+  }
+}
+
+// One wave per row.  The reported similarity is not the f32 chain that won the comparison: it is accumulated again in f64 over the
+// same (converted) operands, lanes striding k and a fixed butterfly.  A chain of K same-sign products - a row against its own best
+// sample - drifts by up to ~3 sqrt(K) / 12 ulp, 6.6e-7 at K = 201, which is more than the 1.5e-7 sum |a b| an MFMA product is
+// quoted at and more than half the decoder's bar; one extra dot product per row costs nothing next to the S it replaces.
+template <typename T>
+__global__ __launch_bounds__(256) void k_decode_finish(const T* __restrict__ pval, const int* __restrict__ pcol, int part_ld, int n_strips,
+                                                       int n_rows, const T* __restrict__ rows, const T* __restrict__ table, int Kp,
+                                                       double* __restrict__ sims, int* __restrict__ best) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_rows) return;
+  T v = pval[r];
+  int c = pcol[r];
+  for (int p = 1; p < n_strips; ++p) take_better(v, c, pval[(size_t)p * part_ld + r], pcol[(size_t)p * part_ld + r]);
+  const T* __restrict__ u = rows + (size_t)r * Kp;
+  const T* __restrict__ w = table + (size_t)c * Kp;
+  double acc = 0.0;
+  for (int k = lane; k < Kp; k += 64) acc = fma((double)u[k], (double)w[k], acc);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if (lane == 0) { sims[r] = acc; best[r] = c; }
+}
+
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+}  // namespace
+
+namespace ssn {
+int probe_fail(int code, const char* what, hipError_t e);      // ssn_host.hip: sets ssn_last_error
+}
+
+namespace {
+
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return ssn::probe_fail(code, buf, hipSuccess);
+}
+
+#define DHIP(expr)                                                                                      \
+  do {                                                                                                  \
+    hipError_t e__ = (expr);                                                                            \
+    if (e__ != hipSuccess) return ssn::probe_fail(e__ == hipErrorOutOfMemory ? SSN_ENOMEM : SSN_EHIP, #expr, e__); \
+  } while (0)
+
+struct DevGuard {      // the decoder's device for the duration of a call, the caller's afterwards
+  int prev = -1;
+  explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
+  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+struct Plan {
+  int64_t chunk_tiles, n_chunks, slots, n_strips, tiles_per_strip;
+};
+
+}  // namespace
+
+struct ssn_decoder {
+  int dtype = 0, device = 0, n_cu = 1;
+  int64_t S = 0, K = 0, Kp = 0, col_tiles = 0, scratch_bytes = 0;
+  size_t esz = 4;
+  void* table = nullptr;
+  char* scratch = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  double kernel_ms = 0.0;          // of the last ssn_decoder_rows* call
+  int64_t launches = 0;
+
+  int64_t row_bytes(int64_t slots) const { return K * 8 + Kp * (int64_t)esz + slots * (int64_t)(esz + 4) + 12; }
+  int64_t min_scratch() const { return TILE * row_bytes(1); }
+
+  Plan plan(int64_t n_rows) const {
+    Plan p;
+    const int64_t t_tiles = std::max<int64_t>(1, (n_rows + TILE - 1) / TILE);
+    p.slots = std::min<int64_t>(col_tiles, MAX_SLOTS);
+    int64_t cap = scratch_bytes / (TILE * row_bytes(p.slots));
+    if (cap < 1) {      // one row tile; as many strip slots as are left beside it
+      cap = 1;
+      p.slots = (scratch_bytes / TILE - row_bytes(0)) / (int64_t)(esz + 4);
+    }
+    cap = std::min<int64_t>(cap, (1 << 24) / TILE);
+    p.n_chunks = (t_tiles + cap - 1) / cap;
+    p.chunk_tiles = (t_tiles + p.n_chunks - 1) / p.n_chunks;
+    p.n_chunks = (t_tiles + p.chunk_tiles - 1) / p.chunk_tiles;
+    // Strips: the kernel keeps two workgroups per CU resident, and a launch runs in ceil(workgroups / resident) rounds of
+    // tiles_per_strip tiles each.  Of the strip lengths the slots allow, take the one that wastes the least of those rounds (the
+    // shortest on ties: more, smaller workgroups even out better).
+    const int64_t resident = 2 * (int64_t)n_cu, max_strips = std::max<int64_t>(1, std::min(p.slots, col_tiles));
+    double best_cost = 0.0;
+    p.tiles_per_strip = 0;
+    for (int64_t tps = (col_tiles + max_strips - 1) / max_strips; tps <= col_tiles; ++tps) {
+      const int64_t strips = (col_tiles + tps - 1) / tps, rounds = (p.chunk_tiles * strips + resident - 1) / resident;
+      const double cost = (double)rounds * (double)tps;
+      if (!p.tiles_per_strip || cost < best_cost) { best_cost = cost; p.tiles_per_strip = tps; }
+      if (rounds == 1) break;      // longer strips only make the single round longer
+    }
+    p.n_strips = (col_tiles + p.tiles_per_strip - 1) / p.tiles_per_strip;
+    return p;
+  }
+
+  ~ssn_decoder() {
+    DevGuard g(device);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (stream) (void)hipStreamDestroy(stream);
+    if (table) (void)hipFree(table);
+    if (scratch) (void)hipFree(scratch);
+  }
+};
+
+namespace {
+
+template <typename T>
+int upload_table(ssn_decoder* d, const double* table) {
+  const int64_t Sp = d->col_tiles * TILE, Kp = d->Kp, K = d->K;
+  DHIP(hipMalloc(&d->table, (size_t)Sp * Kp * sizeof(T)));
+  DHIP(hipMemset(d->table, 0, (size_t)Sp * Kp * sizeof(T)));
+  const int64_t per = std::max<int64_t>(1, (int64_t)(8 << 20) / Kp);
+  std::vector<T> stage((size_t)std::min(per, d->S) * Kp, T(0));
+  for (int64_t r0 = 0; r0 < d->S; r0 += per) {
+    const int64_t n = std::min(per, d->S - r0);
+    for (int64_t r = 0; r < n; ++r) {
+      const double* s = table + (size_t)(r0 + r) * K;
+      T* o = stage.data() + (size_t)r * Kp;
+      for (int64_t k = 0; k < K; ++k) o[k] = (T)s[k];
+    }
+    DHIP(hipMemcpy((T*)d->table + (size_t)r0 * Kp, stage.data(), (size_t)n * Kp * sizeof(T), hipMemcpyHostToDevice));
+  }
+  return SSN_OK;
+}
+
+template <typename T>
+struct Areas {      // the regions of the scratch area for a chunk capacity of `rows` rows and `slots` strips
+  double* stage; T* conv; T* pval; int* pcol; double* sims; int* best;
+  Areas(const ssn_decoder* d, int64_t rows, int64_t slots) {
+    char* p = d->scratch;
+    stage = (double*)p; p += (size_t)rows * d->K * 8;
+    conv = (T*)p; p += (size_t)rows * d->Kp * sizeof(T);
+    pval = (T*)p; p += (size_t)rows * slots * sizeof(T);
+    pcol = (int*)p; p += (size_t)rows * slots * 4;
+    sims = (double*)p; p += (size_t)rows * 8;
+    best = (int*)p;
+  }
+};
+
+template <typename T, typename TI>
+hipError_t launch_prepare(ssn_decoder* d, const TI* src, int64_t ld, int n, int n_pad, T* conv) {
+  hipLaunchKernelGGL((k_decode_prepare<TI, T>), dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, d->stream, src, (long long)ld, n, n_pad, (int)d->K,
+                     (int)d->Kp, conv);
+  return hipGetLastError();
+}
+
+// rows: host doubles (dense, width K) or device rows of dtype rows_dtype with leading dimension ld
+template <typename T>
+int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t n_rows, int32_t* best, double* sims) {
+  DevGuard g(d->device);
+  const Plan p = d->plan(n_rows);
+  const int64_t cap_rows = p.chunk_tiles * TILE;
+  const Areas<T> a(d, cap_rows, p.slots);
+  d->kernel_ms = 0.0;
+  d->launches = 0;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += cap_rows) {
+    const int n = (int)std::min(cap_rows, n_rows - r0), n_pad = (n + TILE - 1) / TILE * TILE;
+    if (host) DHIP(hipMemcpyAsync(a.stage, host + (size_t)r0 * d->K, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
+    DHIP(hipEventRecord(d->e0, d->stream));
+    if (host) DHIP((launch_prepare<T, double>(d, a.stage, d->K, n, n_pad, a.conv)));
+    else if (rows_dtype == SSN_F32) DHIP((launch_prepare<T, float>(d, (const float*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv)));
+    else DHIP((launch_prepare<T, double>(d, (const double*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv)));
+    hipLaunchKernelGGL((k_decode_tiles<T>), dim3((unsigned)(n_pad / TILE), (unsigned)p.n_strips), dim3(256), 0, d->stream, a.conv, (const T*)d->table,
+                       (int)d->Kp, n, (unsigned)d->S, (int)d->col_tiles, (int)p.tiles_per_strip, a.pval, a.pcol, (int)cap_rows);
+    DHIP(hipGetLastError());
+    hipLaunchKernelGGL((k_decode_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, d->stream, a.pval, a.pcol, (int)cap_rows, (int)p.n_strips,
+                       n, (const T*)a.conv, (const T*)d->table, (int)d->Kp, a.sims, a.best);
+    DHIP(hipGetLastError());
+    DHIP(hipEventRecord(d->e1, d->stream));
+    DHIP(hipMemcpyAsync(best + r0, a.best, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+    if (sims) DHIP(hipMemcpyAsync(sims + r0, a.sims, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    DHIP(hipStreamSynchronize(d->stream));
+    float ms = 0.0f;
+    DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
+    d->kernel_ms += ms;
+    d->launches += 3;
+  }
+  return SSN_OK;
+}
+
+// The composition the fused kernel replaces (tools/bench_decode.py, shape (c)): the parent's k_gemm_nt_mfma_f32 into an n_rows x S
+// buffer of its own, then k_argmax_partial with one slice per row.
+int decode_rows_composed(ssn_decoder* d, const double* host, int64_t n_rows, int32_t* best) {
+  DevGuard g(d->device);
+  const int64_t cap_rows = d->scratch_bytes / (TILE * d->row_bytes(0)) * TILE;
+  if (n_rows > cap_rows) return fail(SSN_EINVAL, "ssn_decoder_rows_composed: %lld rows do not fit the scratch area in one chunk (%lld do)", (long long)n_rows, (long long)cap_rows);
+  if ((double)n_rows * (double)d->S > (double)(1 << 29)) return fail(SSN_EINVAL, "ssn_decoder_rows_composed: a %lld x %lld similarity matrix is more than 2 GB", (long long)n_rows, (long long)d->S);
+  const Areas<float> a(d, cap_rows, 0);
+  const int n = (int)n_rows, n_pad = (n + TILE - 1) / TILE * TILE;
+  float *C = nullptr, *part = nullptr;
+  DHIP(hipMalloc(&C, (size_t)n_rows * d->S * 4));
+  if (hipMalloc(&part, (size_t)n_rows * 8) != hipSuccess) { (void)hipFree(C); return fail(SSN_ENOMEM, "hipMalloc"); }
+  std::vector<int32_t> idx((size_t)n_rows);
+  auto run = [&]() -> int {
+    DHIP(hipMemcpyAsync(a.stage, host, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
+    DHIP(hipEventRecord(d->e0, d->stream));
+    DHIP((launch_prepare<float, double>(d, a.stage, d->K, n, n_pad, a.conv)));
+    DHIP(ssn::launch_gemm_nt<float>(d->stream, a.conv, (int)d->Kp, (const float*)d->table, (int)d->Kp, C, (int)d->S, n, (int)d->S, (int)d->Kp, 1));
+    DHIP(ssn::launch_argmax_partial<float>(d->stream, C, (long long)n_rows * d->S, part, n, 1));
+    DHIP(hipEventRecord(d->e1, d->stream));
+    DHIP(hipMemcpyAsync(idx.data(), part + n_rows, (size_t)n_rows * 4, hipMemcpyDeviceToHost, d->stream));
+    DHIP(hipStreamSynchronize(d->stream));
+    float ms = 0.0f;
+    DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
+    d->kernel_ms = ms;
+    d->launches = 3;
+    return SSN_OK;
+  };
+  const int rc = run();
+  (void)hipFree(C);
+  (void)hipFree(part);
+  if (rc == SSN_OK) for (int64_t r = 0; r < n_rows; ++r) best[r] = (int32_t)((int64_t)idx[r] - r * d->S);      // slice r starts at r S
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssn_decoder_create(int32_t dtype, int32_t device, const double* table, int64_t n_samples, int64_t width, int64_t scratch_bytes,
+                       ssn_decoder** out) {
+  if (!out) return fail(SSN_EINVAL, "ssn_decoder_create: null handle");
+  *out = nullptr;
+  if (!table) return fail(SSN_EINVAL, "ssn_decoder_create: null table");
+  if (dtype != SSN_F32 && dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_create: unknown dtype %d", dtype);
+  if (width <= 0 || width > (1 << 20)) return fail(SSN_EINVAL, "ssn_decoder_create: width %lld outside 1 .. 2^20", (long long)width);
+  if (n_samples <= 0 || n_samples > INT32_MAX)
+    return fail(SSN_EINVAL, "ssn_decoder_create: n_samples %lld outside 1 .. 2^31 - 1", (long long)n_samples);
+  if (scratch_bytes < 0) return fail(SSN_EINVAL, "ssn_decoder_create: negative scratch_bytes");
+  std::unique_ptr<ssn_decoder> d(new ssn_decoder);
+  d->dtype = dtype;
+  d->device = device;
+  d->esz = dtype == SSN_F32 ? 4 : 8;
+  d->S = n_samples;
+  d->K = width;
+  d->Kp = (width + KPAD - 1) / KPAD * KPAD;
+  d->col_tiles = (n_samples + TILE - 1) / TILE;
+  d->scratch_bytes = scratch_bytes ? scratch_bytes : std::max<int64_t>((int64_t)64 << 20, d->min_scratch());
+  if (d->scratch_bytes < d->min_scratch())
+    return fail(SSN_EINVAL, "ssn_decoder_create: scratch_bytes %lld too small for one %d-row tile of width %lld (%lld bytes)", (long long)scratch_bytes,
+                TILE, (long long)width, (long long)d->min_scratch());
+  int ndev = 0;
+  const hipError_t dev_err = hipGetDeviceCount(&ndev);
+  if (dev_err != hipSuccess || ndev <= 0)
+    return fail(SSN_EHIP, "no HIP device available (there is no CPU fallback): hipGetDeviceCount -> %s, %d devices", hipGetErrorString(dev_err), ndev);
+  if (device < 0 || device >= ndev) return fail(SSN_EINVAL, "ssn_decoder_create: device %d out of range (%d devices)", device, ndev);
+  DevGuard g(device);
+  hipDeviceProp_t prop;
+  DHIP(hipGetDeviceProperties(&prop, device));
+  d->n_cu = std::max(1, prop.multiProcessorCount);
+  DHIP(hipStreamCreate(&d->stream));
+  DHIP(hipEventCreate(&d->e0));
+  DHIP(hipEventCreate(&d->e1));
+  DHIP(hipMalloc((void**)&d->scratch, (size_t)d->scratch_bytes));
+  const int rc = dtype == SSN_F32 ? upload_table<float>(d.get(), table) : upload_table<double>(d.get(), table);
+  if (rc != SSN_OK) return rc;
+  *out = d.release();
+  return SSN_OK;
+}
+
+void ssn_decoder_destroy(ssn_decoder* dec) { delete dec; }
+
+int ssn_decoder_rows(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t* best, double* sims) {
+  if (!dec) return fail(SSN_EINVAL, "ssn_decoder_rows: null decoder");
+  if (n_rows < 0) return fail(SSN_EINVAL, "ssn_decoder_rows: negative n_rows");
+  if (n_rows == 0) return SSN_OK;
+  if (!rows || !best) return fail(SSN_EINVAL, "ssn_decoder_rows: null argument");
+  return dec->dtype == SSN_F32 ? decode_rows<float>(dec, rows, nullptr, 0, dec->K, n_rows, best, sims)
+                               : decode_rows<double>(dec, rows, nullptr, 0, dec->K, n_rows, best, sims);
+}
+
+int ssn_decoder_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows, int32_t* best, double* sims) {
+  if (!dec) return fail(SSN_EINVAL, "ssn_decoder_rows_device: null decoder");
+  if (n_rows < 0) return fail(SSN_EINVAL, "ssn_decoder_rows_device: negative n_rows");
+  if (rows_dtype != SSN_F32 && rows_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_rows_device: unknown rows_dtype %d", rows_dtype);
+  if (ld < dec->K) return fail(SSN_EINVAL, "ssn_decoder_rows_device: leading dimension %lld below the width %lld", (long long)ld, (long long)dec->K);
+  if (n_rows == 0) return SSN_OK;
+  if (!rows_dev || !best) return fail(SSN_EINVAL, "ssn_decoder_rows_device: null argument");
+  return dec->dtype == SSN_F32 ? decode_rows<float>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, sims)
+                               : decode_rows<double>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, sims);
+}
+
+int ssn_decoder_rows_composed(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t* best) {
+  if (!dec || !rows || !best || n_rows <= 0) return fail(SSN_EINVAL, "ssn_decoder_rows_composed: null or empty argument");
+  if (dec->dtype != SSN_F32) return fail(SSN_EUNSUPPORTED, "ssn_decoder_rows_composed: f32 decoders only (k_gemm_nt_mfma_f32)");
+  return decode_rows_composed(dec, rows, n_rows, best);
+}
+
+int ssn_decoder_get_info(ssn_decoder* dec, int64_t n_rows, ssn_decoder_info* out) {
+  if (!dec || !out || n_rows < 0) return fail(SSN_EINVAL, "ssn_decoder_get_info: null argument");
+  const Plan p = dec->plan(n_rows);
+  out->row_chunk = p.chunk_tiles * TILE;
+  out->n_chunks = n_rows ? p.n_chunks : 0;
+  out->n_strips = p.n_strips;
+  out->tiles_per_strip = p.tiles_per_strip;
+  out->tile = TILE;
+  out->scratch_bytes = dec->scratch_bytes;
+  out->min_scratch_bytes = dec->min_scratch();
+  out->slot_bytes = TILE * (int64_t)(dec->esz + 4);
+  out->padded_width = dec->Kp;
+  out->last_launches = dec->launches;
+  out->last_kernel_ms = dec->kernel_ms;
+  return SSN_OK;
+}
+
+}  // extern "C"

@@ -4097,6 +4097,6 @@ int ssn_device_count(void) {
   return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
 }
 const char* ssn_last_error(void) { return g_err.c_str(); }
-const char* ssn_version(void) { return "libssn_hip 0.10 (gfx950, ABI 10)"; }
+const char* ssn_version(void) { return "libssn_hip 0.11 (gfx950, ABI 11)"; }
 
 }  // extern "C"

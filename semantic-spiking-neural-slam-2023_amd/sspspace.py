@@ -161,6 +161,7 @@ class SSPSpace:
         self.length_scale = (scale * np.ones((self.domain_dim,))).reshape(-1, 1) if scale.size == 1 \
             else scale.reshape(-1, 1)
         self._grid_cache.clear()
+        self._drop_decoders()
 
     # -- sampling the domain --------------------------------------------------------------
     def get_sample_points(self, samples_per_dim=100, method="length-scale"):
@@ -227,11 +228,40 @@ class SSPSpace:
         return {"dft": dft, "lhs": interleave(E[1] * w[None, :]), "rhs": interleave(Er)}
 
     # -- decoding --------------------------------------------------------------------------
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_decoder_cache", None)          # device handles stay with the object they were made for
+        return state
+
+    def _drop_decoders(self):
+        for dec in self.__dict__.pop("_decoder_cache", {}).values():
+            dec.close()
+
+    def _grid_decoder(self, num_samples, sampling_method, dtype):
+        """The GridDecoder of backend="hip" for this sample set, kept next to ``_grid_cache`` (one at a time: it holds the table on
+        the GPU) and dropped by ``update_lengthscale``."""
+        from .decoding import GridDecoder
+        key = (int(num_samples), sampling_method, dtype)
+        if key not in self.__dict__.get("_decoder_cache", {}):
+            self._drop_decoders()
+            self._decoder_cache = {key: GridDecoder(self, num_samples, sampling_method, dtype=dtype)}
+        return self._decoder_cache[key]
+
     def decode(self, ssp, method="from-set", sampling_method="grid", num_samples=300,
-               samples=None, **kwargs):
+               samples=None, backend=None, **kwargs):
+        """``backend``: None (or "numpy") is the float64 host product below; "hip" / "hip-f64" run it on the GPU through a
+        ``decoding.GridDecoder`` (f32 matrix cores / f64 parity mode)."""
         if method != "from-set":
             raise NotImplementedError(
                 f"decode method {method!r}: only 'from-set' is on the SLAM hot path (SURVEY §2 row 6)")
+        if backend is not None:
+            from .decoding import GridDecoder, backend_dtype
+            dtype = backend_dtype(backend)
+            if dtype is not None and samples is None:
+                return self._grid_decoder(num_samples, sampling_method, dtype).decode(ssp)
+            if dtype is not None:
+                with GridDecoder(self, samples=samples, dtype=dtype) as dec:
+                    return dec.decode(ssp)
         ssp = np.atleast_2d(np.asarray(ssp, dtype=float))
         if samples is None:
             sample_ssps, sample_points = self.get_sample_pts_and_ssps(num_samples, sampling_method)
@@ -245,8 +275,8 @@ class SSPSpace:
             best[s:s + step] = np.argmax(sample_ssps @ unit[s:s + step].T, axis=0)
         return sample_points[best]
 
-    def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300):
-        return self.encode(self.decode(ssp, method, sampling_method, num_samples))
+    def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300, backend=None):
+        return self.encode(self.decode(ssp, method, sampling_method, num_samples, backend=backend))
 
     # -- algebra ---------------------------------------------------------------------------
     def normalize(self, ssp):

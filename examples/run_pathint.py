@@ -59,6 +59,8 @@ def parse(argv=None):
                    help="inhibit the oscillators' neurons (weight -10, through add_neuron_input()) for T0 < t <= T1")
     p.add_argument("--decode-backend", default="numpy", choices=["numpy", "hip"],
                    help="grid decode of the probed trajectory: NumPy on the host, or the GPU grid decoder (decoding.GridDecoder)")
+    p.add_argument("--decode-refine", action="store_true",
+                   help="also decode with 'grid-refine' (Newton steps from the grid point) and print both position errors")
     return p.parse_args(argv)
 
 
@@ -114,6 +116,11 @@ def main(argv=None):
           "to the true SSP mean %.4f, final position error %.4f" % (space.ssp_dim, (space.ssp_dim + 1) // 2, args.pi_n_neurons, T,
                                                                    build_time, elapsed_time, T / elapsed_time, decode_time,
                                                                    args.decode_backend, sims[min(200, n - 1):].mean(), err[-1]))
+    if args.decode_refine:
+        t0 = time.time()
+        _, _, err_r = H.pathint_metrics(space, out, pm.real_ssp[:n], path[:n], backend=args.decode_backend, refine=True)
+        print("position error, grid decode | grid-refine (%.2f s): median %.4f | %.4f, mean %.4f | %.4f, final %.4f | %.4f" % (
+            time.time() - t0, np.median(err), np.median(err_r), err.mean(), err_r.mean(), err[-1], err_r[-1]))
     if args.save:
         os.makedirs(args.save_dir, exist_ok=True)
         name = "pi_backend_%s%s_sspdim_%d_pinneurons_%d_T_%d_limit_%s_seed_%d.npz" % (

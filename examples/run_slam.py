@@ -47,6 +47,8 @@ def parse(argv=None):
     p.add_argument("--n-eval-points", default=0, type=int, help="decoder-solve evaluation points; 0 = nengo's default")
     p.add_argument("--decode-backend", default="numpy", choices=["numpy", "hip"],
                    help="grid decodes of the trajectory and the recalled map: NumPy on the host, or the GPU grid decoder")
+    p.add_argument("--decode-refine", action="store_true",
+                   help="also decode with 'grid-refine' (Newton steps from the grid point) and print both sets of errors")
     return p.parse_args(argv)
 
 
@@ -86,6 +88,14 @@ def main(argv=None):
           "%.4f, final position error %.4f; recalled landmark positions: median error %.3f" % (
               space.ssp_dim, T, build_time, elapsed, T / elapsed, decode_time, args.decode_backend, sims[min(200, n - 1):].mean(),
               err[-1], float(np.median(lm_err))))
+    if args.decode_refine:
+        t0 = time.time()
+        _, _, err_r = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n], backend=args.decode_backend, refine=True)
+        _, lm_locs_r = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend, refine=True)
+        lm_err_r = np.linalg.norm(lm_locs_r - sm.obj_locs, axis=1)
+        print("grid decode | grid-refine (%.2f s): position error median %.4f | %.4f, final %.4f | %.4f; recalled landmark "
+              "positions: median error %.4f | %.4f" % (time.time() - t0, np.median(err), np.median(err_r), err[-1], err_r[-1],
+                                                      float(np.median(lm_err)), float(np.median(lm_err_r))))
     if args.save:
         os.makedirs(args.save_dir, exist_ok=True)
         name = "slam_backend_%s%s_sspdim_%d_pinneurons_%d_memnneurons_%d_ccnneurons_%d_T_%d_limit_%s_seed_%d.npz" % (

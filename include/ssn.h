@@ -398,6 +398,25 @@ int ssn_decoder_get_info(ssn_decoder* dec, int64_t n_rows, ssn_decoder_info* out
  * an n_rows x n_samples buffer (at most 2 GB, allocated for the call), then k_argmax_partial; f32 decoders, one row chunk. */
 int ssn_decoder_rows_composed(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t* best);
 
+/* Sub-grid refinement of the grid decode (additive to ABI 11; the rule is written out at k_decode_refine in csrc/ssn_decode.hip and
+ * in DESIGN.md 3.12): from the grid argmax x0 of a row, `iterations` safeguarded Newton steps on
+ *   f(x) = sum_k c_k cos(M_k . x) + s_k sin(M_k . x),   c_k + i s_k = w_k fft(row / |row|)_k,
+ * clipped to the box [max(lo, x0 - pitch), min(hi, x0 + pitch)].  ssn_decoder_set_refine uploads the tables (all host doubles, C
+ * order): dft (2K x width: row 2k = Re, row 2k + 1 = Im of exp(-2 pi i k c / width), unweighted - w is folded in here), M (K x dim,
+ * phase_matrix / length_scale of the K bins used), w (K), points (n_samples x dim: the decoder's sample points), lo / hi / pitch
+ * (dim each).  dim is 1, 2 or 3.  It may be called again to replace the tables.
+ * ssn_decoder_refine_rows* then fill host arrays: x (n_rows x dim), best (the grid index), f (f at x) and status (bit 1: x on a box
+ * face, 2: Hessian not negative definite at x, 4: last step above 1e-6 pitch on some axis); best, f and status may be NULL.
+ * iterations == 0 returns points[best] exactly.  The results do not depend on the scratch size and are the same from run to run.
+ * SSN_EINVAL: null handle or argument, dim outside 1..3, negative iterations, refinement before ssn_decoder_set_refine;
+ * n_rows == 0 succeeds and writes nothing. */
+int ssn_decoder_set_refine(ssn_decoder* dec, const double* dft, int64_t K, const double* M, const double* w, int32_t dim,
+                           const double* points, const double* lo, const double* hi, const double* pitch);
+int ssn_decoder_refine_rows(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t iterations, double* x, int32_t* best,
+                            double* f, int32_t* status);
+int ssn_decoder_refine_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows,
+                                   int32_t iterations, double* x, int32_t* best, double* f, int32_t* status);
+
 int ssn_get_counters(ssn_sim* sim, ssn_counters* out);
 /* Fills at most `capacity` entries; returns the number of kernels with timed launches (or a negative status). */
 int ssn_get_kernel_times(ssn_sim* sim, ssn_kernel_time* out, int32_t capacity);

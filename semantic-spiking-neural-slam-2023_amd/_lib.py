@@ -132,6 +132,11 @@ EXPORTS = {
     "ssn_decoder_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "ssn_decoder_get_info": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(DecoderInfo)]),
     "ssn_decoder_rows_composed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ssn_decoder_set_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "ssn_decoder_refine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssn_decoder_refine_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "ssn_get_counters": (C.c_int, [C.c_void_p, C.POINTER(Counters)]),
     "ssn_get_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(KernelTime), C.c_int32]),
     "ssn_n_steps": (C.c_int64, [C.c_void_p]),
@@ -160,7 +165,11 @@ def load():
         pass
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in EXPORTS.items():
-        fn = getattr(lib, name)          # AttributeError if a declared symbol is not exported
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(f"{LIB_PATH} does not export {name}: it was built from older sources, rebuild it with "
+                              "`make -C semantic-spiking-neural-slam-2023_amd/csrc`") from None
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib

@@ -225,6 +225,196 @@ __global__ __launch_bounds__(256) void k_decode_finish(const T* __restrict__ pva
   if (lane == 0) { sims[r] = acc; best[r] = c; }
 }
 
+// ---- sub-grid refinement of the grid decode (ssn_decoder_refine_rows*) -------------------------------------------------------
+// The rule, which SSPSpace.decode(method='grid-refine') follows in float64 NumPy:
+//   setup   u = the row scaled as above;  c_k + i s_k = w_k fft(u)_k over the K bins of ssn_decoder_set_refine (half spectrum,
+//           w = 1/d, 2/d, 2/d ..., when the phase matrix is conjugate-symmetric, else all d bins with w = 1/d);  M = phase_matrix /
+//           length_scale;  x0 = points[best], the grid argmax;  box = [max(lo, x0 - pitch), min(hi, x0 + pitch)] per axis.
+//   f(x)    = sum_k c_k cos(th_k) + s_k sin(th_k),  th_k = M_k . x          ( = <encode(x), u> )
+//   g_a     = sum_k M_ka (s_k cos th_k - c_k sin th_k),    (-H)_ab = sum_k M_ka M_kb (c_k cos th_k + s_k sin th_k)
+//   step    (exactly `iterations` of them; no data-dependent exit and no comparison of values of f, which f32 cannot rank at a
+//           maximum)  Cholesky of -H, pivot j = (-H)_jj - sum_{i<j} L_ji^2;  when every pivot exceeds 1e-6 max_i (-H)_ii:
+//           p = (-H)^-1 g;  otherwise p = g / max_i |H_ii| (0 when that is 0);  x <- min(max(x + p, box lo), box hi).
+//   output  x;  f(x);  status bit 1: x on a box face, 2: -H not positive definite by that test at x, 4: the last step moved some
+//           axis by more than 1e-6 pitch.  iterations == 0 gives points[best] exactly; an axis whose value still is the rounding of
+//           x0 to the decoder's dtype reports x0 itself, so a zero row returns x0.
+// Spectrum: the scaled, padded rows of k_decode_prepare times the (2K x Kp) table with w folded in, (Re, Im) interleaved:
+// launch_gemm_nt<float> with one split (every entry the k-ordered fmaf chain over Kp), k_decode_spectrum in f64.
+// k_decode_refine<T, DIM>: one wave64 per row, lane l owns bins l, l + 64, ...; up to REFINE_CAP bins per lane (K <= 512, d = 1015
+// has 508) stay in registers with their M rows, above that they are read again from the spectrum area every step.  th is an fma
+// chain in axis order, sincosf / sincos with full range reduction (|th| reaches hundreds of radians), 1 + DIM + DIM (DIM + 1) / 2
+// partial sums per lane in bin order, one xor butterfly (both partners add the same two values, so every lane holds the same
+// bits), and the small solve redundantly in every lane.  No atomics, no LDS.  tools/kernel_resources.py ssn_decode.hip
+// k_decode_refine: f32 125 / 130 / 204 VGPR for DIM 1 / 2 / 3, f64 188 / 250 / 254, no AGPR, no scratch (the slow path of the range
+// reduction stays in registers), no spills, occupancy 2 - 4.
+constexpr int REFINE_CAP = 8;
+
+__device__ __forceinline__ void sin_cos(float t, float* s, float* c) { sincosf(t, s, c); }
+__device__ __forceinline__ void sin_cos(double t, double* s, double* c) { sincos(t, s, c); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_decode_spectrum(const T* __restrict__ rows, const T* __restrict__ dft, int Kp, int N, T* __restrict__ spec) {
+  const int j = blockIdx.y * 256 + threadIdx.x;
+  if (j >= N) return;
+  const T* __restrict__ u = rows + (size_t)blockIdx.x * Kp;
+  const T* __restrict__ w = dft + (size_t)j * Kp;
+  T acc = T(0);
+  for (int k = 0; k < Kp; ++k) acc = fma(u[k], w[k], acc);
+  spec[(size_t)blockIdx.x * N + j] = acc;
+}
+
+// one bin into the partial sums: acc[0] = f, acc[1 ..] = g, then the upper triangle of -H row by row
+template <typename T, int DIM>
+__device__ __forceinline__ void refine_bin(T c, T s, const T* m, const T* x, T* acc) {
+  T th = m[0] * x[0];
+#pragma unroll
+  for (int a = 1; a < DIM; ++a) th = fma(m[a], x[a], th);
+  T sn, cs;
+  sin_cos(th, &sn, &cs);
+  const T v = fma(c, cs, s * sn), dv = fma(s, cs, -(c * sn));
+  acc[0] += v;
+  int q = 1 + DIM;
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) {
+    acc[1 + a] = fma(m[a], dv, acc[1 + a]);
+#pragma unroll
+    for (int b = a; b < DIM; ++b) { acc[q] = fma(m[a] * m[b], v, acc[q]); ++q; }
+  }
+}
+
+// the step from the reduced sums; returns whether -H passed the Cholesky test
+template <typename T, int DIM>
+__device__ __forceinline__ bool refine_step(const T* acc, T* p) {
+  T A[DIM][DIM], L[DIM][DIM];
+  int q = 1 + DIM;
+#pragma unroll
+  for (int a = 0; a < DIM; ++a)
+#pragma unroll
+    for (int b = a; b < DIM; ++b) { A[a][b] = acc[q]; A[b][a] = acc[q]; ++q; }
+  T dmax = A[0][0], amax = fabs(A[0][0]);
+#pragma unroll
+  for (int a = 1; a < DIM; ++a) { dmax = fmax(dmax, A[a][a]); amax = fmax(amax, fabs(A[a][a])); }
+  bool pd = dmax > T(0);
+  const T floor_ = T(1e-6) * dmax;
+#pragma unroll
+  for (int j = 0; j < DIM; ++j) {
+    T piv = A[j][j];
+#pragma unroll
+    for (int i = 0; i < j; ++i) piv = fma(-L[j][i], L[j][i], piv);
+    if (!(piv > floor_)) pd = false;
+    const T ljj = sqrt(pd ? piv : T(1));
+    L[j][j] = ljj;
+#pragma unroll
+    for (int r = j + 1; r < DIM; ++r) {
+      T v = A[r][j];
+#pragma unroll
+      for (int i = 0; i < j; ++i) v = fma(-L[r][i], L[j][i], v);
+      L[r][j] = v / ljj;
+    }
+  }
+  if (pd) {
+    T y[DIM];
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) {
+      T v = acc[1 + j];
+#pragma unroll
+      for (int i = 0; i < j; ++i) v = fma(-L[j][i], y[i], v);
+      y[j] = v / L[j][j];
+    }
+#pragma unroll
+    for (int j = DIM - 1; j >= 0; --j) {
+      T v = y[j];
+#pragma unroll
+      for (int i = j + 1; i < DIM; ++i) v = fma(-L[i][j], p[i], v);
+      p[j] = v / L[j][j];
+    }
+  } else {
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) p[a] = amax > T(0) ? acc[1 + a] / amax : T(0);
+  }
+  return pd;
+}
+
+template <typename T, int DIM>
+__global__ __launch_bounds__(256) void k_decode_refine(const T* __restrict__ spec, int K, const T* __restrict__ Mt, const double* __restrict__ points,
+                                                       const int* __restrict__ best, const double* __restrict__ box, int n_rows, int iterations,
+                                                       double* __restrict__ xout, double* __restrict__ fout, int* __restrict__ status) {
+  constexpr int NS = 1 + DIM + DIM * (DIM + 1) / 2;
+  const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n_rows) return;
+  const T* __restrict__ sp = spec + (size_t)row * 2 * K;
+  const bool in_regs = K <= 64 * REFINE_CAP;
+  T c[REFINE_CAP], s[REFINE_CAP], m[REFINE_CAP][DIM];
+  if (in_regs) {
+#pragma unroll
+    for (int j = 0; j < REFINE_CAP; ++j) {
+      const int k = lane + 64 * j;
+      const bool ok = k < K;
+      c[j] = ok ? sp[2 * k] : T(0);
+      s[j] = ok ? sp[2 * k + 1] : T(0);
+#pragma unroll
+      for (int a = 0; a < DIM; ++a) m[j][a] = ok ? Mt[(size_t)k * DIM + a] : T(0);
+    }
+  }
+  const size_t b = (size_t)best[row];
+  double x0[DIM], lo_d[DIM], hi_d[DIM];
+  T x[DIM], lo[DIM], hi[DIM], tol[DIM], last[DIM];
+#pragma unroll
+  for (int a = 0; a < DIM; ++a) {
+    x0[a] = points[b * DIM + a];
+    const double pitch = box[2 * DIM + a];
+    lo_d[a] = fmax(box[a], x0[a] - pitch);
+    hi_d[a] = fmin(box[DIM + a], x0[a] + pitch);
+    x[a] = (T)x0[a]; lo[a] = (T)lo_d[a]; hi[a] = (T)hi_d[a];
+    tol[a] = (T)(1e-6 * pitch);
+    last[a] = T(0);
+  }
+  T fval = T(0);
+  bool pd = false;
+  for (int it = 0;; ++it) {
+    T acc[NS];
+#pragma unroll
+    for (int q = 0; q < NS; ++q) acc[q] = T(0);
+    if (in_regs) {
+#pragma unroll
+      for (int j = 0; j < REFINE_CAP; ++j) refine_bin<T, DIM>(c[j], s[j], m[j], x, acc);
+    } else {
+      for (int k = lane; k < K; k += 64) {
+        T mk[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) mk[a] = Mt[(size_t)k * DIM + a];
+        refine_bin<T, DIM>(sp[2 * k], sp[2 * k + 1], mk, x, acc);
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+      for (int q = 0; q < NS; ++q) acc[q] += __shfl_xor(acc[q], off, 64);
+    T p[DIM];
+    pd = refine_step<T, DIM>(acc, p);
+    fval = acc[0];
+    if (it >= iterations) break;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+      const T xn = fmin(fmax(x[a] + p[a], lo[a]), hi[a]);
+      last[a] = xn - x[a];
+      x[a] = xn;
+    }
+  }
+  if (lane == 0) {
+    int st = pd ? 0 : 2;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+      if (x[a] <= lo[a] || x[a] >= hi[a]) st |= 1;
+      if (fabs(last[a]) > tol[a]) st |= 4;
+      const double xa = x[a] == (T)x0[a] ? x0[a] : (double)x[a];
+      xout[(size_t)row * DIM + a] = fmin(fmax(xa, lo_d[a]), hi_d[a]);
+    }
+    fout[row] = (double)fval;
+    status[row] = st;
+  }
+}
+
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 }  // namespace
@@ -272,6 +462,18 @@ struct ssn_decoder {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   double kernel_ms = 0.0;          // of the last ssn_decoder_rows* call
   int64_t launches = 0;
+  // refinement (ssn_decoder_set_refine): buffers of its own, beside the scratch area, so the plan stays what it was
+  int r_dim = 0;
+  int64_t r_K = 0, r_rows = 0;     // bins; rows the work area holds
+  void *r_dft = nullptr, *r_M = nullptr;      // (2 r_K x Kp) table with w folded in, (r_K x r_dim) phases, both in the decoder's dtype
+  double *r_points = nullptr, *r_box = nullptr;      // (S x r_dim) sample points; lo, hi, pitch (r_dim each)
+  char* r_work = nullptr;          // per row: 2 r_K spectrum values, r_dim + 1 doubles (x, f), one status word
+
+  void drop_refine() {
+    for (void* p : {r_dft, r_M, (void*)r_points, (void*)r_box, (void*)r_work}) if (p) (void)hipFree(p);
+    r_dft = r_M = nullptr; r_points = r_box = nullptr; r_work = nullptr;
+    r_dim = 0; r_K = r_rows = 0;
+  }
 
   int64_t row_bytes(int64_t slots) const { return K * 8 + Kp * (int64_t)esz + slots * (int64_t)(esz + 4) + 12; }
   int64_t min_scratch() const { return TILE * row_bytes(1); }
@@ -310,6 +512,7 @@ struct ssn_decoder {
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (stream) (void)hipStreamDestroy(stream);
+    drop_refine();
     if (table) (void)hipFree(table);
     if (scratch) (void)hipFree(scratch);
   }
@@ -357,13 +560,65 @@ hipError_t launch_prepare(ssn_decoder* d, const TI* src, int64_t ld, int n, int 
   return hipGetLastError();
 }
 
-// rows: host doubles (dense, width K) or device rows of dtype rows_dtype with leading dimension ld
+struct RefineOut {      // host arrays of ssn_decoder_refine_rows*; f and status may be null
+  int iterations;
+  double* x;
+  double* f;
+  int32_t* status;
+};
+
 template <typename T>
-int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t n_rows, int32_t* best, double* sims) {
+struct RefineAreas {      // the regions of the refiner's work area for `rows` rows
+  T* spec; double* x; double* f; int* status;
+  RefineAreas(const ssn_decoder* d, int64_t rows) {
+    char* p = d->r_work;
+    x = (double*)p; p += (size_t)rows * d->r_dim * 8;
+    f = (double*)p; p += (size_t)rows * 8;
+    spec = (T*)p; p += (size_t)rows * 2 * d->r_K * sizeof(T);
+    status = (int*)p;
+  }
+  static size_t bytes(const ssn_decoder* d, int64_t rows) { return (size_t)rows * ((size_t)d->r_dim * 8 + 8 + 2 * (size_t)d->r_K * sizeof(T) + 4); }
+};
+
+template <typename T, int DIM>
+hipError_t launch_refine(ssn_decoder* d, const RefineAreas<T>& ra, const int* best, int n, int iterations) {
+  hipLaunchKernelGGL((k_decode_refine<T, DIM>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, d->stream, (const T*)ra.spec, (int)d->r_K, (const T*)d->r_M,
+                     (const double*)d->r_points, best, (const double*)d->r_box, n, iterations, ra.x, ra.f, ra.status);
+  return hipGetLastError();
+}
+
+// the spectrum of the prepared rows of a chunk, then the Newton steps from the chunk's grid argmax
+template <typename T>
+hipError_t refine_chunk(ssn_decoder* d, const RefineAreas<T>& ra, const T* conv, const int* best, int n, int iterations) {
+  hipError_t e;
+  if constexpr (sizeof(T) == 4) {
+    e = ssn::launch_gemm_nt<float>(d->stream, conv, (int)d->Kp, (const float*)d->r_dft, (int)d->Kp, ra.spec, (int)(2 * d->r_K), n, (int)(2 * d->r_K), (int)d->Kp, 1);
+  } else {
+    hipLaunchKernelGGL((k_decode_spectrum<T>), dim3((unsigned)n, (unsigned)((2 * d->r_K + 255) / 256)), dim3(256), 0, d->stream, conv, (const T*)d->r_dft,
+                       (int)d->Kp, (int)(2 * d->r_K), ra.spec);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return e;
+  return d->r_dim == 1 ? launch_refine<T, 1>(d, ra, best, n, iterations) : d->r_dim == 2 ? launch_refine<T, 2>(d, ra, best, n, iterations)
+                                                                                         : launch_refine<T, 3>(d, ra, best, n, iterations);
+}
+
+// rows: host doubles (dense, width K) or device rows of dtype rows_dtype with leading dimension ld; ro: also refine (best may be null then)
+template <typename T>
+int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t n_rows, int32_t* best, double* sims,
+                const RefineOut* ro = nullptr) {
   DevGuard g(d->device);
   const Plan p = d->plan(n_rows);
   const int64_t cap_rows = p.chunk_tiles * TILE;
   const Areas<T> a(d, cap_rows, p.slots);
+  if (ro && d->r_rows < cap_rows) {      // the work area follows the row chunk; it only ever grows
+    if (d->r_work) (void)hipFree(d->r_work);
+    d->r_work = nullptr;
+    d->r_rows = 0;
+    DHIP(hipMalloc((void**)&d->r_work, RefineAreas<T>::bytes(d, cap_rows)));
+    d->r_rows = cap_rows;
+  }
+  const RefineAreas<T> ra(d, ro ? d->r_rows : 0);
   d->kernel_ms = 0.0;
   d->launches = 0;
   for (int64_t r0 = 0; r0 < n_rows; r0 += cap_rows) {
@@ -379,15 +634,42 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
     hipLaunchKernelGGL((k_decode_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, d->stream, a.pval, a.pcol, (int)cap_rows, (int)p.n_strips,
                        n, (const T*)a.conv, (const T*)d->table, (int)d->Kp, a.sims, a.best);
     DHIP(hipGetLastError());
+    if (ro) DHIP(refine_chunk<T>(d, ra, (const T*)a.conv, a.best, n, ro->iterations));
     DHIP(hipEventRecord(d->e1, d->stream));
-    DHIP(hipMemcpyAsync(best + r0, a.best, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+    if (best) DHIP(hipMemcpyAsync(best + r0, a.best, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
     if (sims) DHIP(hipMemcpyAsync(sims + r0, a.sims, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    if (ro) {
+      DHIP(hipMemcpyAsync(ro->x + (size_t)r0 * d->r_dim, ra.x, (size_t)n * d->r_dim * 8, hipMemcpyDeviceToHost, d->stream));
+      if (ro->f) DHIP(hipMemcpyAsync(ro->f + r0, ra.f, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+      if (ro->status) DHIP(hipMemcpyAsync(ro->status + r0, ra.status, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+    }
     DHIP(hipStreamSynchronize(d->stream));
     float ms = 0.0f;
     DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
     d->kernel_ms += ms;
-    d->launches += 3;
+    d->launches += ro ? 5 : 3;
   }
+  return SSN_OK;
+}
+
+template <typename T>
+int upload_refine(ssn_decoder* d, const double* dft, const double* M, const double* w, const double* points, const double* lo, const double* hi,
+                  const double* pitch) {
+  const int64_t K = d->r_K, Kp = d->Kp, width = d->K, dim = d->r_dim;
+  std::vector<T> tab((size_t)2 * K * Kp, T(0)), m((size_t)K * dim);
+  for (int64_t r = 0; r < 2 * K; ++r)
+    for (int64_t c = 0; c < width; ++c) tab[(size_t)r * Kp + c] = (T)(w[r / 2] * dft[(size_t)r * width + c]);
+  for (int64_t i = 0; i < K * dim; ++i) m[i] = (T)M[i];
+  std::vector<double> box((size_t)3 * dim);
+  for (int64_t a = 0; a < dim; ++a) { box[a] = lo[a]; box[dim + a] = hi[a]; box[2 * dim + a] = pitch[a]; }
+  DHIP(hipMalloc(&d->r_dft, tab.size() * sizeof(T)));
+  DHIP(hipMalloc(&d->r_M, m.size() * sizeof(T)));
+  DHIP(hipMalloc((void**)&d->r_points, (size_t)d->S * dim * 8));
+  DHIP(hipMalloc((void**)&d->r_box, box.size() * 8));
+  DHIP(hipMemcpy(d->r_dft, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice));
+  DHIP(hipMemcpy(d->r_M, m.data(), m.size() * sizeof(T), hipMemcpyHostToDevice));
+  DHIP(hipMemcpy(d->r_points, points, (size_t)d->S * dim * 8, hipMemcpyHostToDevice));
+  DHIP(hipMemcpy(d->r_box, box.data(), box.size() * 8, hipMemcpyHostToDevice));
   return SSN_OK;
 }
 
@@ -491,6 +773,52 @@ int ssn_decoder_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows
   if (!rows_dev || !best) return fail(SSN_EINVAL, "ssn_decoder_rows_device: null argument");
   return dec->dtype == SSN_F32 ? decode_rows<float>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, sims)
                                : decode_rows<double>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, sims);
+}
+
+int ssn_decoder_set_refine(ssn_decoder* dec, const double* dft, int64_t K, const double* M, const double* w, int32_t dim, const double* points,
+                           const double* lo, const double* hi, const double* pitch) {
+  if (!dec) return fail(SSN_EINVAL, "ssn_decoder_set_refine: null decoder");
+  if (!dft || !M || !w || !points || !lo || !hi || !pitch) return fail(SSN_EINVAL, "ssn_decoder_set_refine: null argument");
+  if (dim < 1 || dim > 3) return fail(SSN_EINVAL, "ssn_decoder_set_refine: dim %d is not supported: k_decode_refine exists for dim 1, 2 and 3", dim);
+  if (K < 1 || K > dec->K) return fail(SSN_EINVAL, "ssn_decoder_set_refine: %lld bins outside 1 .. width %lld", (long long)K, (long long)dec->K);
+  DevGuard g(dec->device);
+  dec->drop_refine();
+  dec->r_dim = dim;
+  dec->r_K = K;
+  const int rc = dec->dtype == SSN_F32 ? upload_refine<float>(dec, dft, M, w, points, lo, hi, pitch) : upload_refine<double>(dec, dft, M, w, points, lo, hi, pitch);
+  if (rc != SSN_OK) dec->drop_refine();
+  return rc;
+}
+
+static int refine_args(const char* who, ssn_decoder* dec, int64_t n_rows, int32_t iterations) {
+  if (!dec) return fail(SSN_EINVAL, "%s: null decoder", who);
+  if (n_rows < 0) return fail(SSN_EINVAL, "%s: negative n_rows", who);
+  if (iterations < 0) return fail(SSN_EINVAL, "%s: negative iterations", who);
+  if (!dec->r_dim) return fail(SSN_EINVAL, "%s: no refinement tables: call ssn_decoder_set_refine first", who);
+  return SSN_OK;
+}
+
+int ssn_decoder_refine_rows(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t iterations, double* x, int32_t* best, double* f,
+                            int32_t* status) {
+  const int rc = refine_args("ssn_decoder_refine_rows", dec, n_rows, iterations);
+  if (rc != SSN_OK || n_rows == 0) return rc;
+  if (!rows || !x) return fail(SSN_EINVAL, "ssn_decoder_refine_rows: null argument");
+  const RefineOut ro{iterations, x, f, status};
+  return dec->dtype == SSN_F32 ? decode_rows<float>(dec, rows, nullptr, 0, dec->K, n_rows, best, nullptr, &ro)
+                               : decode_rows<double>(dec, rows, nullptr, 0, dec->K, n_rows, best, nullptr, &ro);
+}
+
+int ssn_decoder_refine_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows, int32_t iterations,
+                                   double* x, int32_t* best, double* f, int32_t* status) {
+  const int rc = refine_args("ssn_decoder_refine_rows_device", dec, n_rows, iterations);
+  if (rc != SSN_OK) return rc;
+  if (rows_dtype != SSN_F32 && rows_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_refine_rows_device: unknown rows_dtype %d", rows_dtype);
+  if (ld < dec->K) return fail(SSN_EINVAL, "ssn_decoder_refine_rows_device: leading dimension %lld below the width %lld", (long long)ld, (long long)dec->K);
+  if (n_rows == 0) return SSN_OK;
+  if (!rows_dev || !x) return fail(SSN_EINVAL, "ssn_decoder_refine_rows_device: null argument");
+  const RefineOut ro{iterations, x, f, status};
+  return dec->dtype == SSN_F32 ? decode_rows<float>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, nullptr, &ro)
+                               : decode_rows<double>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, nullptr, &ro);
 }
 
 int ssn_decoder_rows_composed(ssn_decoder* dec, const double* rows, int64_t n_rows, int32_t* best) {

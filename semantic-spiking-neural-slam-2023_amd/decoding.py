@@ -46,7 +46,7 @@ class GridDecoder:
     """
 
     def __init__(self, ssp_space=None, num_samples=100, sampling_method="grid", samples=None, dtype="f32", device=0,
-                 scratch_bytes=None):
+                 scratch_bytes=None, trust=None):
         if dtype not in ("f32", "f64"):
             raise ValueError(f"dtype must be 'f32' or 'f64', got {dtype!r}")
         if samples is None:
@@ -60,6 +60,9 @@ class GridDecoder:
             raise ValueError(f"sample_ssps must be (n_samples, width), got shape {table.shape}")
         self.ssp_space = ssp_space
         self.sample_points = np.asarray(sample_points)
+        # the box of refine(): the pitch of the space's own grid, or trust= beside samples=
+        self._grid = (num_samples, sampling_method) if samples is None else None
+        self._trust, self._refine_key = trust, None
         self.n_samples, self.width = int(table.shape[0]), int(table.shape[1])
         self.dtype, self.device = dtype, int(device)
         self._lib = _lib.load()
@@ -103,12 +106,8 @@ class GridDecoder:
         return {name: getattr(out, name) for name, _ in _lib.DecoderInfo._fields_}
 
     # -- decoding ------------------------------------------------------------------------------
-    def indices(self, rows, return_sims=False):
-        """Index of the best sample of every row (int64, lowest index on ties); with ``return_sims`` also the similarity of the
-        scaled row to it.  ``rows``: array-like ``(T, width)`` (or one row), or a torch tensor on the decoder's device (float32 /
-        float64, any row stride), which is read in place."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
+    def _rows_arg(self, rows):
+        """(rows, n, device call arguments or None): host rows as a C-contiguous float64 array, device tensors as they are."""
         tensor = hasattr(rows, "is_cuda") and hasattr(rows, "data_ptr")
         if tensor and not rows.is_cuda:
             rows, tensor = rows.detach().numpy(), False
@@ -133,16 +132,76 @@ class GridDecoder:
             if rows.ndim != 2 or rows.shape[1] != self.width:
                 raise ValueError(f"rows must be (T, {self.width}), got {rows.shape}")
             n = int(rows.shape[0])
+        if tensor:
+            return rows, n, (rows.data_ptr() if n else None, _lib.SSN_F32 if rows.dtype == torch.float32 else _lib.SSN_F64, ld)
+        return rows, n, None
+
+    def indices(self, rows, return_sims=False):
+        """Index of the best sample of every row (int64, lowest index on ties); with ``return_sims`` also the similarity of the
+        scaled row to it.  ``rows``: array-like ``(T, width)`` (or one row), or a torch tensor on the decoder's device (float32 /
+        float64, any row stride), which is read in place."""
+        if self.closed:
+            raise fe.SimulationError("the decoder is closed")
+        rows, n, dev = self._rows_arg(rows)
         best = np.empty(n, dtype=np.int32)
         sims = np.empty(n, dtype=np.float64) if return_sims else None
         sims_p = sims.ctypes.data if return_sims else None
-        if tensor:
-            code = _lib.SSN_F32 if rows.dtype == torch.float32 else _lib.SSN_F64
-            self._check(self._lib.ssn_decoder_rows_device(self._h, rows.data_ptr() if n else None, code, ld, n, best.ctypes.data, sims_p))
+        if dev:
+            self._check(self._lib.ssn_decoder_rows_device(self._h, dev[0], dev[1], dev[2], n, best.ctypes.data, sims_p))
         else:
             self._check(self._lib.ssn_decoder_rows(self._h, rows.ctypes.data, n, best.ctypes.data, sims_p))
         best = best.astype(np.int64)
         return (best, sims) if return_sims else best
+
+    def _set_refine(self, trust=None):
+        """Build and upload the refinement tables on first use (again when ``trust`` changes)."""
+        space = self.ssp_space
+        if space is None:
+            raise ValueError("refine needs the decoder's ssp_space (its phase matrix and length scale)")
+        if space.ssp_dim != self.width or self.sample_points.ndim != 2 or self.sample_points.shape != (self.n_samples, space.domain_dim):
+            raise ValueError(f"refine needs samples of the decoder's ssp_space: ({self.n_samples}, {space.ssp_dim}) SSPs with "
+                             f"({self.n_samples}, {space.domain_dim}) points, got width {self.width} and points {self.sample_points.shape}")
+        if space.domain_dim > 3:
+            raise ValueError(f"refine supports domain_dim 1, 2 and 3, not domain_dim {space.domain_dim}")
+        trust = self._trust if trust is None else trust
+        if trust is None and self._grid is None:
+            raise ValueError("refine on a decoder made with samples= needs trust=: the half width of the box around the best sample")
+        key = ("grid",) if trust is None else tuple(np.atleast_1d(np.asarray(trust, dtype=float)).tolist())
+        if key == self._refine_key:
+            return
+        lo, hi, pitch = space.refine_box(*(self._grid or (None, None)), trust=trust)
+        K, M, w = space.refine_tables()
+        d = self.width
+        W = np.exp(-2j * np.pi * np.outer(np.arange(K), np.arange(d)) / d)
+        dft = np.empty((2 * K, d))
+        dft[0::2], dft[1::2] = W.real, W.imag
+        pts = np.ascontiguousarray(self.sample_points, dtype=np.float64)
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (dft, M, w, pts, lo, hi, pitch)]
+        self._check(self._lib.ssn_decoder_set_refine(self._h, arrs[0].ctypes.data, K, arrs[1].ctypes.data, arrs[2].ctypes.data, space.domain_dim,
+                                                     arrs[3].ctypes.data, arrs[4].ctypes.data, arrs[5].ctypes.data, arrs[6].ctypes.data))
+        self._refine_key = key
+
+    def refine(self, rows, iterations=8, return_info=False, trust=None):
+        """The grid decode followed by ``iterations`` safeguarded Newton steps per row on ``<encode(x), row>`` inside the box
+        ``x0 +- pitch`` (``k_decode_refine``): ``(T, dim)`` float64 points; with ``return_info`` also ``f`` (the
+        similarity at x), ``status`` (bit 1: on a box face, 2: Hessian not negative definite at x, 4: last step above
+        1e-6 pitch) and ``best`` (the grid index).  Rows as ``indices`` takes them.  ``iterations=0`` is the grid decode."""
+        if self.closed:
+            raise fe.SimulationError("the decoder is closed")
+        iterations = int(iterations)
+        if iterations < 0:
+            raise ValueError(f"iterations must be >= 0, got {iterations}")
+        self._set_refine(trust)
+        rows, n, dev = self._rows_arg(rows)
+        dim = self.sample_points.shape[1]
+        x = np.empty((n, dim), dtype=np.float64)
+        best, f, status = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int32)
+        out = (x.ctypes.data, best.ctypes.data, f.ctypes.data, status.ctypes.data)
+        if dev:
+            self._check(self._lib.ssn_decoder_refine_rows_device(self._h, dev[0], dev[1], dev[2], n, iterations, *out))
+        else:
+            self._check(self._lib.ssn_decoder_refine_rows(self._h, rows.ctypes.data, n, iterations, *out))
+        return (x, f, status, best.astype(np.int64)) if return_info else x
 
     def indices_composed(self, rows):
         """Measurement aid (tools/bench_decode.py): the same indices from the composition this decoder replaces - the similarity
@@ -157,8 +216,11 @@ class GridDecoder:
         self._check(self._lib.ssn_decoder_rows_composed(self._h, rows.ctypes.data, rows.shape[0], best.ctypes.data))
         return best.astype(np.int64)
 
-    def decode(self, rows, return_sims=False):
-        """``sample_points[best]``: what ``SSPSpace.decode(rows, 'from-set', ..., samples=...)`` returns."""
+    def decode(self, rows, return_sims=False, refine=False, iterations=8):
+        """``sample_points[best]``: what ``SSPSpace.decode(rows, 'from-set', ..., samples=...)`` returns.  ``refine=True`` is
+        shorthand for ``refine(rows, iterations)``."""
+        if refine:
+            return self.refine(rows, iterations)
         if return_sims:
             best, sims = self.indices(rows, True)
             return self.sample_points[best], sims

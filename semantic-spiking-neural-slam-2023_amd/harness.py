@@ -95,13 +95,14 @@ def make_pathint_model(ssp_space, path, vels, pi_n_neurons, tau=0.05, neuron_typ
     return out
 
 
-def pathint_metrics(ssp_space, sim_out, real_ssp, path, num_samples=None, backend=None):
+def pathint_metrics(ssp_space, sim_out, real_ssp, path, num_samples=None, backend=None, refine=False):
     """(sim_path_est, pi_sims, pi_error) as ``run_pathint.py:179-184``.  ``backend``: decode backend of ``SSPSpace.decode``
-    (None: NumPy on the host, "hip": the GPU grid decoder)."""
+    (None: NumPy on the host, "hip": the GPU grid decoder).  ``refine``: decode with 'grid-refine' (Newton steps from the grid
+    point) instead of 'from-set', which lifts the half-pitch floor of the position error."""
     if num_samples is None:
         num_samples = 100 if ssp_space.domain_dim < 3 else 50
     n = sim_out.shape[0]
-    est = ssp_space.decode(sim_out, "from-set", "grid", num_samples, backend=backend)
+    est = ssp_space.decode(sim_out, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)
     nrm = np.linalg.norm(sim_out, axis=1)
     sims = np.sum(sim_out * real_ssp[:n], axis=1) / np.where(nrm == 0, 1.0, nrm)
     err = np.sqrt(np.sum((path[:n] - est) ** 2, axis=1))
@@ -291,16 +292,16 @@ def get_activities(built_ens, neuron_type, x):
     return neuron_type.rates(proj, built_ens.gain, built_ens.bias)
 
 
-def map_recall(ssp_space, lm_space, built_memory, neuron_type, final_decoders, backend=None):
+def map_recall(ssp_space, lm_space, built_memory, neuron_type, final_decoders, backend=None, refine=False):
     """Definition (i) of map recall, ``run_slam.py:263-268``: activities of the *built* (pre-Voja)
     memory ensemble for each landmark SP times the final PES decoders -> decoded landmark positions."""
     acts = get_activities(built_memory, neuron_type, lm_space.vectors)
     recalled = acts @ np.asarray(final_decoders).T
-    return recalled, ssp_space.decode(recalled, "from-set", "grid", 100, backend=backend)
+    return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", 100, backend=backend)
 
 
 def map_recall_learned(ssp_space, lm_space, built_memory, neuron_type, final_scaled_encoders, final_decoders,
-                       num_samples=100, backend=None):
+                       num_samples=100, backend=None, refine=False):
     """Definition (ii) of map recall, ``slam_map_new.py:342-347`` / ``:447-452``: the landmark SPs are projected on the
     FINAL scaled encoders (``Probe(conn_in.learning_rule, "scaled_encoders")[-1]``, i.e. after Voja moved them) and
     pushed through ``neuron_type.rates(x, gain, bias)``, then through the final PES decoders.
@@ -310,4 +311,4 @@ def map_recall_learned(ssp_space, lm_space, built_memory, neuron_type, final_sca
     x = np.asarray(lm_space.vectors) @ np.asarray(final_scaled_encoders).T
     acts = neuron_type.rates(x, built_memory.gain, built_memory.bias)
     recalled = acts @ np.asarray(final_decoders).T
-    return recalled, ssp_space.decode(recalled, "from-set", "grid", num_samples, backend=backend)
+    return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)

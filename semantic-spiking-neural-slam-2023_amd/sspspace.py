@@ -247,13 +247,150 @@ class SSPSpace:
             self._decoder_cache = {key: GridDecoder(self, num_samples, sampling_method, dtype=dtype)}
         return self._decoder_cache[key]
 
+    # -- sub-grid refinement ('grid-refine') ---------------------------------------------------
+    def refine_tables(self):
+        """``(K, M, w)`` of the refinement rule: the half spectrum, K = (d + 1) / 2 bins with w = 1/d, 2/d, ...,
+        when ``grid_factors``' symmetry test on the phase matrix passes, else all d bins with w = 1/d;
+        ``M = phase_matrix[:K] / length_scale``."""
+        d, dim = self.ssp_dim, self.domain_dim
+        A = np.asarray(self.phase_matrix, dtype=float)
+        if d % 2 == 1 and A.shape == (d, dim) and np.allclose(A[1:], -A[1:][::-1]) and not np.any(A[0] != 0):
+            K = (d + 1) // 2
+            w = np.full(K, 2.0 / d)
+            w[0] = 1.0 / d
+        else:
+            K, w = d, np.full(d, 1.0 / d)
+        return K, np.ascontiguousarray(A[:K] / self.length_scale.reshape(1, -1)), w
+
+    def refine_box(self, num_samples=300, sampling_method="grid", trust=None):
+        """``(lo, hi, pitch)`` per axis: the domain (the bounds ``get_sample_points`` uses; unbounded beside a ``trust=``) and the
+        spacing of the sample grid, or ``trust`` in its place (a scalar or one value per axis)."""
+        dim = self.domain_dim
+        if trust is not None:
+            pitch = np.asarray(trust, dtype=float) * np.ones(dim)
+            if pitch.shape != (dim,) or np.any(pitch < 0) or not np.all(np.isfinite(pitch)):
+                raise ValueError(f"trust must be a finite non-negative scalar or {dim} of them, got {trust!r}")
+            b = self.domain_bounds if self.domain_bounds is not None else np.tile([-np.inf, np.inf], (dim, 1))
+            return b[:, 0].copy(), b[:, 1].copy(), pitch
+        b = self.domain_bounds if self.domain_bounds is not None else np.tile([-10.0, 10.0], (dim, 1))
+        if sampling_method == "grid":
+            counts = [int(num_samples)] * dim
+        elif sampling_method == "length-scale":
+            counts = [2 * int(np.ceil((b[i, 1] - b[i, 0]) / self.length_scale[i, 0])) for i in range(dim)]
+        else:
+            raise NotImplementedError(f"sampling method {sampling_method!r} is not part of the SLAM hot path")
+        pitch = np.array([(b[i, 1] - b[i, 0]) / (counts[i] - 1) if counts[i] > 1 else 0.0 for i in range(dim)])
+        return b[:, 0].copy(), b[:, 1].copy(), pitch
+
+    @staticmethod
+    def _newton_steps(g, A):
+        """The step of the rule for every row: ``g`` (T, dim), ``A = -H`` (T, dim, dim) -> (p, positive definite by the test)."""
+        T, dim = g.shape
+        diag = np.stack([A[:, a, a] for a in range(dim)], axis=1)
+        dmax, amax = diag.max(axis=1), np.abs(diag).max(axis=1)
+        pd = dmax > 0
+        floor = 1e-6 * dmax
+        L = np.zeros((T, dim, dim))
+        for j in range(dim):
+            piv = A[:, j, j] - np.sum(L[:, j, :j] ** 2, axis=1)
+            pd = pd & (piv > floor)
+            ljj = np.sqrt(np.where(pd, piv, 1.0))
+            L[:, j, j] = ljj
+            for r in range(j + 1, dim):
+                L[:, r, j] = (A[:, r, j] - np.sum(L[:, r, :j] * L[:, j, :j], axis=1)) / ljj
+        y = np.zeros((T, dim))
+        for j in range(dim):
+            y[:, j] = (g[:, j] - np.sum(L[:, j, :j] * y[:, :j], axis=1)) / L[:, j, j]
+        p = np.zeros((T, dim))
+        for j in range(dim - 1, -1, -1):
+            p[:, j] = (y[:, j] - np.sum(L[:, j + 1:, j] * p[:, j + 1:], axis=1)) / L[:, j, j]
+        fallback = g / np.where(amax > 0, amax, 1.0)[:, None] * (amax > 0)[:, None]
+        return np.where(pd[:, None], p, fallback), pd
+
+    def _refine_numpy(self, unit, x0, lo, hi, pitch, iterations):
+        """The rule in float64, vectorised over rows (a slab of rows at a time, so the spectrum and the (rows x K) phases stay
+        bounded): ``(x, f, status)``."""
+        K, M, w = self.refine_tables()
+        T, dim = x0.shape
+        x, f, status = np.array(x0, dtype=float), np.zeros(T), np.zeros(T, dtype=np.int32)
+        blo, bhi = np.maximum(lo[None, :], x0 - pitch[None, :]), np.minimum(hi[None, :], x0 + pitch[None, :])
+        iu = [(a, b) for a in range(dim) for b in range(a, dim)]
+        slab = max(1, (1 << 21) // max(K, self.ssp_dim))
+        for r0 in range(0, T, slab):
+            sl = slice(r0, r0 + slab)
+            U = np.fft.fft(unit[sl], axis=1)[:, :K]
+            c, s = w[None, :] * U.real, w[None, :] * U.imag
+            xs, last = x[sl], np.zeros_like(x[sl])
+            for it in range(iterations + 1):
+                th = xs @ M.T
+                cs, sn = np.cos(th), np.sin(th)
+                v, dv = c * cs + s * sn, s * cs - c * sn
+                g = dv @ M
+                A = np.empty((xs.shape[0], dim, dim))
+                for a, b in iu:
+                    A[:, a, b] = A[:, b, a] = v @ (M[:, a] * M[:, b])
+                p, pd = self._newton_steps(g, A)
+                if it == iterations:
+                    break
+                xn = np.minimum(np.maximum(xs + p, blo[sl]), bhi[sl])
+                last, xs = xn - xs, xn
+            x[sl], f[sl] = xs, v.sum(axis=1)
+            status[sl] = (np.any((xs <= blo[sl]) | (xs >= bhi[sl]), axis=1) * 1 + (~pd) * 2
+                          + np.any(np.abs(last) > 1e-6 * pitch[None, :], axis=1) * 4)
+        return x, f, status
+
+    def _decode_refine(self, ssp, sampling_method, num_samples, samples, backend, iterations, trust, return_info):
+        from .decoding import GridDecoder, backend_dtype
+        dtype = backend_dtype(backend)
+        iterations = int(iterations)
+        if iterations < 0:
+            raise ValueError(f"iterations must be >= 0, got {iterations}")
+        if self.domain_dim > 3:
+            raise ValueError(f"'grid-refine' supports domain_dim 1, 2 and 3, not domain_dim {self.domain_dim}")
+        if samples is not None and trust is None:
+            raise ValueError("'grid-refine' with samples= needs trust=: the half width of the box around the best sample, "
+                             "which a grid's pitch gives when the space makes the samples")
+        if dtype is not None:
+            if samples is None:
+                return self._grid_decoder(num_samples, sampling_method, dtype).refine(ssp, iterations, return_info, trust=trust)
+            with GridDecoder(self, samples=samples, dtype=dtype, trust=trust) as dec:
+                return dec.refine(ssp, iterations, return_info)
+        lo, hi, pitch = self.refine_box(num_samples, sampling_method, trust)
+        sample_ssps, sample_points = self.get_sample_pts_and_ssps(num_samples, sampling_method) if samples is None else samples
+        unit, best = self._best_samples(ssp, sample_ssps)
+        x0 = np.asarray(sample_points, dtype=float)[best]
+        if iterations == 0 and not return_info:
+            return x0
+        x, f, status = self._refine_numpy(unit, x0, lo, hi, pitch, iterations)
+        return (x, f, status, best) if return_info else x
+
+    @staticmethod
+    def _best_samples(ssp, sample_ssps):
+        """(rows scaled as decode scales them, index of the most similar sample of each)."""
+        ssp = np.atleast_2d(np.asarray(ssp, dtype=float))
+        nrm = np.linalg.norm(ssp, axis=1, keepdims=True)
+        unit = np.where(nrm < 1e-6, ssp, ssp / np.where(nrm == 0, 1.0, nrm))
+        best = np.empty(ssp.shape[0], dtype=np.int64)
+        step = max(1, int(2 ** 27 // max(1, sample_ssps.shape[0])))  # bound the sims block
+        for s in range(0, ssp.shape[0], step):
+            best[s:s + step] = np.argmax(sample_ssps @ unit[s:s + step].T, axis=0)
+        return unit, best
+
     def decode(self, ssp, method="from-set", sampling_method="grid", num_samples=300,
-               samples=None, backend=None, **kwargs):
+               samples=None, backend=None, iterations=8, trust=None, return_info=False, **kwargs):
         """``backend``: None (or "numpy") is the float64 host product below; "hip" / "hip-f64" run it on the GPU through a
-        ``decoding.GridDecoder`` (f32 matrix cores / f64 parity mode)."""
+        ``decoding.GridDecoder`` (f32 matrix cores / f64 parity mode).
+
+        ``method='grid-refine'``: the 'from-set' decode followed by ``iterations`` safeguarded Newton steps on
+        ``<encode(x), ssp>`` inside the box ``x0 +- pitch`` of the sample grid (``trust``, required, beside ``samples=``); the rule
+        is DESIGN.md 3.12, in float64 NumPy here and in ``csrc/ssn_decode.hip`` behind the hip backends.  With ``return_info``
+        it returns ``(x, f, status, best)``."""
+        if method == "grid-refine":
+            return self._decode_refine(ssp, sampling_method, num_samples, samples, backend, iterations, trust, return_info)
         if method != "from-set":
             raise NotImplementedError(
-                f"decode method {method!r}: only 'from-set' is on the SLAM hot path (SURVEY §2 row 6)")
+                f"decode method {method!r}: only 'from-set' and 'grid-refine' are implemented (SURVEY §2 row 6)"
+                + ("; 'grid-refine' is the working form of what 'direct-optim' aims at" if method == "direct-optim" else ""))
         if backend is not None:
             from .decoding import GridDecoder, backend_dtype
             dtype = backend_dtype(backend)
@@ -262,21 +399,14 @@ class SSPSpace:
             if dtype is not None:
                 with GridDecoder(self, samples=samples, dtype=dtype) as dec:
                     return dec.decode(ssp)
-        ssp = np.atleast_2d(np.asarray(ssp, dtype=float))
         if samples is None:
             sample_ssps, sample_points = self.get_sample_pts_and_ssps(num_samples, sampling_method)
         else:
             sample_ssps, sample_points = samples
-        nrm = np.linalg.norm(ssp, axis=1, keepdims=True)
-        unit = np.where(nrm < 1e-6, ssp, ssp / np.where(nrm == 0, 1.0, nrm))
-        best = np.empty(ssp.shape[0], dtype=np.int64)
-        step = max(1, int(2 ** 27 // max(1, sample_ssps.shape[0])))  # bound the sims block
-        for s in range(0, ssp.shape[0], step):
-            best[s:s + step] = np.argmax(sample_ssps @ unit[s:s + step].T, axis=0)
-        return sample_points[best]
+        return sample_points[self._best_samples(ssp, sample_ssps)[1]]
 
-    def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300, backend=None):
-        return self.encode(self.decode(ssp, method, sampling_method, num_samples, backend=backend))
+    def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300, backend=None, **kwargs):
+        return self.encode(self.decode(ssp, method, sampling_method, num_samples, backend=backend, **kwargs))
 
     # -- algebra ---------------------------------------------------------------------------
     def normalize(self, ssp):

@@ -1,6 +1,6 @@
 """Grid decode of a probed trajectory: the GPU decoder (decoding.GridDecoder) against the NumPy path of SSPSpace.decode.
 
-usage: python tools/bench_decode.py [a] [b] [c] [--rows N] [--repeats R] [--numpy-rows M]
+usage: python tools/bench_decode.py [a] [b] [c] [--rows N] [--repeats R] [--numpy-rows M] [--refine]
 
   a   20 000 x 1015 rows over the 100 x 100 grid (what examples/run_pathint.py decodes after a 20 s config-2 run)
   b   20 000 rows over a 3-D 50^3 grid at ssp_dim 1015 as built (the f32 table is about 0.5 GB)
@@ -10,7 +10,11 @@ usage: python tools/bench_decode.py [a] [b] [c] [--rows N] [--repeats R] [--nump
 Per shape: device milliseconds of the kernels alone (HIP events around prepare + product + finish of every chunk, copies outside),
 wall time of GridDecoder.decode including the upload of the rows, wall time of the NumPy decode on the same box (on --numpy-rows
 rows, scaled to all of them, when that is fewer), the fraction of the 157.3 TFLOP/s f32 matrix peak the kernels reach
-(2 T S d FLOP), and whether the two answers agree.  2 warm-up calls, then the median and minimum of --repeats calls."""
+(2 T S d FLOP), and whether the two answers agree.  2 warm-up calls, then the median and minimum of --repeats calls.
+
+--refine (shapes a and b): GridDecoder.refine (8 Newton steps per row from the grid point, 'grid-refine') on the same rows with the
+same decoder in the same run: kernels and wall time next to the plain decode's, the median position error of both against the
+encoded path, and the NumPy float64 backend of the same rule on --numpy-rows rows."""
 import argparse
 import os
 import sys
@@ -61,10 +65,28 @@ def shape_ab(name, dim, n, args):
             time.perf_counter() - t0, {k: v for k, v in dec.info(T).items() if k in ("row_chunk", "n_chunks", "n_strips", "tiles_per_strip")}), flush=True)
         wall, kern = timed(lambda: dec.decode(rows), args.repeats, lambda: dec.info()["last_kernel_ms"])
         est = dec.decode(rows)
+        if args.refine:
+            wall_r, kern_r = timed(lambda: dec.refine(rows), args.repeats, lambda: dec.info()["last_kernel_ms"])
+            x, _, status, _ = dec.refine(rows, return_info=True)
     flop = 2.0 * T * S * d
     print("  kernels alone:          %s -> %.1f TFLOP/s, %.3f of the f32 matrix peak" % (fmt(kern), flop / np.median(kern) / 1e9, flop / (np.median(kern) * 1e-3) / PEAK))
     print("  GridDecoder.decode:     %s  (wall, rows uploaded as float64)" % fmt(wall), flush=True)
     m = min(T, args.numpy_rows)
+    if args.refine:
+        path = np.random.RandomState(1).uniform(-0.9, 0.9, (T, dim))          # what inputs() encoded
+        K = space.refine_tables()[0]
+        print("  refine, kernels alone:  %s  (prepare + tiles + finish + spectrum + k_decode_refine, K = %d bins)" % (fmt(kern_r), K))
+        print("  GridDecoder.refine:     %s  (wall); added to the grid decode: kernels %.3f ms (%.2f x the decode's), wall %.3f ms" % (
+            fmt(wall_r), np.median(kern_r) - np.median(kern), (np.median(kern_r) - np.median(kern)) / np.median(kern),
+            np.median(wall_r) - np.median(wall)))
+        print("  median position error:  grid %.5f, refined %.5f; status words: %s" % (
+            np.median(np.linalg.norm(est - path, axis=1)), np.median(np.linalg.norm(x - path, axis=1)),
+            dict(zip(*[v.tolist() for v in np.unique(status, return_counts=True)]))), flush=True)
+        t0 = time.perf_counter()
+        xh = space.decode(rows[:m], "grid-refine", "grid", n)
+        t_np = 1e3 * (time.perf_counter() - t0)
+        print("  NumPy 'grid-refine':    %.0f ms for %d rows (grid decode included); largest |x_device - x_numpy| %.2e" % (
+            t_np, m, np.abs(x[:m] - xh).max()), flush=True)
     t0 = time.perf_counter()
     host = space.decode(rows[:m], "from-set", "grid", n)
     t_np = 1e3 * (time.perf_counter() - t0)
@@ -104,6 +126,7 @@ if __name__ == "__main__":
     ap.add_argument("--rows", type=int, default=20000)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--numpy-rows", type=int, default=20000, help="rows of the NumPy timing (scaled up when fewer than --rows)")
+    ap.add_argument("--refine", action="store_true", help="also time GridDecoder.refine on shapes a and b")
     args = ap.parse_args()
     for s in args.shapes:
         if s == "a":

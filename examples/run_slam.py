@@ -6,7 +6,10 @@ that concern the model; ``--backend mi355x`` / ``mi355x-f64``).
 
 Prints the trajectory accuracy and the recalled landmark map (``run_slam.py:263-268``: activities of the memory
 population for each landmark's semantic pointer times the final PES decoders, decoded to positions) and, with
-``--save``, writes the result file with the reference's field names.
+``--save``, writes the result file with the reference's field names.  With ``--decode-backend hip`` the final map is recalled on
+the GPU from the learned state (``sim.recall``: the Voja-learned encoders, as ``slam_map_new.py:342-347`` does) and neither matrix
+is read back.  ``--map-every SECONDS`` also watches the map being learned: a ``MapProbe`` on the landmark SPs, decoded to positions
+(``landmark_loc_over_time`` in the result file, the frames of ``run_slam_map_gif.py``).
 """
 import argparse
 import os
@@ -17,7 +20,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import sspslam_amd.frontend as nengo          # noqa: E402
-from sspslam_amd import harness as H           # noqa: E402
+from sspslam_amd import MapProbe, harness as H # noqa: E402
 from sspslam_amd.simulator import Simulator    # noqa: E402
 
 
@@ -49,6 +52,8 @@ def parse(argv=None):
                    help="grid decodes of the trajectory and the recalled map: NumPy on the host, or the GPU grid decoder")
     p.add_argument("--decode-refine", action="store_true",
                    help="also decode with 'grid-refine' (Newton steps from the grid point) and print both sets of errors")
+    p.add_argument("--map-every", default=0.0, type=float, metavar="SECONDS",
+                   help="recall the landmark map on the GPU every SECONDS of simulated time (a MapProbe) and decode it to positions")
     return p.parse_args(argv)
 
 
@@ -66,7 +71,11 @@ def main(argv=None):
     sm = H.make_slam_model(space, path, vels, n_landmarks=args.n_landmarks, pi_n_neurons=args.pi_n_neurons,
                            mem_n_neurons=args.mem_n_neurons, circonv_n_neurons=args.circonv_n_neurons, view_rad=args.view_rad,
                            update_thres=args.update_thres, shift_rate=args.shift_rate, seed=args.seed, dt=dt,
-                           weights_sample_every=T)
+                           weights_sample_every=None if args.decode_backend == "hip" else T)
+    map_probe = None
+    if args.map_every > 0:
+        with sm.model:
+            map_probe = MapProbe(sm.slam.assomemory, sm.lm_space.vectors, sample_every=args.map_every, label="landmark map")
     dtype = "f64" if args.backend.endswith("f64") else "f32"
     t0 = time.time()
     sim = Simulator(sm.model, dt=dt, dtype=dtype, n_eval_points=args.n_eval_points or None)
@@ -76,13 +85,33 @@ def main(argv=None):
         sim.run(T)
         elapsed = time.time() - start
         out, ts = sim.data[sm.probe], sim.trange()
-        decoders = sim.data[sm.weights_probe][-1]
         built_memory = sim.data[sm.slam.assomemory.memory]
+        if args.decode_backend == "hip":      # the learned map from the device: L x d numbers instead of both matrices
+            lm_ssps = sim.recall(sm.slam.assomemory, sm.lm_space.vectors)
+        else:
+            decoders = sim.data[sm.weights_probe][-1]
+        frames = sim.data[map_probe] if map_probe is not None else None
+        map_ts = sim.trange(sample_every=args.map_every) if map_probe is not None else None
+        recall_time, recall_kernel_ms = sim.recall_seconds, sim.recall_kernel_ms
     n = out.shape[0]
     t0 = time.time()
     est, sims, err = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n], backend=args.decode_backend)
-    lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend)
+    if args.decode_backend == "hip":
+        lm_locs = space.decode(lm_ssps, "from-set", "grid", 100, backend="hip")
+    else:
+        lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend)
     decode_time = time.time() - t0
+    lm_over_time = None
+    if frames is not None:
+        t0 = time.time()
+        lm_over_time = H.map_over_time(space, frames, backend=None if args.decode_backend == "numpy" else args.decode_backend)
+        print("map recall: %d samples of %d landmarks every %.3f s: recall %.3f s (kernels %.1f ms), decode %.2f s (%s); median landmark "
+              "error first -> last sample %.3f -> %.3f" % (frames.shape[0], frames.shape[1], args.map_every, recall_time, recall_kernel_ms,
+                                                        time.time() - t0, args.decode_backend,
+                                                        float(np.median(np.linalg.norm(lm_over_time[0] - sm.obj_locs, axis=1))) if len(frames) else np.nan,
+                                                        float(np.median(np.linalg.norm(lm_over_time[-1] - sm.obj_locs, axis=1))) if len(frames) else np.nan))
+    elif recall_time:
+        print("map recall: final map on the GPU in %.4f s (kernels %.2f ms)" % (recall_time, recall_kernel_ms))
     lm_err = np.linalg.norm(lm_locs - sm.obj_locs, axis=1)
     print("d = %d, T = %.1f s: build %.1f s, run %.2f s (%.2f sim-s/wall-s), decode %.2f s (%s); similarity to the true SSP mean "
           "%.4f, final position error %.4f; recalled landmark positions: median error %.3f" % (
@@ -91,7 +120,10 @@ def main(argv=None):
     if args.decode_refine:
         t0 = time.time()
         _, _, err_r = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n], backend=args.decode_backend, refine=True)
-        _, lm_locs_r = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend, refine=True)
+        if args.decode_backend == "hip":
+            lm_locs_r = space.decode(lm_ssps, "grid-refine", "grid", 100, backend="hip")
+        else:
+            _, lm_locs_r = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend, refine=True)
         lm_err_r = np.linalg.norm(lm_locs_r - sm.obj_locs, axis=1)
         print("grid decode | grid-refine (%.2f s): position error median %.4f | %.4f, final %.4f | %.4f; recalled landmark "
               "positions: median error %.4f | %.4f" % (time.time() - t0, np.median(err), np.median(err_r), err[-1], err_r[-1],
@@ -102,7 +134,7 @@ def main(argv=None):
             args.backend, args.save_name_extra, space.ssp_dim, args.pi_n_neurons, args.mem_n_neurons, args.circonv_n_neurons,
             int(T), args.limit, args.seed)
         H.save_slam_results(os.path.join(args.save_dir, name), space, ts, path, sm.real_ssp, sm.obj_locs, args.view_rad, out,
-                            lm_ssps, lm_locs, elapsed, args=args)
+                            lm_ssps, lm_locs, elapsed, args=args, landmark_loc_over_time=lm_over_time, landmark_loc_over_time_ts=map_ts)
         print("saved", os.path.join(args.save_dir, name))
     return out, lm_locs
 

@@ -417,6 +417,43 @@ int ssn_decoder_refine_rows(ssn_decoder* dec, const double* rows, int64_t n_rows
 int ssn_decoder_refine_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows,
                                    int32_t iterations, double* x, int32_t* best, double* f, int32_t* status);
 
+/* Recall of a learned associative memory on the device (additive to ABI 11; csrc/ssn_recall.hip): for the dense
+ * population whose scaled encoders are buffer `enc_buffer` (n x d_key, the matrix Voja moves) and one of whose outgoing
+ * connections has the decoders `dec_buffer` (d_val x n, the matrix PES moves), and for n_keys key rows V (host doubles, C order),
+ *   J[l][m] = scale[m] (V[l] . E[m]) + bias[m],   a = rate(J),   q[l][r] = sum_m W[r][m] a[l][m]
+ * with rate(J) = amplitude / (tau_ref + tau_rc log1p(1 / (J - 1))) for J > 1, else 0 (SSN_LIF, SSN_LIFRATE) or
+ * amplitude max(J, 0) (SSN_RELU).  scale = gain gives the reference scripts' recall (slam_map_new.py:342-347), scale = 1 the rates
+ * the population really has for that key.  Both matrices are read where the simulator keeps them, in whichever layout the plan
+ * chose, in their state at the time of the call; ssn_recall_run runs on the simulator's own stream, so it belongs between two
+ * ssn_run_steps calls, and fills dst (n_keys x d_val host doubles) before it returns.  scale and bias (n host doubles; zero for
+ * padded neurons, which then contribute nothing), the neuron constants and the keys are uploaded at creation; ssn_recall_set_keys
+ * replaces the keys (any number of rows).  f32 simulators use the f32 matrix cores for both products; the decoder product is cut
+ * into partial sums of 256 neurons that are added in ascending order, the scratch area (scratch_bytes, 0 = all partials up to
+ * 64 MB, at least ssn_recall_info.min_scratch_bytes) only decides how many are kept at a time: the result does not depend on it
+ * and is the same from run to run.  f64 simulators use plain ordered sums.  A recall must be destroyed before its simulator.
+ * SSN_EINVAL: null handle or argument, n_keys == 0, a buffer that is not the shape claimed, scratch too small for one partial;
+ * SSN_EUNSUPPORTED: a buffer of an ensemble array; SSN_EHIP "no HIP device available (there is no CPU fallback)" without a GPU. */
+typedef struct ssn_recall ssn_recall;
+typedef struct ssn_recall_info {
+  int64_t n, d_key, d_val, n_keys;
+  int64_t padded_keys;        /* key rows on the device (whole 64-row tiles)                                     */
+  int64_t chunk;              /* neurons per partial sum of the decoder product (256)                            */
+  int64_t n_chunks;
+  int64_t chunks_per_pass;    /* partial sums the scratch area holds at a time                                   */
+  int64_t scratch_bytes;
+  int64_t min_scratch_bytes;  /* one partial sum                                                                 */
+  int64_t dec_neuron_major;   /* 1: the decoders lie neuron-major [n][ldt] (spike-sparse plan), 0: row-major     */
+  int64_t last_launches;      /* kernel launches of the last ssn_recall_run                                      */
+  double last_kernel_ms;      /* their device time (HIP events around the kernels, the copy outside)             */
+} ssn_recall_info;
+int ssn_recall_create(ssn_sim* sim, int32_t enc_buffer, int32_t dec_buffer, int64_t n, int64_t d_key, int64_t d_val,
+                      const double* scale, const double* bias, int32_t neuron, double tau_rc, double tau_ref, double amplitude,
+                      const double* keys, int64_t n_keys, int64_t scratch_bytes /* 0 = default */, ssn_recall** out);
+void ssn_recall_destroy(ssn_recall* rc);
+int ssn_recall_set_keys(ssn_recall* rc, const double* keys, int64_t n_keys);
+int ssn_recall_run(ssn_recall* rc, double* dst);
+int ssn_recall_get_info(ssn_recall* rc, ssn_recall_info* out);
+
 int ssn_get_counters(ssn_sim* sim, ssn_counters* out);
 /* Fills at most `capacity` entries; returns the number of kernels with timed launches (or a negative status). */
 int ssn_get_kernel_times(ssn_sim* sim, ssn_kernel_time* out, int32_t capacity);

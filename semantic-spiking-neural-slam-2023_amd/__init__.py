@@ -15,3 +15,4 @@ Import as ``sspslam_amd`` (alias of this hyphen-named directory).  Sub-modules:
 __version__ = "0.1.0"
 
 from .sspspace import SPSpace, SSPSpace, HexagonalSSPSpace, RandomSSPSpace  # noqa: F401
+from .frontend import MapProbe  # noqa: F401

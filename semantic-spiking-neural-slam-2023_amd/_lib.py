@@ -97,6 +97,13 @@ class DecoderInfo(C.Structure):
                 ("padded_width", C.c_int64), ("last_launches", C.c_int64), ("last_kernel_ms", C.c_double)]
 
 
+class RecallInfo(C.Structure):
+    _fields_ = [("n", C.c_int64), ("d_key", C.c_int64), ("d_val", C.c_int64), ("n_keys", C.c_int64), ("padded_keys", C.c_int64),
+                ("chunk", C.c_int64), ("n_chunks", C.c_int64), ("chunks_per_pass", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("min_scratch_bytes", C.c_int64), ("dec_neuron_major", C.c_int64), ("last_launches", C.c_int64),
+                ("last_kernel_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("ms_total", C.c_double)]
 
@@ -137,6 +144,12 @@ EXPORTS = {
     "ssn_decoder_refine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssn_decoder_refine_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    "ssn_recall_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "ssn_recall_destroy": (None, [C.c_void_p]),
+    "ssn_recall_set_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "ssn_recall_run": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ssn_recall_get_info": (C.c_int, [C.c_void_p, C.POINTER(RecallInfo)]),
     "ssn_get_counters": (C.c_int, [C.c_void_p, C.POINTER(Counters)]),
     "ssn_get_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(KernelTime), C.c_int32]),
     "ssn_n_steps": (C.c_int64, [C.c_void_p]),

@@ -83,6 +83,7 @@ class BuiltModel:
         self.buffer_meta = []    # {"name", "role": param|state|learned|table|index}
         self.ops = []
         self.probes = []         # {"probe", "src", "width", "every"} | {"probe","buf",...}
+        self.map_probes = []     # {"probe", "recall": recall_spec(...), "shape", "every"}: MapProbe, recalled on the device between step calls
         self.tables = []         # {"node","fn","width","rows_buf","idx_buf"}
         self.params = {}         # frontend object -> Built*
         self.sig = {}            # (obj, "in"|"out"|...) -> (abs_off, len)
@@ -127,6 +128,43 @@ def _kind(obj):
     if isinstance(obj, fe.Connection) or n == "Connection":
         return "connection"
     raise fe.BuildError(f"unsupported object {obj!r}")
+
+
+RECALL_MODES = ("reference", "network")
+
+
+def recall_spec(model, memory, keys, mode="reference"):
+    """What a device recall of a learned memory needs (``MapProbe``, ``Simulator.recall``): the two buffers, the per-neuron
+    scale and bias (zero for padded neurons), the neuron constants and the keys.  ``memory``: an ``AssociativeMemory`` or a
+    pair ``(conn_in or ensemble, conn_out)``.  ``mode="reference"`` scales the key product with the gain once more, as the
+    reference's map scripts do (``harness.map_recall_learned``); ``mode="network"`` does not - the encoders already hold
+    ``gain / radius``.  Refuses by name what the kernels do not cover."""
+    ens, conn_out = fe.recall_target(memory)
+    if mode not in RECALL_MODES:
+        raise fe.BuildError(f"map recall: mode {mode!r} is not one of {RECALL_MODES}")
+    be, bc = model.params.get(ens), model.params.get(conn_out)
+    if be is None or bc is None:
+        raise fe.BuildError(f"map recall: {ens!r} / {conn_out!r} are not part of the built model")
+    refusal = getattr(be, "recall_refusal", None)
+    if refusal:
+        raise fe.BuildError(f"map recall: {ens!r} {refusal}; the device recall covers dense, unsharded populations")
+    if getattr(bc, "learned_buffer", None) is None:
+        raise fe.BuildError(f"map recall: {conn_out!r} has no learned buffer (it needs a PES learning rule)")
+    if not hasattr(be, "encoder_buffer"):
+        raise fe.BuildError(f"map recall: {ens!r} has no encoder buffer (a population nothing reads is not lowered)")
+    keys = np.ascontiguousarray(np.atleast_2d(np.asarray(keys, dtype=np.float64)))
+    E, W = model.buffers[be.encoder_buffer], model.buffers[bc.learned_buffer]
+    n, d_key = E.shape
+    if keys.ndim != 2 or keys.shape[0] == 0 or keys.shape[1] != d_key:
+        raise fe.BuildError(f"map recall: keys of shape {keys.shape} do not match the {d_key}-dimensional keys of {ens!r}")
+    if W.shape[1] != n:
+        raise fe.BuildError(f"map recall: {conn_out!r} holds decoders for {W.shape[1]} neurons, {ens!r} has {n}")
+    scale = np.zeros(n)
+    scale[:be.gain.size] = be.gain if mode == "reference" else 1.0
+    bias = np.zeros(n)
+    bias[:be.bias.size] = be.bias
+    return dict(enc=int(be.encoder_buffer), dec=int(bc.learned_buffer), n=int(n), d_key=int(d_key), d_val=int(W.shape[0]), scale=scale,
+                bias=bias, neuron=dict(be.neuron), keys=keys, mode=mode)
 
 
 def _neuron_desc(nt):
@@ -298,11 +336,17 @@ class Builder:
         # parameters of every ensemble (cheap, vectorised); decoders are solved on demand
         for e in ensembles:
             self._build_ensemble_params(e)
+            # why the device recall (MapProbe, Simulator.recall) cannot use this population, if it cannot
+            self.built_ens[id(e)].recall_refusal = (
+                "is an EnsembleArray member" if id(e) in self.block_of else
+                "is replicated over the ranks of a neuron-sharded build" if self.neuron_shard is not None and id(e) in self.replicated else
+                "is neuron-sharded" if self.neuron_shard is not None else None)
         conns = self._drop_dead_ends(conns, nodes, probes)
         for c in conns:
             self._lower_connection(c)
         self.tap_hull = self._tap_hulls(probes)
         self.tap_ref = {}
+        self.map_pending = []
         for p in probes:
             self._lower_probe(p)
         for e in ensembles:
@@ -310,6 +354,9 @@ class Builder:
         for e in ensembles:
             if id(e) not in self.block_of:
                 self._emit_dense_ensemble(e)
+        for p, conn_out, every in self.map_pending:      # (the encoder buffers exist now)
+            spec = recall_spec(self.model, (p.memory_ensemble, conn_out), p.keys, p.mode)
+            self.model.map_probes.append({"probe": p, "recall": spec, "shape": (spec["keys"].shape[0], spec["d_val"]), "every": every})
         self._live = self._live_elements(probes)
         for blk in self.blocks:
             self._emit_block(blk)
@@ -1053,6 +1100,11 @@ class Builder:
         k = _kind(obj)
         every = 1 if p.sample_every is None else max(1, int(round(p.sample_every / self.dt)))
         attr = p.attr
+        if attr == "map_recall":
+            # MapProbe: no operator and no signal - the simulator recalls the memory on the device between two step calls.  It goes
+            # into a list of its own: `probes` holds what is sampled from a signal or a buffer, which every consumer of a model walks.
+            self.map_pending.append((p, obj, every))
+            return
         if k == "connection" and attr == "weights":
             bc = self.model.params.get(obj)
             if bc is None or bc.learned_buffer is None:

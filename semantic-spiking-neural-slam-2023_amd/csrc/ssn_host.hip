@@ -27,6 +27,7 @@
 
 #include "../../include/ssn.h"
 #include "ssn_launch.hpp"
+#include "ssn_recall.hpp"
 
 namespace {
 
@@ -280,6 +281,7 @@ struct ssn_sim {
   virtual int counters(ssn_counters* out) = 0;
   virtual int kernel_times(ssn_kernel_time* out, int capacity) = 0;
   virtual int64_t n_steps() = 0;
+  virtual int buffer_view(int id, ssn::BufView* out) = 0;      // ssn_recall.hip: a matrix where it lies
 };
 
 namespace {
@@ -3991,6 +3993,17 @@ struct Sim final : ssn_sim {
   }
 
   int64_t n_steps() override { return steps_done; }
+
+  int buffer_view(int id, ssn::BufView* out) override {
+    if (async_active) return fail(SSN_EINVAL, "a stream-ordered run is in flight on the caller's stream: call ssn_phase_sync first");
+    if (id < 0 || id >= (int)bufs.size()) return fail(SSN_EINVAL, "buffer id %d out of range", id);
+    const Buf& b = bufs[id];
+    if (b.kind != SSN_BUF_REAL || !b.shaped || !b.d) return fail(SSN_EINVAL, "buffer %d is not a matrix of reals", id);
+    if (b.perm || b.dec_DP || b.packed) return fail(SSN_EUNSUPPORTED, "buffer %d belongs to an ensemble array (packed or re-ordered on the device)", id);
+    out->d = b.d; out->dtype = sizeof(T) == 4 ? SSN_F32 : SSN_F64; out->device = device; out->stream = stream;
+    out->rows = b.rows; out->cols = b.cols; out->ld = b.ld; out->transposed = b.transposed ? 1 : 0; out->ldt = b.ldt;
+    return SSN_OK;
+  }
 };
 
 template <typename T>
@@ -4003,6 +4016,10 @@ int create_sim(const ssn_model_desc* desc, ssn_sim** out) {
 }
 
 }  // namespace
+
+namespace ssn {
+int sim_buffer_view(ssn_sim* sim, int id, BufView* out) { return sim && out ? sim->buffer_view(id, out) : fail(SSN_EINVAL, "null simulator"); }
+}  // namespace ssn
 
 extern "C" {
 

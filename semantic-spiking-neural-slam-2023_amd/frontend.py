@@ -558,6 +558,44 @@ class Probe:
         return f"<Probe {self.attr} of {self.target!r}>"
 
 
+def recall_target(memory):
+    """(memory ensemble, conn_out) of what ``MapProbe`` / ``Simulator.recall`` were given: an ``AssociativeMemory`` (anything
+    with ``memory`` and ``conn_out``) or a pair ``(conn_in or ensemble, conn_out)``."""
+    if hasattr(memory, "conn_out") and hasattr(memory, "memory"):
+        ens, conn_out = memory.memory, memory.conn_out
+    else:
+        try:
+            first, conn_out = memory
+        except (TypeError, ValueError):
+            raise ValidationError("map recall needs an AssociativeMemory or a pair (conn_in or ensemble, conn_out)", "memory") from None
+        ens = first.post_obj if isinstance(first, Connection) else first
+    if not isinstance(ens, Ensemble):
+        raise ValidationError(f"map recall: {ens!r} is not an Ensemble", "memory")
+    if not isinstance(conn_out, Connection) or conn_out.pre_obj is not ens:
+        raise ValidationError(f"map recall: {conn_out!r} is not a connection out of {ens!r}", "memory")
+    if not isinstance(conn_out.learning_rule_type, PES):
+        raise ValidationError(f"map recall: {conn_out!r} has no learned buffer (it needs a PES learning rule)", "memory")
+    return ens, conn_out
+
+
+class MapProbe(Probe):
+    """Recall of a learned associative memory for fixed keys, sampled during the run on the device: what the reference's map
+    figures compute on the host from ``Probe(conn_out, "weights")`` and ``Probe(conn_in.learning_rule, "scaled_encoders")``
+    (``slam_map_new.py:342-347``).  ``sim.data[probe]`` is ``(samples, L, d_val)``; a sample is taken where a buffer probe with
+    the same ``sample_every`` takes its sample.  ``mode``: "reference" (the scripts' computation, gain applied twice - what
+    ``harness.map_recall_learned`` returns) or "network" (the rates the population really has for a key)."""
+
+    def __init__(self, memory, keys, sample_every=None, mode="reference", label=None):
+        ens, conn_out = recall_target(memory)
+        keys = np.array(keys, dtype=float, ndmin=2)
+        if keys.ndim != 2 or keys.shape[0] == 0 or keys.shape[1] != ens.dimensions:
+            raise ValidationError(f"keys of shape {keys.shape} do not match the {ens.dimensions}-dimensional keys of {ens!r}", "keys")
+        if mode not in ("reference", "network"):
+            raise ValidationError(f"mode {mode!r} is not 'reference' or 'network'", "mode")
+        self.memory_ensemble, self.keys, self.mode = ens, keys, mode
+        super().__init__(conn_out, attr="map_recall", sample_every=sample_every, label=label)
+
+
 class EnsembleArray(Network):
     """``nengo.networks.EnsembleArray``: ``n_ensembles`` equal ensembles."""
 

@@ -10,6 +10,7 @@ one definition of the benchmark workloads:
 * ``make_slam_model``       ``run_slam.py:95-195``
 * ``map_recall``            ``run_slam.py:263-268``        (definition (i): built encoders)
 * ``map_recall_learned``    ``slam_map_new.py:342-347,447-452``  (definition (ii): Voja-probed encoders)
+* ``map_over_time``         ``run_slam_map_gif.py:323-329``     (the frames of a ``MapProbe`` decoded to positions)
 """
 import numpy as np
 
@@ -272,8 +273,12 @@ def save_pathint_results(filename, ssp_space, ts, path, real_ssp, pi_sim_out, el
 
 
 def save_slam_results(filename, ssp_space, ts, path, real_ssp, obj_locs, view_rad, slam_sim_out, landmark_ssps_est,
-                      landmark_loc_est, elapsed_time, args=None, elapsed_thread_time=None):
-    """Field names of ``run_slam.py:282-293``.  Returns the decoded path estimate."""
+                      landmark_loc_est, elapsed_time, args=None, elapsed_thread_time=None, landmark_loc_over_time=None,
+                      landmark_loc_over_time_ts=None):
+    """Field names of ``run_slam.py:282-293``; ``landmark_loc_over_time`` (samples, L, domain_dim) and its sample times
+    ``landmark_loc_over_time_ts`` are added when given (``map_over_time`` of a ``MapProbe``).  Returns the decoded path estimate."""
+    extra = {} if landmark_loc_over_time is None else dict(landmark_loc_over_time=landmark_loc_over_time,
+                                                           landmark_loc_over_time_ts=landmark_loc_over_time_ts)
     slam_path, slam_sims, slam_error = pathint_metrics(ssp_space, slam_sim_out, real_ssp, path)
     n = slam_sim_out.shape[0]
     path, real_ssp = path[:n], real_ssp[:n]
@@ -282,7 +287,7 @@ def save_slam_results(filename, ssp_space, ts, path, real_ssp, obj_locs, view_ra
              slam_path=slam_path, slam_error=slam_error, landmark_ssps_est=landmark_ssps_est,
              landmark_loc_est=landmark_loc_est, elapsed_time=elapsed_time,
              elapsed_thread_time=elapsed_time if elapsed_thread_time is None else elapsed_thread_time,
-             args=np.array(repr(args)), sig_to_noise_ratio=np.array(np.nan))
+             args=np.array(repr(args)), sig_to_noise_ratio=np.array(np.nan), **extra)
     return slam_path
 
 
@@ -312,3 +317,17 @@ def map_recall_learned(ssp_space, lm_space, built_memory, neuron_type, final_sca
     acts = neuron_type.rates(x, built_memory.gain, built_memory.bias)
     recalled = acts @ np.asarray(final_decoders).T
     return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)
+
+
+def map_over_time(ssp_space, frames, num_samples=100, backend=None, refine=False):
+    """Decoded landmark positions of a ``MapProbe``: ``frames`` (samples, L, d) -> (samples, L, domain_dim), every recalled row
+    decoded as ``map_recall_learned`` decodes its rows (``run_slam_map_gif.py:323-329`` per frame), all rows in one decode call
+    (``backend``: None for NumPy on the host, "hip" for the GPU grid decoder; ``refine``: 'grid-refine')."""
+    frames = np.asarray(frames, dtype=float)
+    if frames.ndim != 3:
+        raise ValueError(f"frames must be (samples, L, d), got {frames.shape}")
+    s, n_keys, d = frames.shape
+    if s * n_keys == 0:
+        return np.zeros((s, n_keys, ssp_space.domain_dim))
+    est = ssp_space.decode(frames.reshape(s * n_keys, d), "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)
+    return np.asarray(est).reshape(s, n_keys, -1)

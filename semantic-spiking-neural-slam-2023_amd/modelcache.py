@@ -317,6 +317,10 @@ def _probe(fp, p):
     fp.ref(p.target)
     fp.value(p.synapse)
     fp.value(getattr(p, "unused", None))      # (sharding.py: decoded rows the probe's reader never looks at)
+    if hasattr(p, "keys"):                    # MapProbe: the built model carries the keys and the mode's per-neuron scale
+        fp.feed("map recall", p.mode)
+        fp.ref(p.memory_ensemble)
+        fp.value(np.asarray(p.keys, dtype=float))
 
 
 # ---- (de)serialisation: the model without the live objects ----------------------------------------------------------------

@@ -30,7 +30,7 @@ from ._lib import (  # noqa: F401  (plan switches, for the callers of Simulator(
     SSN_PLAN_FOUR_STEP_FFT, SSN_PLAN_SPLIT_BLOCK,
     PLAN_FLAGS)
 from . import frontend as fe
-from .builder import BuiltModel, build
+from .builder import BuiltModel, build, recall_spec
 
 
 class SimulationData(dict):
@@ -260,6 +260,44 @@ def tabulate(fn, width, steps, dt, stage=None):
     return np.ascontiguousarray(rows[first[~z]]), slot[run].astype(np.int32)
 
 
+class DeviceRecall:
+    """One ``ssn_recall`` object of the library: the recall of a learned memory for a set of keys on the simulator's device
+    (csrc/ssn_recall.hip).  ``spec`` comes from ``builder.recall_spec``.  It reads the simulator's matrices where they lie, so it
+    is closed before the simulator is."""
+
+    def __init__(self, sim, spec, scratch_bytes=0):
+        self._sim, self._lib = sim, sim._lib
+        self.spec = spec
+        self._h = C.c_void_p()
+        nd = spec["neuron"]
+        keys, scale, bias = spec["keys"], spec["scale"], spec["bias"]
+        self.shape = (keys.shape[0], spec["d_val"])
+        sim._check(self._lib.ssn_recall_create(sim._h, spec["enc"], spec["dec"], spec["n"], spec["d_key"], spec["d_val"], scale.ctypes.data,
+                                               bias.ctypes.data, _lib.NEURON_CODE[nd["type"]], nd["tau_rc"], nd["tau_ref"], nd["amplitude"],
+                                               keys.ctypes.data, keys.shape[0], int(scratch_bytes), C.byref(self._h)))
+
+    def set_keys(self, keys):
+        keys = np.ascontiguousarray(keys, dtype=np.float64)
+        self._sim._check(self._lib.ssn_recall_set_keys(self._h, keys.ctypes.data, keys.shape[0]))
+        self.shape = (keys.shape[0], self.shape[1])
+
+    def run(self):
+        out = np.empty(self.shape, dtype=np.float64)
+        self._sim._check(self._lib.ssn_recall_run(self._h, out.ctypes.data))
+        return out
+
+    def info(self):
+        """The plan and the device time of the last ``run`` (``ssn_recall_info``)."""
+        info = _lib.RecallInfo()
+        self._sim._check(self._lib.ssn_recall_get_info(self._h, C.byref(info)))
+        return {f: getattr(info, f) for f, _ in info._fields_}
+
+    def close(self):
+        if self._h:
+            self._lib.ssn_recall_destroy(self._h)
+            self._h = C.c_void_p()
+
+
 class Simulator:
     def __init__(self, network, dt=0.001, seed=None, progress_bar=None, dtype="f32", device=0,
                  n_eval_points=None, steps_per_graph=0, model=None, vco_shard=None, block_steps=0, flags=0):
@@ -285,9 +323,19 @@ class Simulator:
         self._chunks = {}
         for j, p in enumerate(self._sig_probes):
             self._probe_index[p["probe"]] = ("sig", j, p)
+        self._recalls = {}               # MapProbe / (buffers, mode, scratch) of recall() -> DeviceRecall
+        self.recall_seconds = 0.0        # host time spent in device recalls (MapProbe samples and recall()), copies included
+        self.recall_kernel_ms = 0.0      # ... and the device time of their kernels
         for p in model.probes:
             if "src" not in p:
                 self._probe_index[p["probe"]] = ("buf", None, p)
+        for p in getattr(model, "map_probes", ()):
+            self._probe_index[p["probe"]] = ("map", None, p)
+            try:
+                self._recalls[p["probe"]] = DeviceRecall(self, p["recall"])
+            except BaseException:
+                self.close()
+                raise
         for key in self._probe_index:
             self._chunks[key] = []
         self.data = SimulationData(self)
@@ -316,6 +364,9 @@ class Simulator:
 
     def close(self):
         if not self.closed:
+            for r in getattr(self, "_recalls", {}).values():      # (they read the simulator's buffers: gone first)
+                r.close()
+            self._recalls = {}
             self._lib.ssn_destroy(self._h)
             self.closed = True
 
@@ -464,7 +515,7 @@ class Simulator:
                             self._bulk[key] = np.empty((cap, p["width"]), dtype=np.float64)
             else:
                 self.prepare(steps)
-        buf_probes = [(k, v[2]) for k, v in self._probe_index.items() if v[0] == "buf"]
+        buf_probes = [(k, v[2]) for k, v in self._probe_index.items() if v[0] in ("buf", "map")]      # (sampled between step calls)
         self._collector = self._tab_worker = None
         try:
             self._step_loop(steps, profile, pipelined, buf_probes)
@@ -523,7 +574,10 @@ class Simulator:
             # is therefore read BEFORE the timestep whose sample is due.
             for key, p in buf_probes:
                 if (self.n_steps + 1) % p["every"] == 0:
-                    self._chunks[key].append(self.read_buffer(self._probe_buffer_id(p))[None])
+                    if "recall" in p:        # MapProbe: the same instant, L x d_val numbers instead of both matrices
+                        self._chunks[key].append(self._timed_recall(self._recalls[key])[None])
+                    else:
+                        self._chunks[key].append(self.read_buffer(self._probe_buffer_id(p))[None])
             chunk = steps - done
             worker = None
             if pipelined is not None:
@@ -608,6 +662,39 @@ class Simulator:
         if isinstance(b, tuple):
             return self.model.params[p["ens"]].encoder_buffer
         return b
+
+    def _timed_recall(self, rec):
+        t0 = time.perf_counter()
+        out = rec.run()
+        self.recall_seconds += time.perf_counter() - t0
+        self.recall_kernel_ms += rec.info()["last_kernel_ms"]
+        return out
+
+    def recall(self, memory, keys, mode="reference", scratch_bytes=0):
+        """The learned memory recalled for ``keys`` (L x d_key) on the device, from the state the simulator is in now:
+        ``rates(keys @ scaled_encoders.T, gain, bias) @ weights.T`` for ``mode="reference"`` (``harness.map_recall_learned``
+        without reading either matrix back), the population's own steady-state rates for ``mode="network"``.  ``memory``: an
+        ``AssociativeMemory`` or ``(conn_in or ensemble, conn_out)``.  Returns (L, d_val) float64.  No probe is needed; call
+        it between ``run_steps`` calls.  ``scratch_bytes`` bounds the partial sums kept at a time (the result does not depend
+        on it)."""
+        if self.closed:
+            raise fe.SimulationError("simulator is closed")
+        spec = recall_spec(self.model, memory, keys, mode)
+        key = (spec["enc"], spec["dec"], mode, int(scratch_bytes))
+        rec = self._recalls.get(key)
+        if rec is None:
+            rec = self._recalls[key] = DeviceRecall(self, spec, scratch_bytes)
+        else:
+            rec.set_keys(spec["keys"])
+        return self._timed_recall(rec)
+
+    def recall_info(self, probe_or_memory, mode="reference", scratch_bytes=0):
+        """``ssn_recall_info`` of a MapProbe's recall, or of the one ``recall(memory, ...)`` used last with these arguments."""
+        if probe_or_memory in self._recalls:
+            return self._recalls[probe_or_memory].info()
+        ens, conn_out = fe.recall_target(probe_or_memory)
+        key = (self.model.params[ens].encoder_buffer, self.model.params[conn_out].learned_buffer, mode, int(scratch_bytes))
+        return self._recalls[key].info()
 
     _bulk = None
     _bulk_error = None

@@ -59,6 +59,12 @@ def parse(argv=None):
                    help="inhibit the oscillators' neurons (weight -10, through add_neuron_input()) for T0 < t <= T1")
     p.add_argument("--decode-backend", default="numpy", choices=["numpy", "hip"],
                    help="grid decode of the probed trajectory: NumPy on the host, or the GPU grid decoder (decoding.GridDecoder)")
+    p.add_argument("--decode-table", default=None, choices=["host", "device"],
+                   help="with --decode-backend hip: the decoder's sample table encoded on the host and uploaded, or encoded on the "
+                        "GPU from the sample points; prints the decoder-creation seconds")
+    p.add_argument("--encode-backend", default=None, choices=["numpy", "hip"],
+                   help="encode the true path (real_ssp of the metrics) with NumPy or on the GPU (encoding.SSPEncoder); prints the "
+                        "encode seconds")
     p.add_argument("--decode-refine", action="store_true",
                    help="also decode with 'grid-refine' (Newton steps from the grid point) and print both position errors")
     return p.parse_args(argv)
@@ -110,7 +116,15 @@ def main(argv=None):
         spikes, spike_ts = {k: np.array(sim.data[p]) for k, p in spike_probes.items()}, sim.trange(sample_every=skip * dt)
     n = out.shape[0]
     t0 = time.time()
-    est, sims, err = H.pathint_metrics(space, out, pm.real_ssp[:n], path[:n], backend=args.decode_backend)
+    real_ssp, table = pm.real_ssp[:n], args.decode_table or "host"
+    if args.decode_table is not None or args.encode_backend is not None:
+        if table == "device" and args.decode_backend != "hip":
+            raise SystemExit("--decode-table device needs --decode-backend hip")
+        real_ssp, encode_time, creation_time = H.timed_metric_inputs(space, path[:n], args.decode_backend, table, args.encode_backend)
+        print("encode of %d true positions %.3f s (%s); decoder creation %s (table: %s)" % (
+            n, encode_time, args.encode_backend or "numpy", "-" if creation_time is None else "%.3f s" % creation_time, table))
+        t0 = time.time()
+    est, sims, err = H.pathint_metrics(space, out, real_ssp, path[:n], backend=args.decode_backend, table=table)
     decode_time = time.time() - t0
     print("d = %d, %d VCOs x %d neurons, T = %.1f s: build %.1f s, run %.2f s (%.1f sim-s/wall-s), decode %.2f s (%s); similarity "
           "to the true SSP mean %.4f, final position error %.4f" % (space.ssp_dim, (space.ssp_dim + 1) // 2, args.pi_n_neurons, T,
@@ -118,7 +132,7 @@ def main(argv=None):
                                                                    args.decode_backend, sims[min(200, n - 1):].mean(), err[-1]))
     if args.decode_refine:
         t0 = time.time()
-        _, _, err_r = H.pathint_metrics(space, out, pm.real_ssp[:n], path[:n], backend=args.decode_backend, refine=True)
+        _, _, err_r = H.pathint_metrics(space, out, real_ssp, path[:n], backend=args.decode_backend, refine=True, table=table)
         print("position error, grid decode | grid-refine (%.2f s): median %.4f | %.4f, mean %.4f | %.4f, final %.4f | %.4f" % (
             time.time() - t0, np.median(err), np.median(err_r), err.mean(), err_r.mean(), err[-1], err_r[-1]))
     if args.save:

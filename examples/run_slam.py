@@ -50,6 +50,12 @@ def parse(argv=None):
     p.add_argument("--n-eval-points", default=0, type=int, help="decoder-solve evaluation points; 0 = nengo's default")
     p.add_argument("--decode-backend", default="numpy", choices=["numpy", "hip"],
                    help="grid decodes of the trajectory and the recalled map: NumPy on the host, or the GPU grid decoder")
+    p.add_argument("--decode-table", default=None, choices=["host", "device"],
+                   help="with --decode-backend hip: the decoder's sample table encoded on the host and uploaded, or encoded on the "
+                        "GPU from the sample points; prints the decoder-creation seconds")
+    p.add_argument("--encode-backend", default=None, choices=["numpy", "hip"],
+                   help="encode the true path (real_ssp of the metrics) with NumPy or on the GPU (encoding.SSPEncoder); prints the "
+                        "encode seconds")
     p.add_argument("--decode-refine", action="store_true",
                    help="also decode with 'grid-refine' (Newton steps from the grid point) and print both sets of errors")
     p.add_argument("--map-every", default=0.0, type=float, metavar="SECONDS",
@@ -95,16 +101,24 @@ def main(argv=None):
         recall_time, recall_kernel_ms = sim.recall_seconds, sim.recall_kernel_ms
     n = out.shape[0]
     t0 = time.time()
-    est, sims, err = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n], backend=args.decode_backend)
+    real_ssp, table = sm.real_ssp[:n], args.decode_table or "host"
+    if args.decode_table is not None or args.encode_backend is not None:
+        if table == "device" and args.decode_backend != "hip":
+            raise SystemExit("--decode-table device needs --decode-backend hip")
+        real_ssp, encode_time, creation_time = H.timed_metric_inputs(space, path[:n], args.decode_backend, table, args.encode_backend)
+        print("encode of %d true positions %.3f s (%s); decoder creation %s (table: %s)" % (
+            n, encode_time, args.encode_backend or "numpy", "-" if creation_time is None else "%.3f s" % creation_time, table))
+        t0 = time.time()
+    est, sims, err = H.pathint_metrics(space, out, real_ssp, path[:n], backend=args.decode_backend, table=table)
     if args.decode_backend == "hip":
-        lm_locs = space.decode(lm_ssps, "from-set", "grid", 100, backend="hip")
+        lm_locs = space.decode(lm_ssps, "from-set", "grid", 100, backend="hip", table=table)
     else:
         lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend)
     decode_time = time.time() - t0
     lm_over_time = None
     if frames is not None:
         t0 = time.time()
-        lm_over_time = H.map_over_time(space, frames, backend=None if args.decode_backend == "numpy" else args.decode_backend)
+        lm_over_time = H.map_over_time(space, frames, backend=None if args.decode_backend == "numpy" else args.decode_backend, table=table)
         print("map recall: %d samples of %d landmarks every %.3f s: recall %.3f s (kernels %.1f ms), decode %.2f s (%s); median landmark "
               "error first -> last sample %.3f -> %.3f" % (frames.shape[0], frames.shape[1], args.map_every, recall_time, recall_kernel_ms,
                                                         time.time() - t0, args.decode_backend,
@@ -119,9 +133,9 @@ def main(argv=None):
               err[-1], float(np.median(lm_err))))
     if args.decode_refine:
         t0 = time.time()
-        _, _, err_r = H.pathint_metrics(space, out, sm.real_ssp[:n], path[:n], backend=args.decode_backend, refine=True)
+        _, _, err_r = H.pathint_metrics(space, out, real_ssp, path[:n], backend=args.decode_backend, refine=True, table=table)
         if args.decode_backend == "hip":
-            lm_locs_r = space.decode(lm_ssps, "grid-refine", "grid", 100, backend="hip")
+            lm_locs_r = space.decode(lm_ssps, "grid-refine", "grid", 100, backend="hip", table=table)
         else:
             _, lm_locs_r = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend, refine=True)
         lm_err_r = np.linalg.norm(lm_locs_r - sm.obj_locs, axis=1)

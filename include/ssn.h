@@ -417,6 +417,49 @@ int ssn_decoder_refine_rows(ssn_decoder* dec, const double* rows, int64_t n_rows
 int ssn_decoder_refine_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows,
                                    int32_t iterations, double* x, int32_t* best, double* f, int32_t* status);
 
+/* SSP encoding of points on the device (additive to ABI 11; csrc/ssn_encode.hip): SSPSpace.encode as a phase
+ * kernel and one product.  With K bins, M (K x dim: phase_matrix / length_scale of the bins used) and w (K) - what
+ * SSPSpace.refine_tables() returns, host doubles, C order - and th_k = M_k . x,
+ *   encode(x)[c] = sum_{k<K} w_k ( cos th_k cos(2 pi k c / d) - sin th_k sin(2 pi k c / d) ),   c = 0 .. d - 1.
+ * th (an fma chain in axis order) and its sincos are float64 in both dtypes; the product is the k-ordered fmaf chain on the f32 matrix
+ * cores (SSN_F32) or an ordered float64 fma chain (SSN_F64, the parity mode).  An encoder has a stream and a scratch area of its own
+ * (0 = 64 MB; at least ssn_encoder_info.min_scratch_bytes, one 64-point tile) and is independent of ssn_sim.  Points are cut into
+ * chunks that fit the scratch area; the results do not depend on its size, are the same for host and device points of the same
+ * values and the same from run to run.
+ * ssn_encoder_encode: n x dim host doubles (dense) -> n x d host doubles (the encoder's dtype widened).
+ * ssn_encoder_encode_device: points on the host (points_on_device == 0) or on the encoder's device, points_dtype SSN_F32 / SSN_F64,
+ * leading dimension points_ld >= dim (elements) -> a device buffer of the encoder's dtype with leading dimension out_ld >= d, complete
+ * when the call returns.
+ * SSN_EINVAL: null handle or argument, dim < 1, K < 1 or above d, d outside 1 .. 2^20, a leading dimension below the width, scratch
+ * too small; SSN_EHIP "no HIP device available (there is no CPU fallback)" without a GPU; n == 0 succeeds and writes nothing. */
+typedef struct ssn_encoder ssn_encoder;
+typedef struct ssn_encoder_info {
+  int64_t row_chunk;          /* points per chunk (whole tiles)                                                  */
+  int64_t n_chunks;           /* for the n asked about                                                           */
+  int64_t tile;               /* points per tile (64)                                                            */
+  int64_t scratch_bytes;
+  int64_t min_scratch_bytes;  /* one tile                                                                        */
+  int64_t padded_2k;          /* columns of P and B: 2K padded to a multiple of 32                               */
+  int64_t last_launches;      /* kernel launches of the last encode call                                         */
+  double last_kernel_ms;      /* their device time (HIP events around the kernels of every chunk, copies outside) */
+  double last_phase_ms;       /* of which k_encode_phase                                                         */
+  double last_product_ms;     /* and the product (in f32 with the widening of a host-output call)                */
+} ssn_encoder_info;
+int ssn_encoder_create(int32_t dtype, int32_t device, int64_t d, int64_t K, int32_t dim, const double* M, const double* w,
+                       int64_t scratch_bytes /* 0 = default */, ssn_encoder** out);
+void ssn_encoder_destroy(ssn_encoder* enc);
+int ssn_encoder_encode(ssn_encoder* enc, const double* points, int64_t n, double* out);
+int ssn_encoder_encode_device(ssn_encoder* enc, const void* points, int32_t points_on_device, int32_t points_dtype, int64_t points_ld,
+                              int64_t n, void* out_dev, int64_t out_ld);
+int ssn_encoder_get_info(ssn_encoder* enc, int64_t n, ssn_encoder_info* out);
+/* A decoder whose table is made on the device: the n_samples x dim sample points (host doubles) are encoded by a float64 encoder
+ * (d = width, K, dim, M, w as above; enc_scratch_bytes its scratch area, 0 = default) chunk by chunk, each chunk written straight
+ * into the decoder's padded table in the decoder's dtype.  The table never exists on the host; device memory peaks at the table
+ * plus the two scratch areas.  The decoder is in every other respect the one ssn_decoder_create makes. */
+int ssn_decoder_create_from_points(int32_t dtype, int32_t device, const double* points, int64_t n_samples, int64_t width, int64_t K,
+                                   int32_t dim, const double* M, const double* w, int64_t scratch_bytes /* 0 = default */,
+                                   int64_t enc_scratch_bytes /* 0 = default */, ssn_decoder** out);
+
 /* Recall of a learned associative memory on the device (additive to ABI 11; csrc/ssn_recall.hip): for the dense
  * population whose scaled encoders are buffer `enc_buffer` (n x d_key, the matrix Voja moves) and one of whose outgoing
  * connections has the decoders `dec_buffer` (d_val x n, the matrix PES moves), and for n_keys key rows V (host doubles, C order),

@@ -97,6 +97,12 @@ class DecoderInfo(C.Structure):
                 ("padded_width", C.c_int64), ("last_launches", C.c_int64), ("last_kernel_ms", C.c_double)]
 
 
+class EncoderInfo(C.Structure):
+    _fields_ = [("row_chunk", C.c_int64), ("n_chunks", C.c_int64), ("tile", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("min_scratch_bytes", C.c_int64), ("padded_2k", C.c_int64), ("last_launches", C.c_int64),
+                ("last_kernel_ms", C.c_double), ("last_phase_ms", C.c_double), ("last_product_ms", C.c_double)]
+
+
 class RecallInfo(C.Structure):
     _fields_ = [("n", C.c_int64), ("d_key", C.c_int64), ("d_val", C.c_int64), ("n_keys", C.c_int64), ("padded_keys", C.c_int64),
                 ("chunk", C.c_int64), ("n_chunks", C.c_int64), ("chunks_per_pass", C.c_int64), ("scratch_bytes", C.c_int64),
@@ -144,6 +150,14 @@ EXPORTS = {
     "ssn_decoder_refine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssn_decoder_refine_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    "ssn_encoder_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.POINTER(C.c_void_p)]),
+    "ssn_encoder_destroy": (None, [C.c_void_p]),
+    "ssn_encoder_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ssn_encoder_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "ssn_encoder_get_info": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(EncoderInfo)]),
+    "ssn_decoder_create_from_points": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "ssn_recall_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "ssn_recall_destroy": (None, [C.c_void_p]),

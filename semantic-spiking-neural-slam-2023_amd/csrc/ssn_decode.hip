@@ -30,6 +30,9 @@
 // Scratch (fixed at creation, default 64 MB): per row K doubles of upload staging, Kp converted values, one (value, column)
 // partial per strip slot and the (double similarity, best) result.  The host cuts n_rows into chunks of whole row tiles that fit and the
 // column walk into at most `slots` strips (decode_plan); the smallest scratch holds one row tile with one strip.
+//
+// The table comes from the host (ssn_decoder_create: converted and uploaded) or is made here from the sample points
+// (ssn_decoder_create_from_points: a float64 ssn_encoder of csrc/ssn_encode.hip writes it chunk by chunk in the decoder's dtype).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -40,6 +43,7 @@
 #include <memory>
 #include <vector>
 #include "../../include/ssn.h"
+#include "ssn_encode.hpp"       // encoder_encode_into: the table of ssn_decoder_create_from_points
 #include "ssn_kernels.hpp"      // launch_gemm_nt / launch_argmax_partial: the materialising composition ssn_decoder_rows_composed times
 
 namespace {
@@ -708,20 +712,28 @@ int decode_rows_composed(ssn_decoder* d, const double* host, int64_t n_rows, int
   return rc;
 }
 
-}  // namespace
+// the table made where it is used: a float64 encoder of its own writes every chunk of sample points into the padded table, in
+// the decoder's dtype; the encoder and its scratch area go away before the decoder is handed out
+int encode_table(ssn_decoder* d, const double* points, int64_t K, int32_t dim, const double* M, const double* w, int64_t enc_scratch_bytes) {
+  const int64_t Sp = d->col_tiles * TILE;
+  DHIP(hipMalloc(&d->table, (size_t)Sp * d->Kp * d->esz));
+  DHIP(hipMemset(d->table, 0, (size_t)Sp * d->Kp * d->esz));
+  ssn_encoder* enc = nullptr;
+  int rc = ssn_encoder_create(SSN_F64, d->device, d->K, K, dim, M, w, enc_scratch_bytes, &enc);
+  if (rc != SSN_OK) return rc;
+  rc = ssn::encoder_encode_into(enc, points, d->S, d->table, d->dtype, d->Kp);
+  ssn_encoder_destroy(enc);
+  return rc;
+}
 
-extern "C" {
-
-int ssn_decoder_create(int32_t dtype, int32_t device, const double* table, int64_t n_samples, int64_t width, int64_t scratch_bytes,
-                       ssn_decoder** out) {
-  if (!out) return fail(SSN_EINVAL, "ssn_decoder_create: null handle");
-  *out = nullptr;
-  if (!table) return fail(SSN_EINVAL, "ssn_decoder_create: null table");
-  if (dtype != SSN_F32 && dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_create: unknown dtype %d", dtype);
-  if (width <= 0 || width > (1 << 20)) return fail(SSN_EINVAL, "ssn_decoder_create: width %lld outside 1 .. 2^20", (long long)width);
+// what ssn_decoder_create and ssn_decoder_create_from_points share: checks, stream, events and scratch; `fill` makes the table
+template <typename Fill>
+int create_decoder(const char* who, int32_t dtype, int32_t device, int64_t n_samples, int64_t width, int64_t scratch_bytes, ssn_decoder** out, Fill fill) {
+  if (dtype != SSN_F32 && dtype != SSN_F64) return fail(SSN_EINVAL, "%s: unknown dtype %d", who, dtype);
+  if (width <= 0 || width > (1 << 20)) return fail(SSN_EINVAL, "%s: width %lld outside 1 .. 2^20", who, (long long)width);
   if (n_samples <= 0 || n_samples > INT32_MAX)
-    return fail(SSN_EINVAL, "ssn_decoder_create: n_samples %lld outside 1 .. 2^31 - 1", (long long)n_samples);
-  if (scratch_bytes < 0) return fail(SSN_EINVAL, "ssn_decoder_create: negative scratch_bytes");
+    return fail(SSN_EINVAL, "%s: n_samples %lld outside 1 .. 2^31 - 1", who, (long long)n_samples);
+  if (scratch_bytes < 0) return fail(SSN_EINVAL, "%s: negative scratch_bytes", who);
   std::unique_ptr<ssn_decoder> d(new ssn_decoder);
   d->dtype = dtype;
   d->device = device;
@@ -732,13 +744,13 @@ int ssn_decoder_create(int32_t dtype, int32_t device, const double* table, int64
   d->col_tiles = (n_samples + TILE - 1) / TILE;
   d->scratch_bytes = scratch_bytes ? scratch_bytes : std::max<int64_t>((int64_t)64 << 20, d->min_scratch());
   if (d->scratch_bytes < d->min_scratch())
-    return fail(SSN_EINVAL, "ssn_decoder_create: scratch_bytes %lld too small for one %d-row tile of width %lld (%lld bytes)", (long long)scratch_bytes,
+    return fail(SSN_EINVAL, "%s: scratch_bytes %lld too small for one %d-row tile of width %lld (%lld bytes)", who, (long long)scratch_bytes,
                 TILE, (long long)width, (long long)d->min_scratch());
   int ndev = 0;
   const hipError_t dev_err = hipGetDeviceCount(&ndev);
   if (dev_err != hipSuccess || ndev <= 0)
     return fail(SSN_EHIP, "no HIP device available (there is no CPU fallback): hipGetDeviceCount -> %s, %d devices", hipGetErrorString(dev_err), ndev);
-  if (device < 0 || device >= ndev) return fail(SSN_EINVAL, "ssn_decoder_create: device %d out of range (%d devices)", device, ndev);
+  if (device < 0 || device >= ndev) return fail(SSN_EINVAL, "%s: device %d out of range (%d devices)", who, device, ndev);
   DevGuard g(device);
   hipDeviceProp_t prop;
   DHIP(hipGetDeviceProperties(&prop, device));
@@ -747,10 +759,34 @@ int ssn_decoder_create(int32_t dtype, int32_t device, const double* table, int64
   DHIP(hipEventCreate(&d->e0));
   DHIP(hipEventCreate(&d->e1));
   DHIP(hipMalloc((void**)&d->scratch, (size_t)d->scratch_bytes));
-  const int rc = dtype == SSN_F32 ? upload_table<float>(d.get(), table) : upload_table<double>(d.get(), table);
+  const int rc = fill(d.get());
   if (rc != SSN_OK) return rc;
   *out = d.release();
   return SSN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ssn_decoder_create(int32_t dtype, int32_t device, const double* table, int64_t n_samples, int64_t width, int64_t scratch_bytes,
+                       ssn_decoder** out) {
+  if (!out) return fail(SSN_EINVAL, "ssn_decoder_create: null handle");
+  *out = nullptr;
+  if (!table) return fail(SSN_EINVAL, "ssn_decoder_create: null table");
+  return create_decoder("ssn_decoder_create", dtype, device, n_samples, width, scratch_bytes, out, [&](ssn_decoder* d) {
+    return dtype == SSN_F32 ? upload_table<float>(d, table) : upload_table<double>(d, table);
+  });
+}
+
+int ssn_decoder_create_from_points(int32_t dtype, int32_t device, const double* points, int64_t n_samples, int64_t width, int64_t K, int32_t dim,
+                                   const double* M, const double* w, int64_t scratch_bytes, int64_t enc_scratch_bytes, ssn_decoder** out) {
+  if (!out) return fail(SSN_EINVAL, "ssn_decoder_create_from_points: null handle");
+  *out = nullptr;
+  if (!points || !M || !w) return fail(SSN_EINVAL, "ssn_decoder_create_from_points: null argument");
+  return create_decoder("ssn_decoder_create_from_points", dtype, device, n_samples, width, scratch_bytes, out, [&](ssn_decoder* d) {
+    return encode_table(d, points, K, dim, M, w, enc_scratch_bytes);
+  });
 }
 
 void ssn_decoder_destroy(ssn_decoder* dec) { delete dec; }

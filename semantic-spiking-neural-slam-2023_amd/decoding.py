@@ -40,25 +40,38 @@ class GridDecoder:
     needed for ``clean_up``).  ``dtype``: "f32" (matrix cores; the index agrees with the float64 host answer wherever the two best
     similarities differ by more than the f32 error of the product) or "f64" (parity mode).  ``scratch_bytes``: size of the device
     work area (default 64 MB); a smaller one only means more row chunks and fewer column strips, never another answer.
+    ``table``: "host" (the default) encodes the sample table on the host and uploads it; "device" takes only
+    ``ssp_space.get_sample_points`` and has a float64 ``ssn_encoder`` make the table on the GPU, chunk by chunk, straight into the
+    decoder's dtype (``ssn_decoder_create_from_points``) - the table never exists on the host.  Beside ``samples=``
+    it is a ValueError: the caller already holds the SSPs.
 
     Rows are scaled as the host scales them (divided by their norm when it is >= 1e-6).  Non-finite rows are out of contract: their
     index is some value inside ``[0, n_samples)``.
     """
 
     def __init__(self, ssp_space=None, num_samples=100, sampling_method="grid", samples=None, dtype="f32", device=0,
-                 scratch_bytes=None, trust=None):
+                 scratch_bytes=None, trust=None, table="host"):
         if dtype not in ("f32", "f64"):
             raise ValueError(f"dtype must be 'f32' or 'f64', got {dtype!r}")
+        if table not in ("host", "device"):
+            raise ValueError(f"table must be 'host' or 'device', got {table!r}")
+        if table == "device" and samples is not None:
+            raise ValueError("table='device' makes the table from the space's sample points; with samples= the caller already holds the SSPs")
+        if samples is None and ssp_space is None:
+            raise ValueError("GridDecoder needs an ssp_space or samples=(sample_ssps, sample_points)")
+        self.ssp_space = ssp_space
+        self.table_source = table
+        self._encoder = None          # the SSPEncoder of clean_up(encode="device"), made on first use
+        if table == "device":
+            self._init_from_points(num_samples, sampling_method, dtype, device, scratch_bytes, trust)
+            return
         if samples is None:
-            if ssp_space is None:
-                raise ValueError("GridDecoder needs an ssp_space or samples=(sample_ssps, sample_points)")
             sample_ssps, sample_points = ssp_space.get_sample_pts_and_ssps(num_samples, sampling_method)
         else:
             sample_ssps, sample_points = samples
         table = np.ascontiguousarray(np.asarray(sample_ssps, dtype=np.float64))
         if table.ndim != 2:
             raise ValueError(f"sample_ssps must be (n_samples, width), got shape {table.shape}")
-        self.ssp_space = ssp_space
         self.sample_points = np.asarray(sample_points)
         # the box of refine(): the pitch of the space's own grid, or trust= beside samples=
         self._grid = (num_samples, sampling_method) if samples is None else None
@@ -70,6 +83,26 @@ class GridDecoder:
         self.closed = True
         rc = self._lib.ssn_decoder_create(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, table.ctypes.data,
                                           self.n_samples, self.width, int(scratch_bytes or 0), C.byref(self._h))
+        if rc != 0:
+            raise fe.BuildError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
+        self.closed = False
+
+    def _init_from_points(self, num_samples, sampling_method, dtype, device, scratch_bytes, trust):
+        from .encoding import tables
+        space = self.ssp_space
+        pts = np.ascontiguousarray(space.get_sample_points(num_samples, sampling_method), dtype=np.float64)
+        K, M, w = tables(space)
+        self.sample_points = pts
+        self._grid = (num_samples, sampling_method)
+        self._trust, self._refine_key = trust, None
+        self.n_samples, self.width = int(pts.shape[0]), int(space.ssp_dim)
+        self.dtype, self.device = dtype, int(device)
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.closed = True
+        rc = self._lib.ssn_decoder_create_from_points(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, pts.ctypes.data,
+                                                      self.n_samples, self.width, K, int(space.domain_dim), M.ctypes.data, w.ctypes.data,
+                                                      int(scratch_bytes or 0), 0, C.byref(self._h))
         if rc != 0:
             raise fe.BuildError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
         self.closed = False
@@ -86,6 +119,9 @@ class GridDecoder:
         self.close()
 
     def close(self):
+        enc = self.__dict__.pop("_encoder", None)
+        if enc is not None:
+            enc.close()
         if not self.closed:
             self._lib.ssn_decoder_destroy(self._h)
             self.closed = True
@@ -226,8 +262,24 @@ class GridDecoder:
             return self.sample_points[best], sims
         return self.sample_points[self.indices(rows)]
 
-    def clean_up(self, rows):
-        """The SSPs of the decoded points: ``ssp_space.encode(decode(rows))``."""
+    def clean_up(self, rows, refine=False, encode="host", out="host", iterations=8):
+        """The SSPs of the decoded (``refine=True``: refined) points: ``ssp_space.encode(decode(rows))``.  ``encode``: "host" is the
+        space's float64 NumPy transform; "device" / "hip" encode the points with an ``SSPEncoder`` of the decoder's dtype on the
+        decoder's device, and ``out="device"`` then leaves the rows there as a torch tensor."""
         if self.ssp_space is None:
             raise ValueError("clean_up needs the decoder's ssp_space")
-        return self.ssp_space.encode(self.decode(rows))
+        if encode not in ("host", "device", "hip"):
+            raise ValueError(f"encode must be 'host', 'device' or 'hip', got {encode!r}")
+        if out not in ("host", "device"):
+            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+        if encode == "host" and out == "device":
+            raise ValueError("out='device' needs encode='device': the host encode returns a NumPy array")
+        points = self.decode(rows, refine=refine, iterations=iterations)
+        if encode == "host":
+            return self.ssp_space.encode(points)
+        if self.closed:
+            raise fe.SimulationError("the decoder is closed")
+        if self._encoder is None:
+            from .encoding import SSPEncoder
+            self._encoder = SSPEncoder(self.ssp_space, dtype=self.dtype, device=self.device)
+        return self._encoder.encode(points, out=out)

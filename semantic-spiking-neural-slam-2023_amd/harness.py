@@ -96,14 +96,41 @@ def make_pathint_model(ssp_space, path, vels, pi_n_neurons, tau=0.05, neuron_typ
     return out
 
 
-def pathint_metrics(ssp_space, sim_out, real_ssp, path, num_samples=None, backend=None, refine=False):
+def _table_arg(table):
+    """``table=`` of the decode calls below, handed on only when it is not the default ("host": the decoder's sample table encoded on
+    the host; "device": encoded on the GPU from the sample points, hip backends only)."""
+    return {} if table == "host" else {"table": table}
+
+
+def timed_metric_inputs(ssp_space, path, decode_backend=None, table="host", encode_backend=None, num_samples=None):
+    """What the example scripts time beside the decode when ``--decode-table`` / ``--encode-backend`` are given:
+    ``(real_ssp, encode_seconds, creation_seconds)``.  ``real_ssp = ssp_space.encode(path, backend=encode_backend)``;
+    ``creation_seconds`` is the making of the GPU grid decoder ``pathint_metrics`` will find cached on the space (its sample table
+    encoded on the host and uploaded, or encoded on the GPU: ``table``), None when the decode runs on the host."""
+    import time
+    from .decoding import backend_dtype
+    if num_samples is None:
+        num_samples = 100 if ssp_space.domain_dim < 3 else 50
+    t0 = time.time()
+    real_ssp = ssp_space.encode(path, backend=encode_backend)
+    encode_seconds = time.time() - t0
+    creation_seconds = None
+    dtype = backend_dtype(decode_backend)
+    if dtype is not None:
+        t0 = time.time()
+        ssp_space._grid_decoder(num_samples, "grid", dtype, table)
+        creation_seconds = time.time() - t0
+    return real_ssp, encode_seconds, creation_seconds
+
+
+def pathint_metrics(ssp_space, sim_out, real_ssp, path, num_samples=None, backend=None, refine=False, table="host"):
     """(sim_path_est, pi_sims, pi_error) as ``run_pathint.py:179-184``.  ``backend``: decode backend of ``SSPSpace.decode``
     (None: NumPy on the host, "hip": the GPU grid decoder).  ``refine``: decode with 'grid-refine' (Newton steps from the grid
     point) instead of 'from-set', which lifts the half-pitch floor of the position error."""
     if num_samples is None:
         num_samples = 100 if ssp_space.domain_dim < 3 else 50
     n = sim_out.shape[0]
-    est = ssp_space.decode(sim_out, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)
+    est = ssp_space.decode(sim_out, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend, **_table_arg(table))
     nrm = np.linalg.norm(sim_out, axis=1)
     sims = np.sum(sim_out * real_ssp[:n], axis=1) / np.where(nrm == 0, 1.0, nrm)
     err = np.sqrt(np.sum((path[:n] - est) ** 2, axis=1))
@@ -297,16 +324,16 @@ def get_activities(built_ens, neuron_type, x):
     return neuron_type.rates(proj, built_ens.gain, built_ens.bias)
 
 
-def map_recall(ssp_space, lm_space, built_memory, neuron_type, final_decoders, backend=None, refine=False):
+def map_recall(ssp_space, lm_space, built_memory, neuron_type, final_decoders, backend=None, refine=False, table="host"):
     """Definition (i) of map recall, ``run_slam.py:263-268``: activities of the *built* (pre-Voja)
     memory ensemble for each landmark SP times the final PES decoders -> decoded landmark positions."""
     acts = get_activities(built_memory, neuron_type, lm_space.vectors)
     recalled = acts @ np.asarray(final_decoders).T
-    return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", 100, backend=backend)
+    return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", 100, backend=backend, **_table_arg(table))
 
 
 def map_recall_learned(ssp_space, lm_space, built_memory, neuron_type, final_scaled_encoders, final_decoders,
-                       num_samples=100, backend=None, refine=False):
+                       num_samples=100, backend=None, refine=False, table="host"):
     """Definition (ii) of map recall, ``slam_map_new.py:342-347`` / ``:447-452``: the landmark SPs are projected on the
     FINAL scaled encoders (``Probe(conn_in.learning_rule, "scaled_encoders")[-1]``, i.e. after Voja moved them) and
     pushed through ``neuron_type.rates(x, gain, bias)``, then through the final PES decoders.
@@ -316,10 +343,10 @@ def map_recall_learned(ssp_space, lm_space, built_memory, neuron_type, final_sca
     x = np.asarray(lm_space.vectors) @ np.asarray(final_scaled_encoders).T
     acts = neuron_type.rates(x, built_memory.gain, built_memory.bias)
     recalled = acts @ np.asarray(final_decoders).T
-    return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)
+    return recalled, ssp_space.decode(recalled, "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend, **_table_arg(table))
 
 
-def map_over_time(ssp_space, frames, num_samples=100, backend=None, refine=False):
+def map_over_time(ssp_space, frames, num_samples=100, backend=None, refine=False, table="host"):
     """Decoded landmark positions of a ``MapProbe``: ``frames`` (samples, L, d) -> (samples, L, domain_dim), every recalled row
     decoded as ``map_recall_learned`` decodes its rows (``run_slam_map_gif.py:323-329`` per frame), all rows in one decode call
     (``backend``: None for NumPy on the host, "hip" for the GPU grid decoder; ``refine``: 'grid-refine')."""
@@ -329,5 +356,5 @@ def map_over_time(ssp_space, frames, num_samples=100, backend=None, refine=False
     s, n_keys, d = frames.shape
     if s * n_keys == 0:
         return np.zeros((s, n_keys, ssp_space.domain_dim))
-    est = ssp_space.decode(frames.reshape(s * n_keys, d), "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend)
+    est = ssp_space.decode(frames.reshape(s * n_keys, d), "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend, **_table_arg(table))
     return np.asarray(est).reshape(s, n_keys, -1)

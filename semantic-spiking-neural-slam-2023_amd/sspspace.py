@@ -138,8 +138,16 @@ class SSPSpace:
     def encode_fourier(self, x):
         return np.exp(1j * (self._scaled(x) @ self.phase_matrix.T))
 
-    def encode(self, x):
-        """(num_samples, domain_dim) -> (num_samples, ssp_dim) unit-norm SSPs."""
+    def encode(self, x, backend=None):
+        """(num_samples, domain_dim) -> (num_samples, ssp_dim) unit-norm SSPs.
+
+        ``backend``: None (or "numpy") is the float64 host transform below; "hip" / "hip-f64" encode on the GPU through an
+        ``encoding.SSPEncoder`` cached on the space (f32 matrix cores / f64 parity mode)."""
+        if backend is not None:
+            from .encoding import backend_dtype
+            dtype = backend_dtype(backend)
+            if dtype is not None:
+                return self._ssp_encoder(dtype).encode(x)
         x = np.atleast_2d(np.asarray(x, dtype=float))
         rows = max(1, (1 << 22) // self.ssp_dim)
         if x.shape[0] <= 4 * rows:
@@ -231,21 +239,34 @@ class SSPSpace:
     def __getstate__(self):
         state = dict(self.__dict__)
         state.pop("_decoder_cache", None)          # device handles stay with the object they were made for
+        state.pop("_encoder_cache", None)
         return state
 
     def _drop_decoders(self):
         for dec in self.__dict__.pop("_decoder_cache", {}).values():
             dec.close()
+        for enc in self.__dict__.pop("_encoder_cache", {}).values():
+            enc.close()
 
-    def _grid_decoder(self, num_samples, sampling_method, dtype):
+    def _grid_decoder(self, num_samples, sampling_method, dtype, table="host"):
         """The GridDecoder of backend="hip" for this sample set, kept next to ``_grid_cache`` (one at a time: it holds the table on
         the GPU) and dropped by ``update_lengthscale``."""
         from .decoding import GridDecoder
-        key = (int(num_samples), sampling_method, dtype)
+        key = (int(num_samples), sampling_method, dtype) + (() if table == "host" else (table,))
         if key not in self.__dict__.get("_decoder_cache", {}):
-            self._drop_decoders()
-            self._decoder_cache = {key: GridDecoder(self, num_samples, sampling_method, dtype=dtype)}
+            for dec in self.__dict__.pop("_decoder_cache", {}).values():
+                dec.close()
+            self._decoder_cache = {key: GridDecoder(self, num_samples, sampling_method, dtype=dtype, table=table)}
         return self._decoder_cache[key]
+
+    def _ssp_encoder(self, dtype, device=0):
+        """The SSPEncoder of backend="hip", one per (dtype, device), dropped by ``update_lengthscale`` like the decoder."""
+        from .encoding import SSPEncoder
+        cache = self.__dict__.setdefault("_encoder_cache", {})
+        key = (dtype, int(device))
+        if key not in cache:
+            cache[key] = SSPEncoder(self, dtype=dtype, device=device)
+        return cache[key]
 
     # -- sub-grid refinement ('grid-refine') ---------------------------------------------------
     def refine_tables(self):
@@ -339,7 +360,7 @@ class SSPSpace:
                           + np.any(np.abs(last) > 1e-6 * pitch[None, :], axis=1) * 4)
         return x, f, status
 
-    def _decode_refine(self, ssp, sampling_method, num_samples, samples, backend, iterations, trust, return_info):
+    def _decode_refine(self, ssp, sampling_method, num_samples, samples, backend, iterations, trust, return_info, table="host"):
         from .decoding import GridDecoder, backend_dtype
         dtype = backend_dtype(backend)
         iterations = int(iterations)
@@ -352,8 +373,8 @@ class SSPSpace:
                              "which a grid's pitch gives when the space makes the samples")
         if dtype is not None:
             if samples is None:
-                return self._grid_decoder(num_samples, sampling_method, dtype).refine(ssp, iterations, return_info, trust=trust)
-            with GridDecoder(self, samples=samples, dtype=dtype, trust=trust) as dec:
+                return self._grid_decoder(num_samples, sampling_method, dtype, table).refine(ssp, iterations, return_info, trust=trust)
+            with GridDecoder(self, samples=samples, dtype=dtype, trust=trust, table=table) as dec:
                 return dec.refine(ssp, iterations, return_info)
         lo, hi, pitch = self.refine_box(num_samples, sampling_method, trust)
         sample_ssps, sample_points = self.get_sample_pts_and_ssps(num_samples, sampling_method) if samples is None else samples
@@ -377,16 +398,23 @@ class SSPSpace:
         return unit, best
 
     def decode(self, ssp, method="from-set", sampling_method="grid", num_samples=300,
-               samples=None, backend=None, iterations=8, trust=None, return_info=False, **kwargs):
+               samples=None, backend=None, iterations=8, trust=None, return_info=False, table="host", **kwargs):
         """``backend``: None (or "numpy") is the float64 host product below; "hip" / "hip-f64" run it on the GPU through a
-        ``decoding.GridDecoder`` (f32 matrix cores / f64 parity mode).
+        ``decoding.GridDecoder`` (f32 matrix cores / f64 parity mode).  ``table``: "host" encodes the decoder's sample table here
+        and uploads it, "device" has the GPU encode it from the sample points (hip backends only).
 
         ``method='grid-refine'``: the 'from-set' decode followed by ``iterations`` safeguarded Newton steps on
         ``<encode(x), ssp>`` inside the box ``x0 +- pitch`` of the sample grid (``trust``, required, beside ``samples=``); the rule
         is DESIGN.md 3.12, in float64 NumPy here and in ``csrc/ssn_decode.hip`` behind the hip backends.  With ``return_info``
         it returns ``(x, f, status, best)``."""
+        if table != "host":
+            from .decoding import backend_dtype
+            if table != "device":
+                raise ValueError(f"table must be 'host' or 'device', got {table!r}")
+            if backend_dtype(backend) is None:
+                raise ValueError("table='device' needs a hip backend: the NumPy decode has no device table")
         if method == "grid-refine":
-            return self._decode_refine(ssp, sampling_method, num_samples, samples, backend, iterations, trust, return_info)
+            return self._decode_refine(ssp, sampling_method, num_samples, samples, backend, iterations, trust, return_info, table)
         if method != "from-set":
             raise NotImplementedError(
                 f"decode method {method!r}: only 'from-set' and 'grid-refine' are implemented (SURVEY §2 row 6)"
@@ -395,9 +423,9 @@ class SSPSpace:
             from .decoding import GridDecoder, backend_dtype
             dtype = backend_dtype(backend)
             if dtype is not None and samples is None:
-                return self._grid_decoder(num_samples, sampling_method, dtype).decode(ssp)
+                return self._grid_decoder(num_samples, sampling_method, dtype, table).decode(ssp)
             if dtype is not None:
-                with GridDecoder(self, samples=samples, dtype=dtype) as dec:
+                with GridDecoder(self, samples=samples, dtype=dtype, table=table) as dec:
                     return dec.decode(ssp)
         if samples is None:
             sample_ssps, sample_points = self.get_sample_pts_and_ssps(num_samples, sampling_method)
@@ -405,8 +433,9 @@ class SSPSpace:
             sample_ssps, sample_points = samples
         return sample_points[self._best_samples(ssp, sample_ssps)[1]]
 
-    def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300, backend=None, **kwargs):
-        return self.encode(self.decode(ssp, method, sampling_method, num_samples, backend=backend, **kwargs))
+    def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300, backend=None, encode_backend=None, **kwargs):
+        """``encode(decode(ssp))``.  ``encode_backend``: the backend of that ``encode`` (None: the host; "hip" / "hip-f64")."""
+        return self.encode(self.decode(ssp, method, sampling_method, num_samples, backend=backend, **kwargs), backend=encode_backend)
 
     # -- algebra ---------------------------------------------------------------------------
     def normalize(self, ssp):

@@ -82,11 +82,6 @@ __device__ inline f32x2 pk_clamp01(f32x2 x) {
   asm("v_pk_mul_f32 %0, %1, 1.0 op_sel_hi:[1,0] clamp" : "=v"(r) : "v"(x));
   return r;
 }
-__device__ inline f32x2 pk_sub_clamp01(f32x2 x, f32x2 y) {          // clamp(x - y), y a uniform constant pair
-  f32x2 r;
-  asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(r) : "v"(x), "s"(y));
-  return r;
-}
 __device__ inline f32x2 pk_mul_clamp01(f32x2 x, f32x2 y) {
   f32x2 r;
   asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(x), "s"(y));          // (y: a uniform constant pair)
@@ -107,84 +102,59 @@ __device__ inline f32x2 pk_fma_clamp01_trans_vvs(f32x2 x, f32x2 y, f32x2 z) {
   return r;
 }
 
-__device__ inline f32x2 pk_fma_clamp01_vs_negv(f32x2 x, f32x2 y, f32x2 z) {     // clamp(x * y - z), y a uniform constant pair
-  f32x2 r;
-  asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1] clamp" : "=v"(r) : "v"(x), "s"(y), "v"(z));
-  return r;
-}
-
 // Branch-free f32 LIF step, TWO neurons per call in the two halves of 64-bit register pairs, built ONLY from packed
-// multiply / add / FMA (v_pk_*_f32: 2 flops per lane per issue slot) plus one v_rcp_f32 and one v_log_f32 per neuron:
+// multiply / add / FMA (v_pk_*_f32: 2 flops per lane per issue slot) plus one v_rcp_f32 per neuron:
 // no compare, no select, no integer min / max.  On gfx950 every non-FMA vector instruction (v_cndmask, v_cmp, v_max_i32,
 // v_med3 ...) costs a full issue slot of its own per NEURON where a packed one serves two (v_cndmask: five of them - measured,
 // tools/valu_issue_rate.hip, profiles/round3_valu_issue_rate.txt), so the selects of nengo's LIF step (SURVEY
 // Appendix A.4) are rewritten as exact arithmetic on {0, 1} indicators made with the clamp modifier.
 //
-// Inside the time loop the state word is w = 1 - V for a neuron that integrates (0 <= w <= 1: the distance to the threshold)
-// and w = 1 + K (R - dt) for a refractory one (R = refractory time left at the start of the next step, > dt; K a power of two
-// with K tau_ref <= 1: times in units of 1 / K so that they fit the clamp's [0, 1] without losing bits next to the 1).  The
-// input current arrives as J - 1 (the bias registers hold bias - 1).  With everything measured from the threshold, V - 1 and
-// J - 1 - the operands of the spike test and of the spike time - are what the update produces anyway: 15 packed operations
-// per neuron pair against 19 with V and J (round 3's second cut; the words in HBM keep round 2's form, see the prologue).
+// Inside the time loop the state word is w = 1 - V for a neuron that integrates (0 <= w <= 1: the distance to the threshold).
+// A refractory neuron holds, instead of a time, what its NEXT integration needs: with rho = R - dt > 0 the refractory time left
+// after the coming step, g = exp((rho - dt) / tau_rc) is exp(-delta / tau_rc) of that step (delta = clip(dt - rho, 0, dt)),
+// and the word is w = 1 + kappa (g - q), q = exp(-dt / tau_rc), kappa a power of two that maps the range of g - q onto (0, 1].
+// nengo's spike time t_spike = dt + tau_rc log1p(-u), u = (V - 1) / (J - 1), then gives g = C1 (1 - u) with
+// C1 = exp((tau_ref - dt) / tau_rc): the logarithm at the spike and the exponential at the end of the refractory period cancel,
+// g is AFFINE in u, one more step of waiting multiplies it by q, and em = -expm1(-delta / tau_rc) = clip(1 - g, 0, E1),
+// E1 = 1 - q, is affine in w.  No polynomial, no logarithm: 11 packed operations per neuron pair (16 with the two interpolants
+// this replaces, whose errors - 2.3e-7 and 5e-8 - went with them).  The input current arrives as JE = E1 (J - 1): the bias
+// registers hold (bias - 1) E1, the encoder entries are multiplied by E1 as they are loaded (the buffers in HBM are unchanged).
+// With h = dt / tau_rc:  a = 1 / (kappa E1), c = a + 1 rounded up, m1 = 1 + kappa E1, A = kappa (C1 - q), B = kappa C1 E1.
 //
 //   W0 = clamp(w)                 1 - V0  (V0 = 0 while refractory)
-//   dl = clamp(c - a w)           integration time / dt  (nengo: clip(dt - refractory, 0, dt)): a = 1 / (K dt), c = a + 1 rounded
-//                                 up, so that every integrating neuron (w <= 1) gets exactly 1 and a refractory one 1 - (R - dt) / dt
-//   nmt = clamp(w - (1 + K dt))   > 0 while the neuron stays refractory beyond the next step: its new word is 1 + nmt
-//   em = dl * P(dl)               -expm1(-delta / tau_rc), P of degree 2: the interpolant of (1 - exp(-x)) / x through x = h,
-//                                 h / 2, 0.067 h with h = dt / tau_rc <= 1/20 - EXACT for a full step (delta = dt, all steps
-//                                 but the one in which a refractory period ends), within 2.3e-7 of the result for a partial
-//                                 one (a 4-term Taylor polynomial, one operation more, was within 5.3e-8 everywhere)
-//   U  = (Jm1 + W0) * em - W0     V - 1 = V0 + (J - V0) em - 1
+//   dl = clamp(c - a w)           em / E1 = clamp((1 - g) / E1): exactly 1 for every integrating neuron (w <= 1; c - a >= 1 in exact
+//                                 arithmetic), 0 for one that stays refractory through the step (g >= 1)
+//   nmt = clamp(q w - q m1)       kappa (q g - q), > 0 while the neuron stays refractory beyond the next step: its new word is 1 + nmt
+//   t  = W0 E1 + JE               E1 (J - V0)
+//   U  = t dl - W0                V - 1 = V0 + (J - V0) em - 1
 //   spk = clamp(U * 2^100)        1 if V > 1, else 0 (a positive U is at least 2^-53: it is the rounded difference of a
 //                                 product >= 2^-6 and a W0 next to it)
-//   nu = clamp(K tau_ref + K tau_rc ln(1 - u)), u = U / Jm1      K (tau_ref + t_spike - dt) of a spiking neuron, inside [0, 1]
-//                                 because dt <= tau_ref.  A neuron that crosses the threshold in this step has
-//                                 0 <= u <= 1 - exp(-dt / tau_rc) <= 0.049 (the overshoot V - 1 is at most (J - 1) (1 - exp(-delta / tau_rc))),
-//                                 and there ln(1 - u) = u phi(u) with phi = ln(1 - u) / u replaced by its quadratic interpolant through
-//                                 three Chebyshev nodes of [0, u_max]: within 5e-8 of ln(1 - u) - what v_log_f32 of the ROUNDED 1 - u
-//                                 gives as well - for three packed FMAs instead of an FMA and two transcendentals per neuron pair
-//                                 (round 4: 40 -> 20 transcendentals per wave and timestep).  A silent neuron feeds rcp whatever
-//                                 its operand is (0, negative: inf, NaN); the clamp turns any of it into a number in [0, 1]
-//                                 (DX10 clamp: NaN -> 0), spk = 0 discards it
+//   rc = rcp(JE);  u' = U rc      u / E1.  A neuron that crosses the threshold in this step has 0 <= u <= E1 (the overshoot V - 1 is
+//                                 at most (J - 1) em).  A silent neuron feeds rcp whatever its operand is (0, negative: inf, NaN);
+//                                 the clamp below turns any of it into a number in [0, 1] (DX10 clamp: NaN -> 0), spk = 0 discards it
+//   nu = clamp(A - B u')          kappa (C1 (1 - u) - q) of a spiking neuron: inside [0, A], A <= 1, because tau_ref >= dt
 //   Wn = clamp(spk * 2^100 - U)   1 - Vn: voltage of a silent neuron clamped at min_voltage 0, Vn = 0 for a spiking one
 //   w' = (Wn + nmt) + spk * nu    (spiking: Wn = 1, nmt = 0; silent: spk = 0 - exact selects, products with 0 / 1)
-// Requires dt / tau_rc <= 1/20 and tau_ref >= dt (checked by the host planner).
-struct LifConstV3 { float na, ca, m1, c1, c2, c3, p0, p1, p2, ktau_ref, K; };      // p: K tau_rc phi(u) ~ p0 + p1 u + p2 u^2
+// Requires dt / tau_rc <= 1/20, tau_ref >= dt and kappa >= 4 (checked by the host planner, lif_affine_kappa: a smaller kappa -
+// a refractory period of many steps - leaves g - q too few bits; such models run the per-timestep kernel).
+struct LifConstA { float q, nqm1, E1, A, nB, na, c, kq, rkq, tau_rc, rtau_rc; };      // kq = kappa q (prologue), rkq = 1 / (kappa q) (epilogue)
 // The same constants as the time loop reads them: every one as a pair of equal halves, the operand form of the packed
 // instructions.  (Scalar fields, splat at each use, come out of the optimizer as overlapping two-word loads of neighbouring
 // fields, which keep the whole structure in scratch memory once the loop reads it at more places.)
-struct LifConstV3P { f32x2 na, ca, m1, c1, c2, c3, p0, p1, p2, ktau_ref; };
+struct LifConstAP { f32x2 q, nqm1, E1, A, nB, na, c; };
 
-// K, the constants of dl / nmt and the coefficients of P for dl in units of dt (uniform; evaluated once per launch, in double)
-__device__ inline LifConstV3 lif_const_v3(double dt, double tau_rc, double tau_ref) {
-  double K = 1.0;
-  while (2.0 * K * tau_ref <= 1.0 && K < 1048576.0) K *= 2.0;
-  while (K * tau_ref > 1.0) K *= 0.5;
-  const double h = dt / tau_rc;
-  const double x0 = h, x1 = 0.5 * h, x2 = 0.0669872981077807 * h;
-  auto f = [](double x) { return -expm1(-x) / x; };
-  const double f0 = f(x0), f1 = f(x1), f2 = f(x2);
-  // Newton form of the interpolant, expanded to monomials
-  const double d01 = (f1 - f0) / (x1 - x0), d12 = (f2 - f1) / (x2 - x1), d012 = (d12 - d01) / (x2 - x0);
-  const double q2 = d012, q1 = d01 - d012 * (x0 + x1), q0 = f0 - d01 * x0 + d012 * x0 * x1;
-  LifConstV3 c;
-  const float a = (float)(1.0 / (K * dt));
+// (uniform; evaluated once per launch, in double; kappa: lif_affine_kappa, ssn_launch.hpp - the planner reads it too)
+__device__ inline LifConstA lif_const_affine(double dt, double tau_rc, double tau_ref) {
+  const double h = dt / tau_rc, q = exp(-h), E1 = -expm1(-h), C1 = exp((tau_ref - dt) / tau_rc);
+  const double kappa = lif_affine_kappa(dt, tau_rc, tau_ref);
+  LifConstA c;
+  const float a = (float)(1.0 / (kappa * E1));
   float ca = a + 1.0f;
   if ((double)ca < (double)a + 1.0) ca = __builtin_bit_cast(float, __builtin_bit_cast(unsigned int, ca) + 1u);      // next float up: c - a >= 1 in exact arithmetic, a full step is 1, never 1 - ulp
-  c.na = -a; c.ca = ca; c.m1 = (float)(1.0 + K * dt);
-  c.c1 = (float)(q0 * h); c.c2 = (float)(q1 * h * h); c.c3 = (float)(q2 * h * h * h);       // x = dl * h
-  {
-    // phi(u) = ln(1 - u) / u on [0, u_max], u_max = 1 - exp(-h): interpolant through the Chebyshev nodes, times K tau_rc
-    const double um = -expm1(-h);
-    const double u0 = um * 0.9330127018922193, u1 = um * 0.5, u2 = um * 0.0669872981077807;
-    auto phi = [](double u) { return log1p(-u) / u; };
-    const double g0 = phi(u0), g1 = phi(u1), g2 = phi(u2);
-    const double e01 = (g1 - g0) / (u1 - u0), e12 = (g2 - g1) / (u2 - u1), e012 = (e12 - e01) / (u2 - u0);
-    const double r2 = e012, r1 = e01 - e012 * (u0 + u1), r0 = g0 - e01 * u0 + e012 * u0 * u1;
-    c.p0 = (float)(K * tau_rc * r0); c.p1 = (float)(K * tau_rc * r1); c.p2 = (float)(K * tau_rc * r2);
-  }
-  c.ktau_ref = (float)(K * tau_ref); c.K = (float)K;
+  c.na = -a; c.c = ca;
+  c.q = (float)q; c.nqm1 = (float)(-q * (1.0 + kappa * E1)); c.E1 = (float)E1;
+  c.A = (float)(kappa * (C1 - q)); c.nB = (float)(-kappa * C1 * E1);
+  c.kq = (float)(kappa * q); c.rkq = (float)(1.0 / (kappa * q)); c.tau_rc = (float)tau_rc; c.rtau_rc = (float)(1.0 / tau_rc);
   return c;
 }
 
@@ -198,43 +168,33 @@ __device__ inline LifConstV3 lif_const_v3(double dt, double tau_rc, double tau_r
 __device__ inline f32x2 lif_state_dl(f32x2 w, f32x2 na, f32x2 ca) {
   return pk_fma_clamp01_vsv(w, (f32x2)(na), (f32x2)(ca));                   // clamp(c - a w)
 }
-// (uniform coefficients as scalar-register pairs: one constant-bus operand per instruction, the first FMA's second
-//  coefficient lives in a vector register pair)
-__device__ inline f32x2 lif_state_p1(f32x2 dl, f32x2 c3, f32x2 c2) {
-  f32x2 P;
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(dl), "v"((f32x2)(c3)), "s"((f32x2)(c2)));
-  return P;
+__device__ inline f32x2 lif_state_nmt(f32x2 w, f32x2 q, f32x2 nqm1) {
+  return pk_fma_clamp01_vsv(w, (f32x2)(q), (f32x2)(nqm1));                  // clamp(q w - q m1)
 }
-__device__ inline f32x2 lif_state_p2(f32x2 dl, f32x2 P, f32x2 c1) {
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(dl), "v"(P), "s"((f32x2)(c1)));
-  return P;
-}
-__device__ inline void lif_state_part(f32x2 w, const LifConstV3P& c, f32x2& W0, f32x2& em) {
+__device__ inline void lif_state_part(f32x2 w, const LifConstAP& c, f32x2& W0, f32x2& dl) {
   W0 = pk_clamp01(w);
-  const f32x2 dl = lif_state_dl(w, c.na, c.ca);
-  const f32x2 P = lif_state_p2(dl, lif_state_p1(dl, c.c3, c.c2), c.c1);
-  em = dl * P;
+  dl = lif_state_dl(w, c.na, c.c);
 }
 // The input half in three pieces, so that a wave whose neurons are all silent in a timestep can leave out the spike-time
-// arithmetic (round 4): lif_spike_test produces U = V - 1, the spike indicators and the stay-refractory term; lif_finish_spiking
+// arithmetic (round 4): lif_spike_test produces U = V - 1 and the spike indicators; lif_finish_spiking
 // is the rest of lif_input_part; lif_finish_silent is what that rest computes when every indicator is 0 - bit for bit:
 // Wn = clamp(0 * 2^100 - U) = clamp(-U), w' = fma(0, nu, Wn + nmt) = Wn + nmt (nu is a number in [0, 1] after its clamp, so
 // 0 * nu = +0, and Wn + nmt >= 0).
-__device__ inline f32x2 lif_spike_test(f32x2 Jm1, f32x2 w, f32x2 W0, f32x2 em, const LifConstV3P& c, f32x2 big, f32x2& U, f32x2& nmt) {
-  nmt = pk_sub_clamp01(w, (f32x2)(c.m1));                                    // clamp(w - 1 - K dt)
-  U = __builtin_elementwise_fma(Jm1 + W0, em, -W0);
+__device__ inline f32x2 lif_spike_test(f32x2 JE, f32x2 W0, f32x2 dl, const LifConstAP& c, f32x2 big, f32x2& U) {
+  const f32x2 t = __builtin_elementwise_fma(W0, c.E1, JE);
+  U = __builtin_elementwise_fma(t, dl, -W0);
   return pk_mul_clamp01(U, big);
 }
-__device__ inline void lif_finish_spiking(f32x2 Jm1, f32x2& w, f32x2 U, f32x2 nmt, f32x2 spk, const LifConstV3P& c, f32x2 big) {
+__device__ inline void lif_finish_spiking(f32x2 JE, f32x2& w, f32x2 U, f32x2 nmt, f32x2 spk, const LifConstAP& c, f32x2 big) {
   f32x2 rc;
-  rc.x = __builtin_amdgcn_rcpf(Jm1.x);
-  rc.y = __builtin_amdgcn_rcpf(Jm1.y);
-  const f32x2 u = U * rc;                                                    // (V - 1) / (J - 1)
-  f32x2 P, nu;
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(u), "v"((f32x2)(c.p2)), "s"((f32x2)(c.p1)));
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(u), "v"(P), "s"((f32x2)(c.p0)));
-  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(nu) : "v"(u), "v"(P), "s"((f32x2)(c.ktau_ref)));
-  const f32x2 Wn = pk_fma_clamp01_vs_negv(spk, big, U);
+  rc.x = __builtin_amdgcn_rcpf(JE.x);
+  rc.y = __builtin_amdgcn_rcpf(JE.y);
+  f32x2 Wn, u, nu;
+  asm("v_pk_fma_f32 %0, %2, %3, %4 neg_lo:[0,0,1] neg_hi:[0,0,1] clamp\n\t"
+      "v_pk_mul_f32 %1, %4, %5"
+      : "=&v"(Wn), "=v"(u)
+      : "v"(spk), "s"(big), "v"(U), "v"(rc));
+  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(nu) : "v"(u), "s"((f32x2)(c.nB)), "v"((f32x2)(c.A)));
   w = __builtin_elementwise_fma(spk, nu, Wn + nmt);
 }
 __device__ inline void lif_finish_silent(f32x2& w, f32x2 U, f32x2 nmt) {
@@ -242,31 +202,24 @@ __device__ inline void lif_finish_silent(f32x2& w, f32x2 U, f32x2 nmt) {
   asm("v_pk_mul_f32 %0, %1, -1.0 op_sel_hi:[1,0] clamp" : "=v"(Wn) : "v"(U));          // clamp(-U)
   w = Wn + nmt;
 }
-__device__ inline f32x2 lif_input_part(f32x2 Jm1, f32x2& w, f32x2 W0, f32x2 em, const LifConstV3P& c, f32x2 big) {
-  const f32x2 nmt = pk_sub_clamp01(w, (f32x2)(c.m1));                        // clamp(w - 1 - K dt)
-  const f32x2 U = __builtin_elementwise_fma(Jm1 + W0, em, -W0);
-  const f32x2 spk = pk_mul_clamp01(U, big);
-  f32x2 rc;
-  rc.x = __builtin_amdgcn_rcpf(Jm1.x);
-  rc.y = __builtin_amdgcn_rcpf(Jm1.y);
+// (nmt: lif_state_nmt of the word, here or - hoisted groups of the pipelined tail - one timestep ahead)
+__device__ inline f32x2 lif_input_part(f32x2 JE, f32x2& w, f32x2 W0, f32x2 dl, f32x2 nmt, const LifConstAP& c, f32x2 big) {
+  f32x2 U;
+  const f32x2 spk = lif_spike_test(JE, W0, dl, c, big, U);
   // Wn = clamp(spk * 2^100 - U) sits between the reciprocals and their first reader: the wait state a non-transcendental reader
   // of a transcendental's result needs is filled by an instruction that has to be issued anyway (the compiler's hazard recognizer
-  // does not look inside inline asm, so the order is fixed by ONE asm statement: Wn, then u = U * rc)
-  // nu = clamp(K tau_ref + u (p0 + u (p1 + u p2))): the spike time without v_log (see the table above)
-  f32x2 Wn, u, P, nu;
-  asm("v_pk_fma_f32 %0, %2, %3, %4 neg_lo:[0,0,1] neg_hi:[0,0,1] clamp\n\t"
-      "v_pk_mul_f32 %1, %4, %5"
-      : "=&v"(Wn), "=v"(u)
-      : "v"(spk), "s"(big), "v"(U), "v"(rc));
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(u), "v"((f32x2)(c.p2)), "s"((f32x2)(c.p1)));
-  asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(P) : "v"(u), "v"(P), "s"((f32x2)(c.p0)));
-  asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(nu) : "v"(u), "v"(P), "s"((f32x2)(c.ktau_ref)));
-  w = __builtin_elementwise_fma(spk, nu, Wn + nmt);
+  // does not look inside inline asm, so the order is fixed by ONE asm statement: Wn, then u' = U * rc)
+  lif_finish_spiking(JE, w, U, nmt, spk, c, big);
   return spk;
 }
-// HBM state word (s >= 0: voltage; s < 0: -(R - dt)) <-> loop word
-__device__ inline float lif_word_in(float s, float K) { return __builtin_fmaf(-s, s < 0.0f ? K : 1.0f, 1.0f); }
-__device__ inline float lif_word_out(float w, float K) { return (1.0f - w) * (w > 1.0f ? 1.0f / K : 1.0f); }
+// HBM state word (s >= 0: voltage; s < 0: -(R - dt)) <-> loop word, in the forms that keep relative accuracy as R - dt -> 0:
+// kappa (g - q) = kappa q expm1(rho / tau_rc), rho = tau_rc log1p((w - 1) / (kappa q)) - never exp / log of a number next to 1
+__device__ inline float lif_word_in(float s, float kq, float rtau_rc) {
+  return s < 0.0f ? __builtin_fmaf(kq, expm1f(-s * rtau_rc), 1.0f) : 1.0f - s;
+}
+__device__ inline float lif_word_out(float w, float rkq, float tau_rc) {
+  return w > 1.0f ? -(tau_rc * log1pf((w - 1.0f) * rkq)) : 1.0f - w;
+}
 
 __device__ inline float bits_f(unsigned int x) { return __builtin_bit_cast(float, x); }
 __device__ inline unsigned int f_bits(float x) { return __builtin_bit_cast(unsigned int, x); }
@@ -308,13 +261,17 @@ inline hipError_t read_block_stamps(unsigned long long* out, int reset) {
 // The f32 time loop's tail, pipelined (variants with five or more neuron groups; 0 restores the plain loop):
 //   SSN_BLOCK_PIPE     the next timestep's input row is read from LDS in front of the wave reduction and x of timestep jj + 1 is
 //                      assembled at the end of timestep jj, so that no LDS round trip sits between the totals and the first encode FMA
-//   SSN_BLOCK_HOIST_A  neuron groups whose lif_state_part of timestep jj + 1 runs between the publication of the wave sums and the barrier
+//   SSN_BLOCK_HOIST_A  neuron groups whose state half of timestep jj + 1 runs between the publication of the wave sums and the barrier
 //   SSN_BLOCK_HOIST_B  ... between the LDS read of the wave sums and the wait for it
-//   SSN_BLOCK_HOIST_C  ... (0 or 2) instruction by instruction between the four DPP steps of the row sum, in their wait states
-// A hoisted group costs four registers from the tail to its round of the next timestep; block_hoist() cuts the three
-// counts to what the variant's register budget (512 / waves per SIMD) leaves.  Measured at (512, 20, LDS), ms per bench step
-// against 2.98 - 3.00 for the plain loop (profiles/block_tail_placements.txt): A 2, B 4, C 2 2.79 - 2.81; A 0 2.90 - 2.96 and
-// A 4 2.84 - 2.99 whatever B is; C 0 2.86 - 3.00.  Outputs are bit for bit those of the plain loop for every setting.
+//   SSN_BLOCK_HOIST_D  ... between the filter update and the v_readlane that reads it
+//   SSN_BLOCK_HOIST_NMT  1: the state half is W0, dl and the stay-refractory term nmt (three packed operations, six registers from
+//                      the tail to the group's round of the next timestep); 0: W0 and dl only (two operations, four registers)
+// block_hoist() cuts the counts to what the variant's register budget (512 / waves per SIMD) leaves.  Outputs are bit for bit
+// those of the plain loop for every setting.  Measured at (512, 20, LDS), ms per bench step (profiles/lif_affine_placements.txt):
+// nothing hoisted 2.57 - 2.58; D 1, A 2, B 4 2.52 - 2.53, with nmt 2.51; D 0 2.56 - 2.58, D 2 2.60 - 2.62; B 2 or 6 2.54 - 2.55.
+// (The five-operation state half of the polynomial step also ran two groups instruction by instruction between the four DPP steps
+// of the row sum - profiles/block_tail_placements.txt; rewritten for W0 / dl of four groups it measured 2.53 - 2.55 against
+// 2.52 - 2.53 without: removed.)
 #ifndef SSN_BLOCK_PIPE
 #define SSN_BLOCK_PIPE 1
 #endif
@@ -324,18 +281,21 @@ inline hipError_t read_block_stamps(unsigned long long* out, int reset) {
 #ifndef SSN_BLOCK_HOIST_B
 #define SSN_BLOCK_HOIST_B 4
 #endif
-#ifndef SSN_BLOCK_HOIST_C
-#define SSN_BLOCK_HOIST_C 2
+#ifndef SSN_BLOCK_HOIST_D
+#define SSN_BLOCK_HOIST_D 1
 #endif
-struct BlockHoist { int a, b, c; };
+#ifndef SSN_BLOCK_HOIST_NMT
+#define SSN_BLOCK_HOIST_NMT 1
+#endif
+struct BlockHoist { int a, b, d; };
 constexpr BlockHoist block_hoist(bool pipe, int tpb, int ng) {
   if (!pipe || SSN_BLOCK_SKIP != 0) return {0, 0, 0};
   const int room = tpb <= 512 && ng >= 10 ? ng : 0;         // only two waves per SIMD at ten groups have registers to spare: 768 threads
                                                             // spill, (512, 10) would drop from three waves per SIMD to two
-  const int c = SSN_BLOCK_HOIST_C >= 2 && room >= 2 ? 2 : 0;      // (a pair or nothing: two instructions fill a DPP step's wait states)
-  int b = SSN_BLOCK_HOIST_B < room - c ? SSN_BLOCK_HOIST_B : room - c;
-  int a_ = SSN_BLOCK_HOIST_A < room - c - b ? SSN_BLOCK_HOIST_A : room - c - b;
-  return {a_, b, c};
+  const int d = SSN_BLOCK_HOIST_D < room ? SSN_BLOCK_HOIST_D : room;
+  const int b = SSN_BLOCK_HOIST_B < room - d ? SSN_BLOCK_HOIST_B : room - d;
+  const int a_ = SSN_BLOCK_HOIST_A < room - d - b ? SSN_BLOCK_HOIST_A : room - d - b;
+  return {a_, b, d};
 }
 
 // Neurons are dealt to threads in groups of PK adjacent neurons (PK = 2 for f32: one 64-bit register pair,
@@ -373,7 +333,8 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
   constexpr bool PIPE = F32 && NG >= 5 && SSN_BLOCK_PIPE != 0;     // (variants with one to three groups keep the plain loop: their
                                                                    //  1024-thread workgroups have no register to spare for the row)
   constexpr BlockHoist HO = block_hoist(PIPE, TPB, NG);
-  constexpr int HC = HO.c, HA = HO.a, HB = HO.b, HT = HC + HA + HB;      // hoisted groups: [0, HC) | [HC, HC + HA) | [HC + HA, HT)
+  constexpr int HD = HO.d, HA = HO.a, HB = HO.b, HT = HD + HA + HB;      // hoisted groups: [0, HD) | [HD, HD + HA) | [HD + HA, HT)
+  constexpr bool HNMT = SSN_BLOCK_HOIST_NMT != 0;                        // the hoisted groups carry their nmt along
   using G = typename std::conditional<F32, f32x2, T>::type;   // one group of neurons
   constexpr int DP = DOUT <= 4 ? 4 : 8;
   // split ensembles: P consecutive workgroups are the members of ensemble k (f32, DOUT <= 4 only - the planner sees to it)
@@ -401,11 +362,10 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
   // (uniform values: readfirstlane moves them to scalar registers, where the packed instructions of the time loop can take
   //  them as their one constant-bus operand)
   auto uni = [](float v) { return bits_f(__builtin_amdgcn_readfirstlane(f_bits(v))); };
-  const LifConstV3 lc0 = lif_const_v3((double)np.dt, (double)np.tau_rc, (double)np.tau_ref);
+  const LifConstA lc0 = lif_const_affine((double)np.dt, (double)np.tau_rc, (double)np.tau_ref);
   auto uni2 = [&](float v) { const float u = uni(v); return (f32x2){u, u}; };
-  const LifConstV3P lc = {uni2(lc0.na), uni2(lc0.ca), uni2(lc0.m1), uni2(lc0.c1), uni2(lc0.c2), uni2(lc0.c3), uni2(lc0.p0), uni2(lc0.p1),
-                          uni2(lc0.p2), uni2(lc0.ktau_ref)};
-  const float lcK = uni(lc0.K);
+  const LifConstAP lc = {uni2(lc0.q), uni2(lc0.nqm1), uni2(lc0.E1), uni2(lc0.A), uni2(lc0.nB), uni2(lc0.na), uni2(lc0.c)};
+  const float lcE1 = uni(lc0.E1), lcKq = uni(lc0.kq), lcRkq = uni(lc0.rkq), lcTau = uni(lc0.tau_rc), lcRtau = uni(lc0.rtau_rc);
   const f32x2 big = {0x1p100f, 0x1p100f};
 
   // ---- parameters and state of this thread's neurons -> registers ---------------------------------------------
@@ -435,14 +395,15 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
     auto ld = [&](const T* p) -> G { if constexpr (F32) return *reinterpret_cast<const f32x2*>(p) * msk; else return *p * msk; };
 #pragma unroll
     for (int d = 0; d < DIN; ++d) {
-      const G ev = ld(enc + d * row + ii);
+      G ev = ld(enc + d * row + ii);
+      if constexpr (F32) ev = ev * lcE1;                   // the encode FMAs produce JE = E1 (J - 1)
       if constexpr (ENC_LDS) *reinterpret_cast<G*>(e_lds + d * cap + i0) = ev; else e[g][d] = ev;
     }
     b[g] = ld(bias + ii);
     s[g] = ld(Sp + ii);
-    if constexpr (F32) {                                   // the time loop's forms: J - 1, distance to the threshold (lif_state_part / lif_input_part)
-      b[g] = b[g] - 1.0f;
-      s[g] = (f32x2){lif_word_in(s[g].x, lcK), lif_word_in(s[g].y, lcK)};
+    if constexpr (F32) {                                   // the time loop's forms: E1 (J - 1), distance to the threshold (lif_state_part / lif_input_part)
+      b[g] = (b[g] - 1.0f) * lcE1;
+      s[g] = (f32x2){lif_word_in(s[g].x, lcKq, lcRtau), lif_word_in(s[g].y, lcKq, lcRtau)};
     }
     if (a.dec_neuron_major) {
       const T* dp = a.dec + ((size_t)k * row + noff + ii) * DP;
@@ -546,12 +507,16 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
       x[d] = __builtin_fmaf(xa[d], st, xin[d]);                 // (xa = 0 where no state feeds the input)
     }
   };
-  // pipelined tail: the state half (W0, em) of the hoisted groups' NEXT step, computed in the waits of the cross-wave sum
+  // pipelined tail: the state half (W0, dl) of the hoisted groups' NEXT step, computed in the waits of the cross-wave sum
   // (the state word is final when a group's round ends; after the last timestep of the launch the values are dropped)
-  f32x2 W0h[HT > 0 ? HT : 1], emh[HT > 0 ? HT : 1];
+  f32x2 W0h[HT > 0 ? HT : 1], dlh[HT > 0 ? HT : 1], nmth[HT > 0 ? HT : 1];
+  auto hoist_state = [&](int g) {
+    lif_state_part(s[g], lc, W0h[g], dlh[g]);
+    if constexpr (HNMT) nmth[g] = lif_state_nmt(s[g], lc.q, lc.nqm1);
+  };
   if constexpr (HT > 0) {
 #pragma unroll
-    for (int g = 0; g < HT; ++g) lif_state_part(s[g], lc, W0h[g], emh[g]);
+    for (int g = 0; g < HT; ++g) hoist_state(g);
   }
   for (int j0 = 0; j0 < a.B; j0 += CH) {
     const int cn = min(CH, a.B - j0);
@@ -648,7 +613,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           for (int u = 0; u < IL; ++u) {
             if (g0 + u >= NG) continue;
             f32x2 pj;
-            asm("v_pk_add_f32 %0, %1, 1.0 op_sel_hi:[1,0] clamp" : "=v"(pj) : "v"(J[u]));      // clamp(J): J[] holds J - 1
+            asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(pj) : "v"(J[u]), "s"(lc.E1));      // clamp(E1 J): J[] holds E1 (J - 1)
             const f32x2 q = s[g0 + u] - 1.0f;
             r2 += __builtin_elementwise_fma(q, q, pj);
           }
@@ -662,9 +627,10 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
 #pragma unroll
           for (int u = 0; u < IL; ++u) {
             const int g = g0 + u < NG ? g0 + u : NG - 1;
-            f32x2 W0, em;
-            lif_state_part(s[g], lc, W0, em);
-            spk[u] = lif_spike_test(J[u], s[g], W0, em, lc, big, Uu[u], nm[u]);
+            f32x2 W0, dl;
+            lif_state_part(s[g], lc, W0, dl);
+            nm[u] = lif_state_nmt(s[g], lc.q, lc.nqm1);
+            spk[u] = lif_spike_test(J[u], W0, dl, lc, big, Uu[u]);
             if (g0 + u < NG) any2 += spk[u];
           }
           if (__builtin_amdgcn_ballot_w64(any2.x + any2.y != 0.0f) != 0ull) {
@@ -694,10 +660,12 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           if constexpr (F32 && SSN_BLOCK_SKIP == 1) {
             // (stepped above)
           } else if constexpr (F32) {
-            f32x2 W0, em;
-            if (g < HT) { W0 = W0h[g < HT ? g : 0]; em = emh[g < HT ? g : 0]; }      // (computed in the tail of the timestep before)
-            else lif_state_part(s[g], lc, W0, em);
-            spk[u] = lif_input_part(J[u], s[g], W0, em, lc, big);
+            f32x2 W0, dl, nmt;
+            if (g < HT) { W0 = W0h[g < HT ? g : 0]; dl = dlh[g < HT ? g : 0]; }      // (computed in the tail of the timestep before)
+            else lif_state_part(s[g], lc, W0, dl);
+            if (HNMT && g < HT) nmt = nmth[g < HT ? g : 0];
+            else nmt = lif_state_nmt(s[g], lc.q, lc.nqm1);
+            spk[u] = lif_input_part(J[u], s[g], W0, dl, nmt, lc, big);
           } else {
             // packed state word -> nengo's LIF step, operation for operation k_ensarray's fast path
             const T sw = s[g];
@@ -793,7 +761,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           // hoisted state halves, first place: behind the publication, in front of the barrier (delays the wave's arrival: few)
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int g = HC; g < HC + HA; ++g) lif_state_part(s[g], lc, W0h[g], emh[g]);
+          for (int g = HD; g < HD + HA; ++g) hoist_state(g);
           __builtin_amdgcn_sched_barrier(0);
         }
         SSN_BSTAMP(bt3);
@@ -807,36 +775,10 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
             // second place: between the LDS read of the wave sums and the wait for it - both waves of a SIMD fill it together
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = HC + HA; g < HT; ++g) lif_state_part(s[g], lc, W0h[g], emh[g]);
+            for (int g = HD + HA; g < HT; ++g) hoist_state(g);
             __builtin_amdgcn_sched_barrier(0);
           }
-          // row r of every wave: total of decoded row r.  Third place: row_sum_dpp's four steps with the state halves of groups 0 and
-          // 1 between them, instruction by instruction - a DPP step may read its operand two wait states after the add before it
-          // wrote it, and two independent packed instructions are exactly that.  ONE asm statement: the compiler's hazard recognizer
-          // does not count the instructions of an asm statement as wait states (it would add its s_nop 1 to them), and its
-          // scheduler moves non-volatile asm statements across scheduling barriers.  Same operations as row_sum_dpp
-          // (v + dpp(v), all lanes valid) and lif_state_part.
-          if constexpr (HC == 2) {
-            f32x2 dl0, dl1, P0, P1;
-            v0 = rv;
-            asm volatile(
-                "v_pk_fma_f32 %1, %7, %9, %10 clamp\n\t"          // (first: whatever wrote v0 in front of the statement is two wait states away too)
-                "v_pk_fma_f32 %2, %8, %9, %10 clamp\n\t"
-                "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                "v_pk_fma_f32 %3, %1, %11, %12\n\t"
-                "v_pk_fma_f32 %4, %2, %11, %12\n\t"
-                "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                "v_pk_fma_f32 %3, %1, %3, %13\n\t"
-                "v_pk_fma_f32 %4, %2, %4, %13\n\t"
-                "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                "v_pk_mul_f32 %5, %1, %3\n\t"
-                "v_pk_mul_f32 %6, %2, %4\n\t"
-                "v_add_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                : "+v"(v0), "=&v"(dl0), "=&v"(dl1), "=&v"(P0), "=&v"(P1), "=&v"(emh[0]), "=&v"(emh[1])
-                : "v"(s[0]), "v"(s[1]), "s"(lc.na), "v"(lc.ca), "v"(lc.c3), "s"(lc.c2), "s"(lc.c1));
-          } else {
-            v0 = row_sum_dpp(rv);
-          }
+          v0 = row_sum_dpp(rv);                                    // row r of every wave: total of decoded row r
           if constexpr (DOUT > 4) v1 = rv1;
         } else {
           v0 = row_sum_dpp(red[par][lane]);                        // row r of every wave: total of decoded row r
@@ -871,11 +813,11 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
           }
         }
         F0 = __builtin_fmaf(la0, F0, lb0 * v0);                    // rows without a filter: la = lb = 0
-        if constexpr (HC > 0) {
-          // (the last instruction of the HC groups' state halves: between the filter update and the v_readlane that reads it)
+        if constexpr (HD > 0) {
+          // third place: between the filter update and the v_readlane that reads it
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int g = 0; g < HC; ++g) W0h[g] = pk_clamp01(s[g]);
+          for (int g = 0; g < HD; ++g) hoist_state(g);
           __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (DOUT > 4) {
@@ -953,7 +895,7 @@ __global__ __launch_bounds__(TPB) void k_ens_block(BlockArgs<T> a) {   // SPLIT:
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     const int i0 = (g * nthr + tid2) * PK;
-    if constexpr (F32) s[g] = (f32x2){lif_word_out(s[g].x, lcK), lif_word_out(s[g].y, lcK)};
+    if constexpr (F32) s[g] = (f32x2){lif_word_out(s[g].x, lcRkq, lcTau), lif_word_out(s[g].y, lcRkq, lcTau)};
     if (i0 < n_loc) *reinterpret_cast<G*>(Sp + i0) = s[g];         // (padding elements of the row are never read back)
   }
   if constexpr (TAP != 0) {

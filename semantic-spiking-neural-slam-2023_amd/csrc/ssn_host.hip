@@ -1469,7 +1469,7 @@ struct Sim final : ssn_sim {
       if (split_P > 1) n_member = (int)(((n_ens + split_P - 1) / split_P + 3) / 4 * 4);
     }
     // (a driven array is not eligible: k_ens_block has no drive columns)
-    if (defer && !drv && !opt.has(SSN_PLAN_NO_BLOCK_KERNEL) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt)) &&
+    if (defer && !drv && !opt.has(SSN_PLAN_NO_BLOCK_KERNEL) && ens_fast(eo) && (sizeof(T) == 8 || (dt <= 0.05 * eo.f[0] && eo.f[1] >= dt && ssn::lif_affine_kappa((double)(T)dt, (double)(T)eo.f[0], (double)(T)eo.f[1]) >= 4.0)) &&
         ssn::ens_block_supported<T>((int)din, (int)dout, split_P > 1 ? n_member : (int)eo.i[2], opt.block_variant.v, &blk_threads, &blk_tpb, &blk_npt, &blk_lds)) {
       FilterTabs ft;
       CHK(filter_tables(ft, true));

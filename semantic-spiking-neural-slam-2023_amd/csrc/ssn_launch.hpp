@@ -334,6 +334,14 @@ template <typename T> hipError_t launch_ens_finish(hipStream_t, const FinishArgs
 template <typename T> hipError_t launch_dft(hipStream_t, const DftBatch&, int count);   // (T only selects the translation unit)
 template <typename T> hipError_t launch_ens_block(hipStream_t, const BlockArgs<T>&);
 template <typename T> bool ens_block_supported(int din, int dout, int n, const int want[3], int* threads, int* tpb, int* npt, int* enc_lds);
+// Scale of the f32 whole-block kernel's refractory word (ssn_block.hpp): the largest power of two with kappa (C1 - q) <= 1,
+// C1 = exp((tau_ref - dt) / tau_rc), q = exp(-dt / tau_rc).  Kernel and planner: the planner admits the kernel at kappa >= 4.
+__host__ __device__ inline double lif_affine_kappa(double dt, double tau_rc, double tau_ref) {
+  const double span = exp((tau_ref - dt) / tau_rc) - exp(-dt / tau_rc);
+  double kappa = 1048576.0;
+  while (kappa * span > 1.0 && kappa > 0x1p-20) kappa *= 0.5;
+  return kappa;
+}
 template <typename T> hipError_t launch_program(hipStream_t, const MicroOp<T>* ops, const ProgDesc* progs, int n_progs, T* sig, StepCtx* ctx);
 template <typename T> hipError_t launch_vecops(hipStream_t, const MicroOp<T>* ops, int n_ops, int wgs, T* sig, const StepCtx* ctx);
 template <typename T> hipError_t launch_matvec(hipStream_t, const MatvecBatch<T>&, int count);

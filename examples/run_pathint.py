@@ -17,6 +17,11 @@ the sample times ``ts``.
 ``--gate-oscillators T0 T1`` inhibits every oscillator for T0 < t <= T1 through ``oscillators.add_neuron_input()`` (a
 weight of -10 on every neuron, the gate of the reference's ``AdditiveInputGatedMemory``; at the oscillators' default
 rates of up to 400 Hz that thins their spikes out, it does not silence every neuron).
+
+``--save-maps N`` makes the similarity maps every figure script of the reference ends with (``sim_grid`` of
+``run_pathint_gif.py:231-232``: every 10th probed sample against the N x N sample grid, squared, raw rows) through
+``harness.similarity_frames`` - NumPy, or ``k_decode_map`` on the GPU with ``--decode-backend hip`` - prints the map seconds next to
+the decode seconds and, with ``--save``, writes them to ``<result file minus .npz>_maps.npz`` (``ts``, ``sim_grid``).
 """
 import argparse
 import os
@@ -67,6 +72,9 @@ def parse(argv=None):
                         "encode seconds")
     p.add_argument("--decode-refine", action="store_true",
                    help="also decode with 'grid-refine' (Newton steps from the grid point) and print both position errors")
+    p.add_argument("--save-maps", default=0, type=int, metavar="N",
+                   help="similarity maps of every 10th probed sample over the N x ... x N sample grid (sim_grid of "
+                        "run_pathint_gif.py: squared, raw rows), made by --decode-backend; with --save written to <result>_maps.npz")
     return p.parse_args(argv)
 
 
@@ -126,6 +134,14 @@ def main(argv=None):
         t0 = time.time()
     est, sims, err = H.pathint_metrics(space, out, real_ssp, path[:n], backend=args.decode_backend, table=table)
     decode_time = time.time() - t0
+    sim_grid = None
+    if args.save_maps > 0:
+        t0 = time.time()
+        map_ts = ts[9::10]
+        sim_grid = np.moveaxis(H.similarity_frames(space, out[9::10], args.save_maps, power=2, backend=args.decode_backend, table=table), 0, -1)
+        print("similarity maps: %d samples over %s samples, %.1f MB: maps %.2f s (%s), decode %.2f s" % (
+            sim_grid.shape[-1], " x ".join(["%d" % args.save_maps] * domain_dim), sim_grid.nbytes / 1e6, time.time() - t0,
+            args.decode_backend, decode_time))
     print("d = %d, %d VCOs x %d neurons, T = %.1f s: build %.1f s, run %.2f s (%.1f sim-s/wall-s), decode %.2f s (%s); similarity "
           "to the true SSP mean %.4f, final position error %.4f" % (space.ssp_dim, (space.ssp_dim + 1) // 2, args.pi_n_neurons, T,
                                                                    build_time, elapsed_time, T / elapsed_time, decode_time,
@@ -142,6 +158,10 @@ def main(argv=None):
         H.save_pathint_results(os.path.join(args.save_dir, name), space, ts, path, pm.real_ssp, out, elapsed_time, args=args,
                                elapsed_thread_time=elapsed_thread_time)
         print("saved", os.path.join(args.save_dir, name))
+        if sim_grid is not None:
+            maps_name = name[:-len(".npz")] + "_maps.npz"
+            np.savez(os.path.join(args.save_dir, maps_name), ts=map_ts, sim_grid=sim_grid)
+            print("saved", os.path.join(args.save_dir, maps_name))
         if spikes:
             spike_name = name[:-len(".npz")] + "_spikes.npz"
             np.savez(os.path.join(args.save_dir, spike_name), ts=spike_ts, **{"vco_n%d" % k: v for k, v in spikes.items()})

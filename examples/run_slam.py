@@ -9,7 +9,11 @@ population for each landmark's semantic pointer times the final PES decoders, de
 ``--save``, writes the result file with the reference's field names.  With ``--decode-backend hip`` the final map is recalled on
 the GPU from the learned state (``sim.recall``: the Voja-learned encoders, as ``slam_map_new.py:342-347`` does) and neither matrix
 is read back.  ``--map-every SECONDS`` also watches the map being learned: a ``MapProbe`` on the landmark SPs, decoded to positions
-(``landmark_loc_over_time`` in the result file, the frames of ``run_slam_map_gif.py``).
+(``landmark_loc_over_time`` in the result file, the frames of ``run_slam_map_gif.py``).  ``--save-maps N`` adds that script's
+similarity maps over the N x N sample grid at every map sample (``harness.similarity_frames``; ``k_decode_map`` on the GPU with
+``--decode-backend hip``): ``sim_grid`` of the probed trajectory (squared, raw rows) and ``landmark_sim_grid`` of the recalled
+frames (normalised, squared; a landmark not seen yet gives a zero map where the reference's ``q / norm`` gives NaN), written with
+``--save`` to ``<result file minus .npz>_maps.npz``; the map seconds are printed next to the decode seconds.
 """
 import argparse
 import os
@@ -60,12 +64,18 @@ def parse(argv=None):
                    help="also decode with 'grid-refine' (Newton steps from the grid point) and print both sets of errors")
     p.add_argument("--map-every", default=0.0, type=float, metavar="SECONDS",
                    help="recall the landmark map on the GPU every SECONDS of simulated time (a MapProbe) and decode it to positions")
+    p.add_argument("--save-maps", default=0, type=int, metavar="N",
+                   help="with --map-every: similarity maps over the N x ... x N sample grid at every map sample - sim_grid of the "
+                        "probed trajectory (squared, raw rows) and landmark_sim_grid of the MapProbe frames (normalised, squared), "
+                        "made by --decode-backend; with --save written to <result>_maps.npz")
     return p.parse_args(argv)
 
 
 def main(argv=None):
     args = parse(argv)
     dt = 0.001
+    if args.save_maps > 0 and not args.map_every > 0:
+        raise SystemExit("--save-maps needs --map-every: the maps are made at the map samples")
     if args.path_data is None:
         T = args.T
         path, vels = H.make_random_path(T, dt=dt, limit=args.limit, seed=args.seed, domain_dim=args.domain_dim)
@@ -115,7 +125,7 @@ def main(argv=None):
     else:
         lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend)
     decode_time = time.time() - t0
-    lm_over_time = None
+    lm_over_time = sim_grid = landmark_sim_grid = None
     if frames is not None:
         t0 = time.time()
         lm_over_time = H.map_over_time(space, frames, backend=None if args.decode_backend == "numpy" else args.decode_backend, table=table)
@@ -124,6 +134,17 @@ def main(argv=None):
                                                         time.time() - t0, args.decode_backend,
                                                         float(np.median(np.linalg.norm(lm_over_time[0] - sm.obj_locs, axis=1))) if len(frames) else np.nan,
                                                         float(np.median(np.linalg.norm(lm_over_time[-1] - sm.obj_locs, axis=1))) if len(frames) else np.nan))
+        if args.save_maps > 0:
+            # sim_grid of run_slam_map_gif.py:316-317 at the map samples, and q_sims of :366-368 for every landmark of every frame.  A
+            # landmark not seen yet recalls a near-zero row: it stays as it is and its map is zero (the reference's q / norm is NaN)
+            t1 = time.time()
+            backend = None if args.decode_backend == "numpy" else args.decode_backend
+            rows = out[np.searchsorted(ts, map_ts - 0.5 * dt)]
+            sim_grid = np.moveaxis(H.similarity_frames(space, rows, args.save_maps, power=2, backend=backend, table=table), 0, -1)
+            landmark_sim_grid = H.similarity_frames(space, frames, args.save_maps, power=2, normalize=True, backend=backend, table=table)
+            print("similarity maps: %d path and %d x %d landmark maps over %s samples, %.1f MB: maps %.2f s (%s), decode %.2f s" % (
+                rows.shape[0], frames.shape[0], frames.shape[1], " x ".join(["%d" % args.save_maps] * space.domain_dim),
+                (sim_grid.nbytes + landmark_sim_grid.nbytes) / 1e6, time.time() - t1, args.decode_backend, t1 - t0))
     elif recall_time:
         print("map recall: final map on the GPU in %.4f s (kernels %.2f ms)" % (recall_time, recall_kernel_ms))
     lm_err = np.linalg.norm(lm_locs - sm.obj_locs, axis=1)
@@ -150,6 +171,10 @@ def main(argv=None):
         H.save_slam_results(os.path.join(args.save_dir, name), space, ts, path, sm.real_ssp, sm.obj_locs, args.view_rad, out,
                             lm_ssps, lm_locs, elapsed, args=args, landmark_loc_over_time=lm_over_time, landmark_loc_over_time_ts=map_ts)
         print("saved", os.path.join(args.save_dir, name))
+        if sim_grid is not None:
+            maps_name = name[:-len(".npz")] + "_maps.npz"
+            np.savez(os.path.join(args.save_dir, maps_name), ts=map_ts, sim_grid=sim_grid, landmark_sim_grid=landmark_sim_grid)
+            print("saved", os.path.join(args.save_dir, maps_name))
     return out, lm_locs
 
 

@@ -417,6 +417,29 @@ int ssn_decoder_refine_rows(ssn_decoder* dec, const double* rows, int64_t n_rows
 int ssn_decoder_refine_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows,
                                    int32_t iterations, double* x, int32_t* best, double* f, int32_t* status);
 
+/* Similarity maps (additive to ABI 11; k_decode_map in csrc/ssn_decode.hip): the n_rows x n_samples similarities
+ * the decode compares, kept:  out[t * out_ld + j] = (sum_k row_t[k] table[j][k]) ^ (1 or 2).  flags: SSN_MAP_NORMALIZE scales every
+ * row as the decode does (otherwise the rows are used raw), SSN_MAP_SQUARE stores s * s (one multiply in the decoder's dtype).
+ * rows: n_rows x width host doubles, dense (rows_on_device == 0; rows_dtype and rows_ld are ignored), or rows on the decoder's
+ * device of rows_dtype SSN_F32 / SSN_F64 with leading dimension rows_ld >= width (elements).  out: host memory (out_on_device == 0)
+ * or memory on the decoder's device, of out_dtype = the decoder's dtype, or SSN_F64 from an f32 decoder (exact widening; SSN_F32
+ * from an f64 decoder is not offered), with leading dimension out_ld >= n_samples (elements).  Only out[t][j], t < n_rows,
+ * j < n_samples, is written - padding up to out_ld is left alone - and the map is complete when the call returns.  Every stored
+ * value is the accumulator ssn_decoder_rows compares (with SSN_MAP_NORMALIZE), so the argmax of a row, lowest index on ties, is
+ * best[t]; the bits do not depend on the scratch or stage size, on where rows and output live, or on the run.
+ * A device output is written in place.  A host output goes through a device stage and pinned host memory of the same size, made on
+ * first use: ssn_decoder_set_map_stage sets that size (0 = the default: 64 MB, or one 128-row tile of doubles, 1024 n_samples
+ * bytes, when that is more); rows per chunk are the whole tiles that fit both the row scratch and the stage, never n_rows x
+ * n_samples.  The copy back of a chunk is not overlapped with the kernels of the next.  ssn_decoder_get_info reports
+ * last_launches / last_kernel_ms of a map call (prepare + k_decode_map of every chunk) as of a decode call.
+ * SSN_EINVAL: null handle or argument, unknown flags or dtype, rows_ld below the width, out_ld below n_samples, an out_dtype
+ * narrower than the decoder's, a stage below one tile (128 n_samples elements of the decoder's dtype in ssn_decoder_set_map_stage, of
+ * out_dtype in ssn_decoder_map); n_rows == 0 succeeds and writes nothing. */
+enum { SSN_MAP_NORMALIZE = 1, SSN_MAP_SQUARE = 2 };
+int ssn_decoder_map(ssn_decoder* dec, const void* rows, int32_t rows_on_device, int32_t rows_dtype, int64_t rows_ld, int64_t n_rows,
+                    int32_t flags, void* out, int32_t out_on_device, int32_t out_dtype, int64_t out_ld);
+int ssn_decoder_set_map_stage(ssn_decoder* dec, int64_t bytes /* 0 = default */);
+
 /* SSP encoding of points on the device (additive to ABI 11; csrc/ssn_encode.hip): SSPSpace.encode as a phase
  * kernel and one product.  With K bins, M (K x dim: phase_matrix / length_scale of the bins used) and w (K) - what
  * SSPSpace.refine_tables() returns, host doubles, C order - and th_k = M_k . x,

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("SSN_HIP_LIB") or os.path.join(_HERE, "libssn_hip.so")
 
 SSN_ABI_VERSION = 11
 SSN_F32, SSN_F64 = 0, 1
+SSN_MAP_NORMALIZE, SSN_MAP_SQUARE = 1, 2          # flags of ssn_decoder_map
 SSN_BUF_REAL, SSN_BUF_I32, SSN_BUF_TAPS, SSN_BUF_DRIVES = 0, 1, 2, 3
 NEURON_CODE = {"lif": 0, "lifrate": 1, "relu": 2}
 OP_CODE = {"fill": 1, "table": 2, "axpy": 3, "matvec": 4, "lowpass": 5, "ensarray": 6, "neurons": 7,
@@ -150,6 +151,9 @@ EXPORTS = {
     "ssn_decoder_refine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssn_decoder_refine_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    "ssn_decoder_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32,
+                                  C.c_int32, C.c_int64]),
+    "ssn_decoder_set_map_stage": (C.c_int, [C.c_void_p, C.c_int64]),
     "ssn_encoder_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.POINTER(C.c_void_p)]),
     "ssn_encoder_destroy": (None, [C.c_void_p]),

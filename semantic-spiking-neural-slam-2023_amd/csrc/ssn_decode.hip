@@ -26,6 +26,16 @@
 //                      occupancy 1.  One k step of a wave is 4 LDS reads for 4 MFMAs (f64: 8 for 16).
 //   k_decode_finish    one wave per row: the partials of its strips in column order, same rule -> int32 best; the similarity to
 //                      that sample accumulated again in f64.
+//   k_decode_map       the storing twin of k_decode_tiles behind ssn_decoder_map: the same tile walk, and after each
+//                      tile's K loop the tile itself - s, or s * s - is stored at out[(t0 + r) out_ld + col] for rows < n_rows and
+//                      columns < S, in T or widened to double.  No running best, no LDS reduction, no strips, no finish kernel.
+//                      tools/kernel_resources.py ssn_decode.hip k_decode_map:  f32 250 VGPR (64 accumulator, 32 prefetch, the rest
+//                      hoisted store addresses), 0 AGPR, no scratch, LDS 33 792 B, occupancy 2;  f64 254 VGPR + 140 AGPR, LDS
+//                      34 816 B, occupancy 1.  Store form: plain dword stores, an accumulator register of a wave being 32
+//                      consecutive columns of two rows (two 128-B segments); with a device output the kernel costs what
+//                      k_decode_tiles + k_decode_finish cost on the same rows (0.49 against 0.52 ms at 2 000 x 1015 over 100 x 100,
+//                      3.7 against 4.1 ms at 20 000 rows), so the LDS-transposed 16-byte store was not built: it had no time left to
+//                      recover.  k_decode_prepare<.., SCALE = false> feeds it the raw rows of normalize=False.
 //
 // Scratch (fixed at creation, default 64 MB): per row K doubles of upload staging, Kp converted values, one (value, column)
 // partial per strip slot and the (double similarity, best) result.  The host cuts n_rows into chunks of whole row tiles that fit and the
@@ -40,6 +50,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <memory>
 #include <vector>
 #include "../../include/ssn.h"
@@ -76,7 +87,8 @@ __device__ __forceinline__ void take_better(T& bv, int& bc, T v, int c) {
   if (v > bv || (v == bv && c < bc)) { bv = v; bc = c; }
 }
 
-template <typename TI, typename T>
+// SCALE = false (the raw rows of a map with normalize off) leaves out the norm: the rows are only converted and padded
+template <typename TI, typename T, bool SCALE = true>
 __global__ __launch_bounds__(256) void k_decode_prepare(const TI* __restrict__ src, long long ld, int n_rows, int n_pad_rows, int K, int Kp,
                                                         T* __restrict__ dst) {
   const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -87,12 +99,16 @@ __global__ __launch_bounds__(256) void k_decode_prepare(const TI* __restrict__ s
     return;
   }
   const TI* s = src + (size_t)row * ld;
-  double ss = 0.0;
-  for (int k = lane; k < K; k += 64) { const double x = (double)s[k]; ss += x * x; }
+  double nrm = 1.0;
+  bool scale = false;
+  if constexpr (SCALE) {
+    double ss = 0.0;
+    for (int k = lane; k < K; k += 64) { const double x = (double)s[k]; ss += x * x; }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-  const double nrm = sqrt(ss);
-  const bool scale = nrm >= 1e-6;
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    nrm = sqrt(ss);
+    scale = nrm >= 1e-6;
+  }
   for (int k = lane; k < Kp; k += 64) {
     double x = 0.0;
     if (k < K) { x = (double)s[k]; if (scale) x = x / nrm; }
@@ -204,6 +220,88 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 1) void k_decode_tiles(co
     take_better(v, c, red_v[1][tid], red_c[1][tid]);
     pval[(size_t)blockIdx.y * part_ld + t0 + tid] = v;
     pcol[(size_t)blockIdx.y * part_ld + t0 + tid] = c;
+  }
+}
+
+// The storing twin of k_decode_tiles (ssn_decoder_map): the same tile walk - operands, Kp padding, slab order and MFMA sequence - so
+// every s below is the accumulator value k_decode_tiles compares, but no running best, no reduction and no finish kernel: a
+// workgroup owns (row tile, the tiles_per_run column tiles from blockIdx.y tiles_per_run) and after each tile's K loop stores
+// s (square: s * s, one multiply in T) converted to TO at out[(t0 + r) out_ld + col].  Only rows < n_rows and columns < S are
+// written, with plain stores: in the 32x32x2 layout an accumulator register is 32 consecutive columns of two rows, so one store
+// instruction of a wave is two full 128-B segments (f64: four rows of 16 doubles).
+template <typename T, typename TO>
+__global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 1) void k_decode_map(const T* __restrict__ rows, const T* __restrict__ table, int Kp, int n_rows, unsigned S,
+                                                      int col_tiles, int tiles_per_run, int square, TO* __restrict__ out, long long out_ld) {
+  using M = Mma<T>;
+  constexpr int BK = M::BK, LD = BK + 1, MT = M::MT, NI = 64 / MT, AR = M::AR, KS = M::KS;
+  constexpr int RS = 256 / BK, RPT = TILE / RS;
+  __shared__ T As[TILE][LD];
+  __shared__ T Ws[TILE][LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int t0 = blockIdx.x * TILE;
+  const int ct0 = blockIdx.y * tiles_per_run, ct1 = min(ct0 + tiles_per_run, col_tiles);
+  const int lr = tid / BK, lc = tid % BK;
+  const T* __restrict__ a0 = rows + (size_t)t0 * Kp;
+  const unsigned voff = (unsigned)lr * (unsigned)Kp + (unsigned)lc;
+  T ra[RPT], rw[RPT];
+  auto fetch = [&](int ct, int k0) {
+    const T* a = a0 + k0;
+    const T* w = table + (size_t)ct * TILE * Kp + k0;
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+      const unsigned o = (unsigned)(RS * i) * (unsigned)Kp;
+      ra[i] = (a + o)[voff];
+      rw[i] = (w + o)[voff];
+    }
+  };
+  const int mn = M::lane_mn(lane);
+  const T* ap = &As[wm * 64 + mn][M::lane_k(lane)];
+  const T* wp = &Ws[wn * 64 + mn][M::lane_k(lane)];
+  fetch(ct0, 0);
+  for (int ct = ct0; ct < ct1; ++ct) {
+    typename M::acc_t acc[NI][NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NI; ++j)
+#pragma unroll
+        for (int v = 0; v < AR; ++v) acc[i][j][v] = T(0);
+    for (int k0 = 0; k0 < Kp; k0 += BK) {
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) { As[lr + RS * i][lc] = ra[i]; Ws[lr + RS * i][lc] = rw[i]; }
+      __syncthreads();
+      if (k0 + BK < Kp) fetch(ct, k0 + BK);
+      else if (ct + 1 < ct1) fetch(ct + 1, 0);
+#pragma unroll 4
+      for (int kk = 0; kk < BK; kk += KS) {
+        T a[NI], b[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) { a[i] = ap[i * MT * LD + kk]; b[i] = wp[i * MT * LD + kk]; }
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int j = 0; j < NI; ++j) acc[i][j] = M::mma(a[i], b[j], acc[i][j]);
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const unsigned col = (unsigned)ct * TILE + wn * 64 + j * MT + mn;
+      if (col < S) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int v = 0; v < AR; ++v) {
+            const int r = t0 + wm * 64 + i * MT + M::acc_row(v, lane);
+            if (r < n_rows) {
+              T s = acc[i][j][v];
+              if (square) s = s * s;
+              out[(size_t)r * (size_t)out_ld + col] = (TO)s;
+            }
+          }
+      }
+    }
   }
 }
 
@@ -472,6 +570,18 @@ struct ssn_decoder {
   void *r_dft = nullptr, *r_M = nullptr;      // (2 r_K x Kp) table with w folded in, (r_K x r_dim) phases, both in the decoder's dtype
   double *r_points = nullptr, *r_box = nullptr;      // (S x r_dim) sample points; lo, hi, pitch (r_dim each)
   char* r_work = nullptr;          // per row: 2 r_K spectrum values, r_dim + 1 doubles (x, f), one status word
+  // staging of host map outputs (ssn_decoder_map): a device area and pinned host memory of the same size, made on first use
+  int64_t m_stage_bytes = 0, m_alloc = 0;      // asked for (0 = default_map_stage()); allocated
+  char *m_dev = nullptr, *m_pin = nullptr;
+
+  void drop_map_stage() {
+    if (m_dev) (void)hipFree(m_dev);
+    if (m_pin) (void)hipHostFree(m_pin);
+    m_dev = m_pin = nullptr;
+    m_alloc = 0;
+  }
+  int64_t min_map_stage(size_t out_esz) const { return TILE * S * (int64_t)out_esz; }      // one row tile of the map
+  int64_t default_map_stage() const { return std::max<int64_t>((int64_t)64 << 20, min_map_stage(8)); }
 
   void drop_refine() {
     for (void* p : {r_dft, r_M, (void*)r_points, (void*)r_box, (void*)r_work}) if (p) (void)hipFree(p);
@@ -517,6 +627,7 @@ struct ssn_decoder {
     if (e1) (void)hipEventDestroy(e1);
     if (stream) (void)hipStreamDestroy(stream);
     drop_refine();
+    drop_map_stage();
     if (table) (void)hipFree(table);
     if (scratch) (void)hipFree(scratch);
   }
@@ -557,9 +668,9 @@ struct Areas {      // the regions of the scratch area for a chunk capacity of `
   }
 };
 
-template <typename T, typename TI>
+template <typename T, typename TI, bool SCALE = true>
 hipError_t launch_prepare(ssn_decoder* d, const TI* src, int64_t ld, int n, int n_pad, T* conv) {
-  hipLaunchKernelGGL((k_decode_prepare<TI, T>), dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, d->stream, src, (long long)ld, n, n_pad, (int)d->K,
+  hipLaunchKernelGGL((k_decode_prepare<TI, T, SCALE>), dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, d->stream, src, (long long)ld, n, n_pad, (int)d->K,
                      (int)d->Kp, conv);
   return hipGetLastError();
 }
@@ -656,8 +767,82 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
   return SSN_OK;
 }
 
+// The similarity map of ssn_decoder_map.  Rows as decode_rows takes them.  A device output is written in place by the kernel; a host
+// output goes chunk by chunk through the device stage (dense, leading dimension S) and the pinned area, and from there row by row
+// into `out`.  Rows per chunk: whole tiles that fit the row scratch (upload staging + converted rows) and, for a host output, the
+// stage - never n_rows x S.  Column tiles are cut into runs as decode_plan cuts strips, without the slot limit (nothing is kept per
+// run).  Every tile is computed alone, so neither cut shows in the result.  Single-buffered: the copy back of a chunk is not
+// overlapped with the next chunk's kernels.
+template <typename T, typename TO>
+int map_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t n_rows, int flags, TO* out, bool out_on_device,
+             int64_t out_ld) {
+  DevGuard g(d->device);
+  const int64_t S = d->S, t_tiles = (n_rows + TILE - 1) / TILE;
+  int64_t cap = std::min<int64_t>(d->scratch_bytes / (TILE * d->row_bytes(0)), (1 << 24) / TILE);      // >= 1: min_scratch() is larger
+  if (!out_on_device) {
+    const int64_t want = d->m_stage_bytes ? d->m_stage_bytes : d->default_map_stage();
+    if (want < d->min_map_stage(sizeof(TO)))
+      return fail(SSN_EINVAL, "ssn_decoder_map: map stage of %lld bytes too small for one %d-row tile of %lld samples (%lld bytes)", (long long)want, TILE,
+                  (long long)S, (long long)d->min_map_stage(sizeof(TO)));
+    if (d->m_alloc != want) {
+      d->drop_map_stage();
+      DHIP(hipMalloc((void**)&d->m_dev, (size_t)want));
+      if (hipHostMalloc((void**)&d->m_pin, (size_t)want, hipHostMallocDefault) != hipSuccess) { d->drop_map_stage(); return fail(SSN_ENOMEM, "ssn_decoder_map: hipHostMalloc of %lld bytes", (long long)want); }
+      d->m_alloc = want;
+    }
+    cap = std::min<int64_t>(cap, want / d->min_map_stage(sizeof(TO)));
+  }
+  const int64_t n_chunks = (t_tiles + cap - 1) / cap, chunk_tiles = (t_tiles + n_chunks - 1) / n_chunks, cap_rows = chunk_tiles * TILE;
+  // runs of column tiles: the length that wastes the least of the launch's rounds of resident workgroups (shortest on ties)
+  const int64_t resident = 2 * (int64_t)d->n_cu, max_runs = std::min<int64_t>(d->col_tiles, 4096);
+  int64_t tpr = 0;
+  double best_cost = 0.0;
+  for (int64_t t = (d->col_tiles + max_runs - 1) / max_runs; t <= d->col_tiles; ++t) {
+    const int64_t runs = (d->col_tiles + t - 1) / t, rounds = (chunk_tiles * runs + resident - 1) / resident;
+    const double cost = (double)rounds * (double)t;
+    if (!tpr || cost < best_cost) { best_cost = cost; tpr = t; }
+    if (rounds == 1) break;
+  }
+  const int64_t n_runs = (d->col_tiles + tpr - 1) / tpr;
+  const Areas<T> a(d, cap_rows, 0);
+  const bool scale = flags & SSN_MAP_NORMALIZE;
+  const int square = flags & SSN_MAP_SQUARE ? 1 : 0;
+  d->kernel_ms = 0.0;
+  d->launches = 0;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += cap_rows) {
+    const int n = (int)std::min(cap_rows, n_rows - r0), n_pad = (n + TILE - 1) / TILE * TILE;
+    if (host) DHIP(hipMemcpyAsync(a.stage, host + (size_t)r0 * d->K, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
+    DHIP(hipEventRecord(d->e0, d->stream));
+    if (host) DHIP(scale ? (launch_prepare<T, double, true>(d, a.stage, d->K, n, n_pad, a.conv)) : (launch_prepare<T, double, false>(d, a.stage, d->K, n, n_pad, a.conv)));
+    else if (rows_dtype == SSN_F32) {
+      const float* src = (const float*)dev + (size_t)r0 * ld;
+      DHIP(scale ? (launch_prepare<T, float, true>(d, src, ld, n, n_pad, a.conv)) : (launch_prepare<T, float, false>(d, src, ld, n, n_pad, a.conv)));
+    } else {
+      const double* src = (const double*)dev + (size_t)r0 * ld;
+      DHIP(scale ? (launch_prepare<T, double, true>(d, src, ld, n, n_pad, a.conv)) : (launch_prepare<T, double, false>(d, src, ld, n, n_pad, a.conv)));
+    }
+    TO* dst = out_on_device ? out + (size_t)r0 * out_ld : (TO*)d->m_dev;
+    hipLaunchKernelGGL((k_decode_map<T, TO>), dim3((unsigned)(n_pad / TILE), (unsigned)n_runs), dim3(256), 0, d->stream, (const T*)a.conv, (const T*)d->table,
+                       (int)d->Kp, n, (unsigned)S, (int)d->col_tiles, (int)tpr, square, dst, (long long)(out_on_device ? out_ld : S));
+    DHIP(hipGetLastError());
+    DHIP(hipEventRecord(d->e1, d->stream));
+    if (!out_on_device) DHIP(hipMemcpyAsync(d->m_pin, d->m_dev, (size_t)n * S * sizeof(TO), hipMemcpyDeviceToHost, d->stream));
+    DHIP(hipStreamSynchronize(d->stream));
+    if (!out_on_device) {
+      const TO* src = (const TO*)d->m_pin;
+      if (out_ld == S) memcpy(out + (size_t)r0 * S, src, (size_t)n * S * sizeof(TO));
+      else for (int64_t r = 0; r < n; ++r) memcpy(out + (size_t)(r0 + r) * out_ld, src + (size_t)r * S, (size_t)S * sizeof(TO));
+    }
+    float ms = 0.0f;
+    DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
+    d->kernel_ms += ms;
+    d->launches += 2;
+  }
+  return SSN_OK;
+}
+
 template <typename T>
-int upload_refine(ssn_decoder* d, const double* dft, const double* M, const double* w, const double* points, const double* lo, const double* hi,
+int upload_refine(ssn_decoder* d,const double* dft, const double* M, const double* w, const double* points, const double* lo, const double* hi,
                   const double* pitch) {
   const int64_t K = d->r_K, Kp = d->Kp, width = d->K, dim = d->r_dim;
   std::vector<T> tab((size_t)2 * K * Kp, T(0)), m((size_t)K * dim);
@@ -861,6 +1046,38 @@ int ssn_decoder_rows_composed(ssn_decoder* dec, const double* rows, int64_t n_ro
   if (!dec || !rows || !best || n_rows <= 0) return fail(SSN_EINVAL, "ssn_decoder_rows_composed: null or empty argument");
   if (dec->dtype != SSN_F32) return fail(SSN_EUNSUPPORTED, "ssn_decoder_rows_composed: f32 decoders only (k_gemm_nt_mfma_f32)");
   return decode_rows_composed(dec, rows, n_rows, best);
+}
+
+int ssn_decoder_map(ssn_decoder* dec, const void* rows, int32_t rows_on_device, int32_t rows_dtype, int64_t rows_ld, int64_t n_rows, int32_t flags,
+                    void* out, int32_t out_on_device, int32_t out_dtype, int64_t out_ld) {
+  if (!dec) return fail(SSN_EINVAL, "ssn_decoder_map: null decoder");
+  if (n_rows < 0) return fail(SSN_EINVAL, "ssn_decoder_map: negative n_rows");
+  if (flags & ~(SSN_MAP_NORMALIZE | SSN_MAP_SQUARE)) return fail(SSN_EINVAL, "ssn_decoder_map: unknown flags 0x%x", flags);
+  if (rows_on_device && rows_dtype != SSN_F32 && rows_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_map: unknown rows_dtype %d", rows_dtype);
+  if (rows_on_device && rows_ld < dec->K)
+    return fail(SSN_EINVAL, "ssn_decoder_map: leading dimension %lld of the rows below the width %lld", (long long)rows_ld, (long long)dec->K);
+  if (out_dtype != SSN_F32 && out_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_map: unknown out_dtype %d", out_dtype);
+  if (out_dtype == SSN_F32 && dec->dtype == SSN_F64)
+    return fail(SSN_EINVAL, "ssn_decoder_map: out_dtype f32 is narrower than the f64 decoder's (narrowing is not offered)");
+  if (out_ld < dec->S) return fail(SSN_EINVAL, "ssn_decoder_map: leading dimension %lld of the output below n_samples %lld", (long long)out_ld, (long long)dec->S);
+  if (n_rows == 0) return SSN_OK;
+  if (!rows || !out) return fail(SSN_EINVAL, "ssn_decoder_map: null argument");
+  const double* host = rows_on_device ? nullptr : (const double*)rows;
+  const void* dev = rows_on_device ? rows : nullptr;
+  const int64_t ld = rows_on_device ? rows_ld : dec->K;
+  if (dec->dtype == SSN_F64) return map_rows<double, double>(dec, host, dev, rows_dtype, ld, n_rows, flags, (double*)out, out_on_device != 0, out_ld);
+  return out_dtype == SSN_F32 ? map_rows<float, float>(dec, host, dev, rows_dtype, ld, n_rows, flags, (float*)out, out_on_device != 0, out_ld)
+                              : map_rows<float, double>(dec, host, dev, rows_dtype, ld, n_rows, flags, (double*)out, out_on_device != 0, out_ld);
+}
+
+int ssn_decoder_set_map_stage(ssn_decoder* dec, int64_t bytes) {
+  if (!dec) return fail(SSN_EINVAL, "ssn_decoder_set_map_stage: null decoder");
+  if (bytes < 0) return fail(SSN_EINVAL, "ssn_decoder_set_map_stage: negative size");
+  if (bytes && bytes < dec->min_map_stage(dec->esz))
+    return fail(SSN_EINVAL, "ssn_decoder_set_map_stage: %lld bytes too small for one %d-row tile of %lld samples (%lld bytes)", (long long)bytes, TILE,
+                (long long)dec->S, (long long)dec->min_map_stage(dec->esz));
+  dec->m_stage_bytes = bytes;      // the areas are made again, at this size, by the next host-output map
+  return SSN_OK;
 }
 
 int ssn_decoder_get_info(ssn_decoder* dec, int64_t n_rows, ssn_decoder_info* out) {

@@ -9,7 +9,10 @@ similarity matrix never exists.  There is no CPU fallback: without a GPU the con
     with GridDecoder(space, 100) as dec:
         est = dec.decode(sim.data[probe])              # == space.decode(sim.data[probe], 'from-set', 'grid', 100)
 
-``SSPSpace.decode(..., backend="hip")`` does the same through a decoder cached on the space.
+``SSPSpace.decode(..., backend="hip")`` does the same through a decoder cached on the space.  Where the similarities themselves are
+wanted - the maps the reference's figure scripts draw - ``GridDecoder.similarity`` keeps them (``k_decode_map``):
+
+        sims = dec.similarity(sim.data[probe], power=2)    # == (sim.data[probe] @ sample_ssps.T) ** 2, (T, n_samples)
 """
 import ctypes as C
 
@@ -188,6 +191,60 @@ class GridDecoder:
             self._check(self._lib.ssn_decoder_rows(self._h, rows.ctypes.data, n, best.ctypes.data, sims_p))
         best = best.astype(np.int64)
         return (best, sims) if return_sims else best
+
+    def set_map_stage(self, nbytes=0):
+        """Size of the device + pinned staging of host maps (0: the default, 64 MB or one tile of doubles); at least one 128-row
+        tile, ``128 * n_samples`` values.  Never changes a result."""
+        if self.closed:
+            raise fe.SimulationError("the decoder is closed")
+        self._check(self._lib.ssn_decoder_set_map_stage(self._h, int(nbytes)))
+
+    def similarity(self, rows, power=1, normalize=False, out="host", out_dtype=None, into=None):
+        """The ``(T, n_samples)`` similarity map ``(rows @ table.T) ** power`` (``k_decode_map``): the values
+        ``indices`` compares, kept.  ``rows`` as ``indices`` takes them; ``normalize=True`` scales them as ``decode`` does (a row of
+        norm below 1e-6 stays as it is), the default uses them raw like the reference's figure scripts.  ``power``: 1 or 2 (the
+        square is one multiply in the decoder's dtype).  ``out="host"`` returns float64 NumPy (``out_dtype="f32"``: float32, from an
+        f32 decoder - half the copy); ``out="device"`` a torch tensor in the decoder's dtype; ``into=`` a caller's 2-D device tensor
+        of that dtype, ``(T, n_samples)`` with unit column stride and any row stride >= n_samples, written in place (nothing outside
+        ``[:T, :n_samples]`` is touched) and returned.  With ``normalize=True, power=1`` the argmax of a row is ``indices(rows)``."""
+        if self.closed:
+            raise fe.SimulationError("the decoder is closed")
+        if power not in (1, 2) or isinstance(power, bool):
+            raise ValueError(f"power must be 1 or 2, got {power!r}")
+        if out not in ("host", "device"):
+            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+        if out_dtype not in (None, "f32", "f64"):
+            raise ValueError(f"out_dtype must be None, 'f32' or 'f64', got {out_dtype!r}")
+        if out_dtype == "f32" and self.dtype == "f64":
+            raise ValueError("out_dtype='f32' from an f64 decoder is not offered: the map is never narrowed")
+        if (out == "device" or into is not None) and out_dtype not in (None, self.dtype):
+            raise ValueError(f"a device map has the decoder's dtype {self.dtype!r}, not out_dtype={out_dtype!r}")
+        rows, n, dev = self._rows_arg(rows)
+        flags = (_lib.SSN_MAP_NORMALIZE if normalize else 0) | (_lib.SSN_MAP_SQUARE if power == 2 else 0)
+        rows_args = (dev[0], 1, dev[1], dev[2]) if dev else (rows.ctypes.data, 0, 0, self.width)
+        code = {"f32": _lib.SSN_F32, "f64": _lib.SSN_F64}
+        if out == "host" and into is None:
+            dt = out_dtype or "f64"
+            res = np.empty((n, self.n_samples), dtype=np.float32 if dt == "f32" else np.float64)
+            self._check(self._lib.ssn_decoder_map(self._h, *rows_args, n, flags, res.ctypes.data, 0, code[dt], self.n_samples))
+            return res
+        import torch
+        tdt = torch.float32 if self.dtype == "f32" else torch.float64
+        if into is None:
+            into = torch.empty((n, self.n_samples), dtype=tdt, device=f"cuda:{self.device}")
+        else:
+            if not (hasattr(into, "is_cuda") and into.is_cuda and into.device.index == self.device):
+                raise ValueError(f"into= must be a tensor on the decoder's device {self.device}")
+            if into.dtype != tdt:
+                raise ValueError(f"into= must be {tdt}, the decoder's dtype, got {into.dtype}")
+            if into.dim() != 2 or tuple(into.shape) != (n, self.n_samples):
+                raise ValueError(f"into= must be ({n}, {self.n_samples}), got {tuple(into.shape)}")
+            if into.stride(1) != 1 or (n > 1 and into.stride(0) < self.n_samples):
+                raise ValueError(f"into= needs unit column stride and a row stride >= {self.n_samples}, got strides {tuple(into.stride())}")
+            torch.cuda.current_stream(into.device).synchronize()          # whatever filled it is complete before the decoder's stream writes
+        ld = max(int(into.stride(0)), self.n_samples) if n > 1 else self.n_samples
+        self._check(self._lib.ssn_decoder_map(self._h, *rows_args, n, flags, into.data_ptr() if n else None, 1, code[self.dtype], ld))
+        return into
 
     def _set_refine(self, trust=None):
         """Build and upload the refinement tables on first use (again when ``trust`` changes)."""

@@ -11,6 +11,7 @@ one definition of the benchmark workloads:
 * ``map_recall``            ``run_slam.py:263-268``        (definition (i): built encoders)
 * ``map_recall_learned``    ``slam_map_new.py:342-347,447-452``  (definition (ii): Voja-probed encoders)
 * ``map_over_time``         ``run_slam_map_gif.py:323-329``     (the frames of a ``MapProbe`` decoded to positions)
+* ``similarity_frames``     ``run_pathint_gif.py:231-232``, ``run_slam_map_gif.py:316-317,366-368``  (similarity maps over the sample grid)
 """
 import numpy as np
 
@@ -358,3 +359,24 @@ def map_over_time(ssp_space, frames, num_samples=100, backend=None, refine=False
         return np.zeros((s, n_keys, ssp_space.domain_dim))
     est = ssp_space.decode(frames.reshape(s * n_keys, d), "grid-refine" if refine else "from-set", "grid", num_samples, backend=backend, **_table_arg(table))
     return np.asarray(est).reshape(s, n_keys, -1)
+
+
+def similarity_frames(ssp_space, rows_or_frames, num_samples=100, power=2, normalize=False, backend=None, table="host", sampling_method="grid"):
+    """Similarity maps over the sample grid, shaped for plotting: rows ``(T, d)`` -> ``(T, n, ..., n)``, ``MapProbe`` frames
+    ``(samples, L, d)`` -> ``(samples, L, n, ..., n)``, float64.  The sample axis is reshaped in the order of
+    ``get_sample_pts_and_ssps(n, "grid")``, so ``np.moveaxis(out, 0, -1)`` of a 2-D path result is the reference's
+    ``sim_grid = (sample_ssps.reshape(n, n, -1) @ sim_ssps.T) ** 2`` (``run_pathint_gif.py:231-232``), and a frame's map with
+    ``normalize=True`` is ``q_sims`` of ``run_slam_map_gif.py:366-368`` - except that a landmark not yet seen, whose recalled row is
+    near zero, stays as it is and gives a zero map where the reference's ``q_ssp / norm`` gives NaN.  All rows go through one
+    ``SSPSpace.similarity_map`` call (``backend``: None for NumPy, "hip" / "hip-f64" for ``k_decode_map``).  Grid sampling only."""
+    if sampling_method != "grid":
+        raise ValueError(f"similarity_frames reshapes the sample axis to the grid: sampling_method must be 'grid', got {sampling_method!r}")
+    arr = np.asarray(rows_or_frames, dtype=float)
+    if arr.ndim not in (2, 3):
+        raise ValueError(f"rows must be (T, d) or frames (samples, L, d), got {arr.shape}")
+    n, dim = int(num_samples), ssp_space.domain_dim
+    lead, d = arr.shape[:-1], arr.shape[-1]
+    if int(np.prod(lead)) == 0:
+        return np.zeros(lead + (n,) * dim)
+    maps = ssp_space.similarity_map(arr.reshape(-1, d), n, "grid", power=power, normalize=normalize, backend=backend, **_table_arg(table))
+    return maps.reshape(lead + (n,) * dim)

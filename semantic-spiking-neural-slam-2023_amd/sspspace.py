@@ -433,6 +433,36 @@ class SSPSpace:
             sample_ssps, sample_points = samples
         return sample_points[self._best_samples(ssp, sample_ssps)[1]]
 
+    def similarity_map(self, ssp, num_samples=100, sampling_method="grid", samples=None, power=1, normalize=False, backend=None,
+                       table="host"):
+        """``(T, S)`` float64 similarities of every row of ``ssp`` to every sample SSP, to the ``power`` (1 or 2): the map the
+        reference's figure scripts form as ``(sample_ssps @ rows.T) ** 2`` and ``similarity_plot`` plots unsquared.  The defaults
+        are those raw products; ``normalize=True`` scales the rows as ``decode`` does (divided by the norm unless it is below
+        1e-6, so an all-zero recalled row gives a zero map where ``q / norm`` gives NaN).  ``backend=None`` is NumPy; "hip" /
+        "hip-f64" keep the similarities of the decoder cached on the space (``GridDecoder.similarity``)."""
+        from .decoding import GridDecoder, backend_dtype
+        dtype = backend_dtype(backend)
+        if power not in (1, 2) or isinstance(power, bool):
+            raise ValueError(f"power must be 1 or 2, got {power!r}")
+        if table not in ("host", "device"):
+            raise ValueError(f"table must be 'host' or 'device', got {table!r}")
+        if table == "device" and dtype is None:
+            raise ValueError("table='device' needs a hip backend: the NumPy map has no device table")
+        if dtype is not None:
+            if samples is None:
+                return self._grid_decoder(num_samples, sampling_method, dtype, table).similarity(ssp, power=power, normalize=normalize)
+            with GridDecoder(self, samples=samples, dtype=dtype, table=table) as dec:
+                return dec.similarity(ssp, power=power, normalize=normalize)
+        sample_ssps = self.get_sample_pts_and_ssps(num_samples, sampling_method)[0] if samples is None else np.asarray(samples[0], dtype=float)
+        rows = np.atleast_2d(np.asarray(ssp, dtype=float))
+        if rows.ndim != 2 or rows.shape[1] != sample_ssps.shape[1]:
+            raise ValueError(f"ssp must be (T, {sample_ssps.shape[1]}), got {rows.shape}")
+        if normalize:
+            nrm = np.linalg.norm(rows, axis=1, keepdims=True)
+            rows = np.where(nrm < 1e-6, rows, rows / np.where(nrm == 0, 1.0, nrm))          # the scaling of _best_samples
+        sims = rows @ sample_ssps.T
+        return sims ** 2 if power == 2 else sims
+
     def clean_up(self, ssp, method="from-set", sampling_method="grid", num_samples=300, backend=None, encode_backend=None, **kwargs):
         """``encode(decode(ssp))``.  ``encode_backend``: the backend of that ``encode`` (None: the host; "hip" / "hip-f64")."""
         return self.encode(self.decode(ssp, method, sampling_method, num_samples, backend=backend, **kwargs), backend=encode_backend)

@@ -26,20 +26,24 @@
 //                      occupancy 1.  One k step of a wave is 4 LDS reads for 4 MFMAs (f64: 8 for 16).
 //   k_decode_finish    one wave per row: the partials of its strips in column order, same rule -> int32 best; the similarity to
 //                      that sample accumulated again in f64.
-//   k_decode_map       the storing twin of k_decode_tiles behind ssn_decoder_map: the same tile walk, and after each
-//                      tile's K loop the tile itself - s, or s * s - is stored at out[(t0 + r) out_ld + col] for rows < n_rows and
-//                      columns < S, in T or widened to double.  No running best, no LDS reduction, no strips, no finish kernel.
+//   k_decode_map       the storing twin of k_decode_tiles behind ssn_decoder_map: the same tile walk - operands, Kp
+//                      padding, slab order and MFMA sequence, over the tiles_per_run column tiles of a run instead of a strip - so
+//                      every entry is the accumulator value k_decode_tiles compares; after each tile's K loop the tile itself - s,
+//                      or s * s (one multiply in T) - is stored at out[(t0 + r) out_ld + col] for rows < n_rows and columns < S,
+//                      in T or widened to double.  No running best, no LDS reduction, no finish kernel.
 //                      tools/kernel_resources.py ssn_decode.hip k_decode_map:  f32 250 VGPR (64 accumulator, 32 prefetch, the rest
 //                      hoisted store addresses), 0 AGPR, no scratch, LDS 33 792 B, occupancy 2;  f64 254 VGPR + 140 AGPR, LDS
 //                      34 816 B, occupancy 1.  Store form: plain dword stores, an accumulator register of a wave being 32
-//                      consecutive columns of two rows (two 128-B segments); with a device output the kernel costs what
-//                      k_decode_tiles + k_decode_finish cost on the same rows (0.49 against 0.52 ms at 2 000 x 1015 over 100 x 100,
-//                      3.7 against 4.1 ms at 20 000 rows), so the LDS-transposed 16-byte store was not built: it had no time left to
-//                      recover.  k_decode_prepare<.., SCALE = false> feeds it the raw rows of normalize=False.
+//                      consecutive columns of two rows (two 128-B segments; f64: four rows of 16 doubles); with a device output the
+//                      kernel costs what k_decode_tiles + k_decode_finish cost on the same rows (0.49 against 0.52 ms at 2 000 x
+//                      1015 over 100 x 100, 3.7 against 4.1 ms at 20 000 rows), so the LDS-transposed 16-byte store was not built:
+//                      it had no time left to recover.  k_decode_prepare<.., SCALE = false> feeds it the raw rows of normalize=False.
 //
 // Scratch (fixed at creation, default 64 MB): per row K doubles of upload staging, Kp converted values, one (value, column)
 // partial per strip slot and the (double similarity, best) result.  The host cuts n_rows into chunks of whole row tiles that fit and the
-// column walk into at most `slots` strips (decode_plan); the smallest scratch holds one row tile with one strip.
+// column walk into at most `slots` strips (ssn_decoder::plan: cut_rows, tiles_per_part); the smallest scratch holds one row tile with
+// one strip.  The error reporting, the device guard and the device check at creation are csrc/ssn_service.hpp's, shared with the
+// encoder and the recall.
 //
 // The table comes from the host (ssn_decoder_create: converted and uploaded) or is made here from the sample points
 // (ssn_decoder_create_from_points: a float64 ssn_encoder of csrc/ssn_encode.hip writes it chunk by chunk in the decoder's dtype).
@@ -48,14 +52,15 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <vector>
 #include "../../include/ssn.h"
 #include "ssn_encode.hpp"       // encoder_encode_into: the table of ssn_decoder_create_from_points
 #include "ssn_kernels.hpp"      // launch_gemm_nt / launch_argmax_partial: the materialising composition ssn_decoder_rows_composed times
+#include "ssn_service.hpp"
+
+using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, check_device
 
 namespace {
 
@@ -223,12 +228,9 @@ __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 1) void k_decode_tiles(co
   }
 }
 
-// The storing twin of k_decode_tiles (ssn_decoder_map): the same tile walk - operands, Kp padding, slab order and MFMA sequence - so
-// every s below is the accumulator value k_decode_tiles compares, but no running best, no reduction and no finish kernel: a
-// workgroup owns (row tile, the tiles_per_run column tiles from blockIdx.y tiles_per_run) and after each tile's K loop stores
-// s (square: s * s, one multiply in T) converted to TO at out[(t0 + r) out_ld + col].  Only rows < n_rows and columns < S are
-// written, with plain stores: in the 32x32x2 layout an accumulator register is 32 consecutive columns of two rows, so one store
-// instruction of a wave is two full 128-B segments (f64: four rows of 16 doubles).
+// k_decode_tiles' walk, copied up to the epilogue on purpose.  One force-inlined body for both (if constexpr on a store flag; outputs as
+// parameters or as a struct; __restrict__ kept or dropped; plain inline) compiles to the same resources, except k_decode_tiles<double>: 158
+// -> 156 AGPR.  k_decode_tiles' own text behind a force-inlined call does the same, so no shared body reproduces the registers above.
 template <typename T, typename TO>
 __global__ __launch_bounds__(256, sizeof(T) == 4 ? 2 : 1) void k_decode_map(const T* __restrict__ rows, const T* __restrict__ table, int Kp, int n_rows, unsigned S,
                                                       int col_tiles, int tiles_per_run, int square, TO* __restrict__ out, long long out_ld) {
@@ -517,40 +519,32 @@ __global__ __launch_bounds__(256) void k_decode_refine(const T* __restrict__ spe
   }
 }
 
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
-}  // namespace
-
-namespace ssn {
-int probe_fail(int code, const char* what, hipError_t e);      // ssn_host.hip: sets ssn_last_error
-}
-
-namespace {
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return ssn::probe_fail(code, buf, hipSuccess);
-}
-
-#define DHIP(expr)                                                                                      \
-  do {                                                                                                  \
-    hipError_t e__ = (expr);                                                                            \
-    if (e__ != hipSuccess) return ssn::probe_fail(e__ == hipErrorOutOfMemory ? SSN_ENOMEM : SSN_EHIP, #expr, e__); \
-  } while (0)
-
-struct DevGuard {      // the decoder's device for the duration of a call, the caller's afterwards
-  int prev = -1;
-  explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 struct Plan {
   int64_t chunk_tiles, n_chunks, slots, n_strips, tiles_per_strip;
 };
+
+// t_tiles row tiles in chunks of at most `cap`: as few chunks as that allows, of even size; returns the tiles per chunk
+int64_t cut_rows(int64_t t_tiles, int64_t cap, int64_t* n_chunks = nullptr) {
+  const int64_t n = (t_tiles + cap - 1) / cap, chunk_tiles = (t_tiles + n - 1) / n;
+  if (n_chunks) *n_chunks = (t_tiles + chunk_tiles - 1) / chunk_tiles;      // even chunks may be fewer
+  return chunk_tiles;
+}
+
+// Column tiles per part - a strip of k_decode_tiles, a run of k_decode_map.  Both kernels keep two workgroups per CU resident, and
+// a launch of chunk_tiles x parts workgroups runs in ceil(workgroups / resident) rounds of that many tiles each.  Of the lengths
+// that make at most max_parts parts, the one that wastes the least of those rounds (the shortest on ties: more, smaller workgroups
+// even out better).
+int64_t tiles_per_part(int64_t col_tiles, int64_t max_parts, int64_t chunk_tiles, int64_t resident) {
+  int64_t best = 0;
+  double best_cost = 0.0;
+  for (int64_t t = (col_tiles + max_parts - 1) / max_parts; t <= col_tiles; ++t) {
+    const int64_t parts = (col_tiles + t - 1) / t, rounds = (chunk_tiles * parts + resident - 1) / resident;
+    const double cost = (double)rounds * (double)t;
+    if (!best || cost < best_cost) { best_cost = cost; best = t; }
+    if (rounds == 1) break;      // longer parts only make the single round longer
+  }
+  return best;
+}
 
 }  // namespace
 
@@ -602,21 +596,8 @@ struct ssn_decoder {
       p.slots = (scratch_bytes / TILE - row_bytes(0)) / (int64_t)(esz + 4);
     }
     cap = std::min<int64_t>(cap, (1 << 24) / TILE);
-    p.n_chunks = (t_tiles + cap - 1) / cap;
-    p.chunk_tiles = (t_tiles + p.n_chunks - 1) / p.n_chunks;
-    p.n_chunks = (t_tiles + p.chunk_tiles - 1) / p.chunk_tiles;
-    // Strips: the kernel keeps two workgroups per CU resident, and a launch runs in ceil(workgroups / resident) rounds of
-    // tiles_per_strip tiles each.  Of the strip lengths the slots allow, take the one that wastes the least of those rounds (the
-    // shortest on ties: more, smaller workgroups even out better).
-    const int64_t resident = 2 * (int64_t)n_cu, max_strips = std::max<int64_t>(1, std::min(p.slots, col_tiles));
-    double best_cost = 0.0;
-    p.tiles_per_strip = 0;
-    for (int64_t tps = (col_tiles + max_strips - 1) / max_strips; tps <= col_tiles; ++tps) {
-      const int64_t strips = (col_tiles + tps - 1) / tps, rounds = (p.chunk_tiles * strips + resident - 1) / resident;
-      const double cost = (double)rounds * (double)tps;
-      if (!p.tiles_per_strip || cost < best_cost) { best_cost = cost; p.tiles_per_strip = tps; }
-      if (rounds == 1) break;      // longer strips only make the single round longer
-    }
+    p.chunk_tiles = cut_rows(t_tiles, cap, &p.n_chunks);
+    p.tiles_per_strip = tiles_per_part(col_tiles, std::max<int64_t>(1, std::min(p.slots, col_tiles)), p.chunk_tiles, 2 * (int64_t)n_cu);      // a slot per strip
     p.n_strips = (col_tiles + p.tiles_per_strip - 1) / p.tiles_per_strip;
     return p;
   }
@@ -638,8 +619,8 @@ namespace {
 template <typename T>
 int upload_table(ssn_decoder* d, const double* table) {
   const int64_t Sp = d->col_tiles * TILE, Kp = d->Kp, K = d->K;
-  DHIP(hipMalloc(&d->table, (size_t)Sp * Kp * sizeof(T)));
-  DHIP(hipMemset(d->table, 0, (size_t)Sp * Kp * sizeof(T)));
+  SVC_HIP(hipMalloc(&d->table, (size_t)Sp * Kp * sizeof(T)));
+  SVC_HIP(hipMemset(d->table, 0, (size_t)Sp * Kp * sizeof(T)));
   const int64_t per = std::max<int64_t>(1, (int64_t)(8 << 20) / Kp);
   std::vector<T> stage((size_t)std::min(per, d->S) * Kp, T(0));
   for (int64_t r0 = 0; r0 < d->S; r0 += per) {
@@ -649,7 +630,7 @@ int upload_table(ssn_decoder* d, const double* table) {
       T* o = stage.data() + (size_t)r * Kp;
       for (int64_t k = 0; k < K; ++k) o[k] = (T)s[k];
     }
-    DHIP(hipMemcpy((T*)d->table + (size_t)r0 * Kp, stage.data(), (size_t)n * Kp * sizeof(T), hipMemcpyHostToDevice));
+    SVC_HIP(hipMemcpy((T*)d->table + (size_t)r0 * Kp, stage.data(), (size_t)n * Kp * sizeof(T), hipMemcpyHostToDevice));
   }
   return SSN_OK;
 }
@@ -668,11 +649,25 @@ struct Areas {      // the regions of the scratch area for a chunk capacity of `
   }
 };
 
-template <typename T, typename TI, bool SCALE = true>
-hipError_t launch_prepare(ssn_decoder* d, const TI* src, int64_t ld, int n, int n_pad, T* conv) {
-  hipLaunchKernelGGL((k_decode_prepare<TI, T, SCALE>), dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, d->stream, src, (long long)ld, n, n_pad, (int)d->K,
-                     (int)d->Kp, conv);
+template <typename T, typename TI>
+hipError_t launch_prepare(ssn_decoder* d, const TI* src, int64_t ld, int n, int n_pad, T* conv, bool scale) {
+  hipLaunchKernelGGL((scale ? k_decode_prepare<TI, T, true> : k_decode_prepare<TI, T, false>), dim3((unsigned)((n_pad + 3) / 4)), dim3(256), 0, d->stream, src,
+                     (long long)ld, n, n_pad, (int)d->K, (int)d->Kp, conv);
   return hipGetLastError();
+}
+
+// The start of a chunk, rows [r0, r0 + n) of a call.  Rows: host doubles (dense, width K), copied to the staging area first, or
+// device rows of dtype rows_dtype with leading dimension ld, read where they are.  Records e0 - after the upload, so the timed span
+// holds kernels only - and launches k_decode_prepare into a.conv, scaling the rows or not.
+template <typename T>
+int prepare_chunk(ssn_decoder* d, const Areas<T>& a, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t r0, int n, int n_pad,
+                  bool scale) {
+  if (host) SVC_HIP(hipMemcpyAsync(a.stage, host + (size_t)r0 * d->K, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
+  SVC_HIP(hipEventRecord(d->e0, d->stream));
+  if (host) SVC_HIP(launch_prepare<T>(d, (const double*)a.stage, d->K, n, n_pad, a.conv, scale));
+  else if (rows_dtype == SSN_F32) SVC_HIP(launch_prepare<T>(d, (const float*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv, scale));
+  else SVC_HIP(launch_prepare<T>(d, (const double*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv, scale));
+  return SSN_OK;
 }
 
 struct RefineOut {      // host arrays of ssn_decoder_refine_rows*; f and status may be null
@@ -730,7 +725,7 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
     if (d->r_work) (void)hipFree(d->r_work);
     d->r_work = nullptr;
     d->r_rows = 0;
-    DHIP(hipMalloc((void**)&d->r_work, RefineAreas<T>::bytes(d, cap_rows)));
+    SVC_HIP(hipMalloc((void**)&d->r_work, RefineAreas<T>::bytes(d, cap_rows)));
     d->r_rows = cap_rows;
   }
   const RefineAreas<T> ra(d, ro ? d->r_rows : 0);
@@ -738,29 +733,25 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
   d->launches = 0;
   for (int64_t r0 = 0; r0 < n_rows; r0 += cap_rows) {
     const int n = (int)std::min(cap_rows, n_rows - r0), n_pad = (n + TILE - 1) / TILE * TILE;
-    if (host) DHIP(hipMemcpyAsync(a.stage, host + (size_t)r0 * d->K, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
-    DHIP(hipEventRecord(d->e0, d->stream));
-    if (host) DHIP((launch_prepare<T, double>(d, a.stage, d->K, n, n_pad, a.conv)));
-    else if (rows_dtype == SSN_F32) DHIP((launch_prepare<T, float>(d, (const float*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv)));
-    else DHIP((launch_prepare<T, double>(d, (const double*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv)));
+    if (const int rc = prepare_chunk<T>(d, a, host, dev, rows_dtype, ld, r0, n, n_pad, true)) return rc;      // decode always scales
     hipLaunchKernelGGL((k_decode_tiles<T>), dim3((unsigned)(n_pad / TILE), (unsigned)p.n_strips), dim3(256), 0, d->stream, a.conv, (const T*)d->table,
                        (int)d->Kp, n, (unsigned)d->S, (int)d->col_tiles, (int)p.tiles_per_strip, a.pval, a.pcol, (int)cap_rows);
-    DHIP(hipGetLastError());
+    SVC_HIP(hipGetLastError());
     hipLaunchKernelGGL((k_decode_finish<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, d->stream, a.pval, a.pcol, (int)cap_rows, (int)p.n_strips,
                        n, (const T*)a.conv, (const T*)d->table, (int)d->Kp, a.sims, a.best);
-    DHIP(hipGetLastError());
-    if (ro) DHIP(refine_chunk<T>(d, ra, (const T*)a.conv, a.best, n, ro->iterations));
-    DHIP(hipEventRecord(d->e1, d->stream));
-    if (best) DHIP(hipMemcpyAsync(best + r0, a.best, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
-    if (sims) DHIP(hipMemcpyAsync(sims + r0, a.sims, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+    SVC_HIP(hipGetLastError());
+    if (ro) SVC_HIP(refine_chunk<T>(d, ra, (const T*)a.conv, a.best, n, ro->iterations));
+    SVC_HIP(hipEventRecord(d->e1, d->stream));
+    if (best) SVC_HIP(hipMemcpyAsync(best + r0, a.best, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+    if (sims) SVC_HIP(hipMemcpyAsync(sims + r0, a.sims, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
     if (ro) {
-      DHIP(hipMemcpyAsync(ro->x + (size_t)r0 * d->r_dim, ra.x, (size_t)n * d->r_dim * 8, hipMemcpyDeviceToHost, d->stream));
-      if (ro->f) DHIP(hipMemcpyAsync(ro->f + r0, ra.f, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-      if (ro->status) DHIP(hipMemcpyAsync(ro->status + r0, ra.status, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+      SVC_HIP(hipMemcpyAsync(ro->x + (size_t)r0 * d->r_dim, ra.x, (size_t)n * d->r_dim * 8, hipMemcpyDeviceToHost, d->stream));
+      if (ro->f) SVC_HIP(hipMemcpyAsync(ro->f + r0, ra.f, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
+      if (ro->status) SVC_HIP(hipMemcpyAsync(ro->status + r0, ra.status, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
     }
-    DHIP(hipStreamSynchronize(d->stream));
+    SVC_HIP(hipStreamSynchronize(d->stream));
     float ms = 0.0f;
-    DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
+    SVC_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
     d->kernel_ms += ms;
     d->launches += ro ? 5 : 3;
   }
@@ -770,8 +761,8 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
 // The similarity map of ssn_decoder_map.  Rows as decode_rows takes them.  A device output is written in place by the kernel; a host
 // output goes chunk by chunk through the device stage (dense, leading dimension S) and the pinned area, and from there row by row
 // into `out`.  Rows per chunk: whole tiles that fit the row scratch (upload staging + converted rows) and, for a host output, the
-// stage - never n_rows x S.  Column tiles are cut into runs as decode_plan cuts strips, without the slot limit (nothing is kept per
-// run).  Every tile is computed alone, so neither cut shows in the result.  Single-buffered: the copy back of a chunk is not
+// stage - never n_rows x S.  Column tiles are cut into runs as ssn_decoder::plan cuts strips (tiles_per_part), without the slot limit.
+// Every tile is computed alone, so neither cut shows in the result.  Single-buffered: the copy back of a chunk is not
 // overlapped with the next chunk's kernels.
 template <typename T, typename TO>
 int map_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t n_rows, int flags, TO* out, bool out_on_device,
@@ -786,23 +777,14 @@ int map_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype
                   (long long)S, (long long)d->min_map_stage(sizeof(TO)));
     if (d->m_alloc != want) {
       d->drop_map_stage();
-      DHIP(hipMalloc((void**)&d->m_dev, (size_t)want));
+      SVC_HIP(hipMalloc((void**)&d->m_dev, (size_t)want));
       if (hipHostMalloc((void**)&d->m_pin, (size_t)want, hipHostMallocDefault) != hipSuccess) { d->drop_map_stage(); return fail(SSN_ENOMEM, "ssn_decoder_map: hipHostMalloc of %lld bytes", (long long)want); }
       d->m_alloc = want;
     }
     cap = std::min<int64_t>(cap, want / d->min_map_stage(sizeof(TO)));
   }
-  const int64_t n_chunks = (t_tiles + cap - 1) / cap, chunk_tiles = (t_tiles + n_chunks - 1) / n_chunks, cap_rows = chunk_tiles * TILE;
-  // runs of column tiles: the length that wastes the least of the launch's rounds of resident workgroups (shortest on ties)
-  const int64_t resident = 2 * (int64_t)d->n_cu, max_runs = std::min<int64_t>(d->col_tiles, 4096);
-  int64_t tpr = 0;
-  double best_cost = 0.0;
-  for (int64_t t = (d->col_tiles + max_runs - 1) / max_runs; t <= d->col_tiles; ++t) {
-    const int64_t runs = (d->col_tiles + t - 1) / t, rounds = (chunk_tiles * runs + resident - 1) / resident;
-    const double cost = (double)rounds * (double)t;
-    if (!tpr || cost < best_cost) { best_cost = cost; tpr = t; }
-    if (rounds == 1) break;
-  }
+  const int64_t chunk_tiles = cut_rows(t_tiles, cap), cap_rows = chunk_tiles * TILE;
+  const int64_t tpr = tiles_per_part(d->col_tiles, std::min<int64_t>(d->col_tiles, 4096), chunk_tiles, 2 * (int64_t)d->n_cu);      // nothing is kept per run
   const int64_t n_runs = (d->col_tiles + tpr - 1) / tpr;
   const Areas<T> a(d, cap_rows, 0);
   const bool scale = flags & SSN_MAP_NORMALIZE;
@@ -811,30 +793,21 @@ int map_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype
   d->launches = 0;
   for (int64_t r0 = 0; r0 < n_rows; r0 += cap_rows) {
     const int n = (int)std::min(cap_rows, n_rows - r0), n_pad = (n + TILE - 1) / TILE * TILE;
-    if (host) DHIP(hipMemcpyAsync(a.stage, host + (size_t)r0 * d->K, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
-    DHIP(hipEventRecord(d->e0, d->stream));
-    if (host) DHIP(scale ? (launch_prepare<T, double, true>(d, a.stage, d->K, n, n_pad, a.conv)) : (launch_prepare<T, double, false>(d, a.stage, d->K, n, n_pad, a.conv)));
-    else if (rows_dtype == SSN_F32) {
-      const float* src = (const float*)dev + (size_t)r0 * ld;
-      DHIP(scale ? (launch_prepare<T, float, true>(d, src, ld, n, n_pad, a.conv)) : (launch_prepare<T, float, false>(d, src, ld, n, n_pad, a.conv)));
-    } else {
-      const double* src = (const double*)dev + (size_t)r0 * ld;
-      DHIP(scale ? (launch_prepare<T, double, true>(d, src, ld, n, n_pad, a.conv)) : (launch_prepare<T, double, false>(d, src, ld, n, n_pad, a.conv)));
-    }
+    if (const int rc = prepare_chunk<T>(d, a, host, dev, rows_dtype, ld, r0, n, n_pad, scale)) return rc;
     TO* dst = out_on_device ? out + (size_t)r0 * out_ld : (TO*)d->m_dev;
     hipLaunchKernelGGL((k_decode_map<T, TO>), dim3((unsigned)(n_pad / TILE), (unsigned)n_runs), dim3(256), 0, d->stream, (const T*)a.conv, (const T*)d->table,
                        (int)d->Kp, n, (unsigned)S, (int)d->col_tiles, (int)tpr, square, dst, (long long)(out_on_device ? out_ld : S));
-    DHIP(hipGetLastError());
-    DHIP(hipEventRecord(d->e1, d->stream));
-    if (!out_on_device) DHIP(hipMemcpyAsync(d->m_pin, d->m_dev, (size_t)n * S * sizeof(TO), hipMemcpyDeviceToHost, d->stream));
-    DHIP(hipStreamSynchronize(d->stream));
+    SVC_HIP(hipGetLastError());
+    SVC_HIP(hipEventRecord(d->e1, d->stream));
+    if (!out_on_device) SVC_HIP(hipMemcpyAsync(d->m_pin, d->m_dev, (size_t)n * S * sizeof(TO), hipMemcpyDeviceToHost, d->stream));
+    SVC_HIP(hipStreamSynchronize(d->stream));
     if (!out_on_device) {
       const TO* src = (const TO*)d->m_pin;
       if (out_ld == S) memcpy(out + (size_t)r0 * S, src, (size_t)n * S * sizeof(TO));
       else for (int64_t r = 0; r < n; ++r) memcpy(out + (size_t)(r0 + r) * out_ld, src + (size_t)r * S, (size_t)S * sizeof(TO));
     }
     float ms = 0.0f;
-    DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
+    SVC_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
     d->kernel_ms += ms;
     d->launches += 2;
   }
@@ -851,14 +824,14 @@ int upload_refine(ssn_decoder* d,const double* dft, const double* M, const doubl
   for (int64_t i = 0; i < K * dim; ++i) m[i] = (T)M[i];
   std::vector<double> box((size_t)3 * dim);
   for (int64_t a = 0; a < dim; ++a) { box[a] = lo[a]; box[dim + a] = hi[a]; box[2 * dim + a] = pitch[a]; }
-  DHIP(hipMalloc(&d->r_dft, tab.size() * sizeof(T)));
-  DHIP(hipMalloc(&d->r_M, m.size() * sizeof(T)));
-  DHIP(hipMalloc((void**)&d->r_points, (size_t)d->S * dim * 8));
-  DHIP(hipMalloc((void**)&d->r_box, box.size() * 8));
-  DHIP(hipMemcpy(d->r_dft, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice));
-  DHIP(hipMemcpy(d->r_M, m.data(), m.size() * sizeof(T), hipMemcpyHostToDevice));
-  DHIP(hipMemcpy(d->r_points, points, (size_t)d->S * dim * 8, hipMemcpyHostToDevice));
-  DHIP(hipMemcpy(d->r_box, box.data(), box.size() * 8, hipMemcpyHostToDevice));
+  SVC_HIP(hipMalloc(&d->r_dft, tab.size() * sizeof(T)));
+  SVC_HIP(hipMalloc(&d->r_M, m.size() * sizeof(T)));
+  SVC_HIP(hipMalloc((void**)&d->r_points, (size_t)d->S * dim * 8));
+  SVC_HIP(hipMalloc((void**)&d->r_box, box.size() * 8));
+  SVC_HIP(hipMemcpy(d->r_dft, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice));
+  SVC_HIP(hipMemcpy(d->r_M, m.data(), m.size() * sizeof(T), hipMemcpyHostToDevice));
+  SVC_HIP(hipMemcpy(d->r_points, points, (size_t)d->S * dim * 8, hipMemcpyHostToDevice));
+  SVC_HIP(hipMemcpy(d->r_box, box.data(), box.size() * 8, hipMemcpyHostToDevice));
   return SSN_OK;
 }
 
@@ -872,20 +845,18 @@ int decode_rows_composed(ssn_decoder* d, const double* host, int64_t n_rows, int
   const Areas<float> a(d, cap_rows, 0);
   const int n = (int)n_rows, n_pad = (n + TILE - 1) / TILE * TILE;
   float *C = nullptr, *part = nullptr;
-  DHIP(hipMalloc(&C, (size_t)n_rows * d->S * 4));
+  SVC_HIP(hipMalloc(&C, (size_t)n_rows * d->S * 4));
   if (hipMalloc(&part, (size_t)n_rows * 8) != hipSuccess) { (void)hipFree(C); return fail(SSN_ENOMEM, "hipMalloc"); }
   std::vector<int32_t> idx((size_t)n_rows);
   auto run = [&]() -> int {
-    DHIP(hipMemcpyAsync(a.stage, host, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
-    DHIP(hipEventRecord(d->e0, d->stream));
-    DHIP((launch_prepare<float, double>(d, a.stage, d->K, n, n_pad, a.conv)));
-    DHIP(ssn::launch_gemm_nt<float>(d->stream, a.conv, (int)d->Kp, (const float*)d->table, (int)d->Kp, C, (int)d->S, n, (int)d->S, (int)d->Kp, 1));
-    DHIP(ssn::launch_argmax_partial<float>(d->stream, C, (long long)n_rows * d->S, part, n, 1));
-    DHIP(hipEventRecord(d->e1, d->stream));
-    DHIP(hipMemcpyAsync(idx.data(), part + n_rows, (size_t)n_rows * 4, hipMemcpyDeviceToHost, d->stream));
-    DHIP(hipStreamSynchronize(d->stream));
+    if (const int rc = prepare_chunk<float>(d, a, host, nullptr, 0, d->K, 0, n, n_pad, true)) return rc;      // host rows from row 0, scaled
+    SVC_HIP(ssn::launch_gemm_nt<float>(d->stream, a.conv, (int)d->Kp, (const float*)d->table, (int)d->Kp, C, (int)d->S, n, (int)d->S, (int)d->Kp, 1));
+    SVC_HIP(ssn::launch_argmax_partial<float>(d->stream, C, (long long)n_rows * d->S, part, n, 1));
+    SVC_HIP(hipEventRecord(d->e1, d->stream));
+    SVC_HIP(hipMemcpyAsync(idx.data(), part + n_rows, (size_t)n_rows * 4, hipMemcpyDeviceToHost, d->stream));
+    SVC_HIP(hipStreamSynchronize(d->stream));
     float ms = 0.0f;
-    DHIP(hipEventElapsedTime(&ms, d->e0, d->e1));
+    SVC_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
     d->kernel_ms = ms;
     d->launches = 3;
     return SSN_OK;
@@ -901,8 +872,8 @@ int decode_rows_composed(ssn_decoder* d, const double* host, int64_t n_rows, int
 // the decoder's dtype; the encoder and its scratch area go away before the decoder is handed out
 int encode_table(ssn_decoder* d, const double* points, int64_t K, int32_t dim, const double* M, const double* w, int64_t enc_scratch_bytes) {
   const int64_t Sp = d->col_tiles * TILE;
-  DHIP(hipMalloc(&d->table, (size_t)Sp * d->Kp * d->esz));
-  DHIP(hipMemset(d->table, 0, (size_t)Sp * d->Kp * d->esz));
+  SVC_HIP(hipMalloc(&d->table, (size_t)Sp * d->Kp * d->esz));
+  SVC_HIP(hipMemset(d->table, 0, (size_t)Sp * d->Kp * d->esz));
   ssn_encoder* enc = nullptr;
   int rc = ssn_encoder_create(SSN_F64, d->device, d->K, K, dim, M, w, enc_scratch_bytes, &enc);
   if (rc != SSN_OK) return rc;
@@ -931,19 +902,15 @@ int create_decoder(const char* who, int32_t dtype, int32_t device, int64_t n_sam
   if (d->scratch_bytes < d->min_scratch())
     return fail(SSN_EINVAL, "%s: scratch_bytes %lld too small for one %d-row tile of width %lld (%lld bytes)", who, (long long)scratch_bytes,
                 TILE, (long long)width, (long long)d->min_scratch());
-  int ndev = 0;
-  const hipError_t dev_err = hipGetDeviceCount(&ndev);
-  if (dev_err != hipSuccess || ndev <= 0)
-    return fail(SSN_EHIP, "no HIP device available (there is no CPU fallback): hipGetDeviceCount -> %s, %d devices", hipGetErrorString(dev_err), ndev);
-  if (device < 0 || device >= ndev) return fail(SSN_EINVAL, "%s: device %d out of range (%d devices)", who, device, ndev);
+  if (const int rc = check_device(who, device)) return rc;
   DevGuard g(device);
   hipDeviceProp_t prop;
-  DHIP(hipGetDeviceProperties(&prop, device));
+  SVC_HIP(hipGetDeviceProperties(&prop, device));
   d->n_cu = std::max(1, prop.multiProcessorCount);
-  DHIP(hipStreamCreate(&d->stream));
-  DHIP(hipEventCreate(&d->e0));
-  DHIP(hipEventCreate(&d->e1));
-  DHIP(hipMalloc((void**)&d->scratch, (size_t)d->scratch_bytes));
+  SVC_HIP(hipStreamCreate(&d->stream));
+  SVC_HIP(hipEventCreate(&d->e0));
+  SVC_HIP(hipEventCreate(&d->e1));
+  SVC_HIP(hipMalloc((void**)&d->scratch, (size_t)d->scratch_bytes));
   const int rc = fill(d.get());
   if (rc != SSN_OK) return rc;
   *out = d.release();

@@ -23,17 +23,14 @@
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <memory>
 #include <vector>
 #include "../../include/ssn.h"
 #include "ssn_launch.hpp"      // launch_gemm_nt<float>, instantiated by ssn_f32.hip
 #include "ssn_encode.hpp"
+#include "ssn_service.hpp"
 
-namespace ssn {
-int probe_fail(int code, const char* what, hipError_t e);      // ssn_host.hip: sets ssn_last_error
-}
+using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, check_device
 
 namespace {
 
@@ -115,28 +112,6 @@ __global__ __launch_bounds__(256) void k_encode_widen(const float* __restrict__ 
   if (i < count) dst[i] = (double)src[i];
 }
 
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return ssn::probe_fail(code, buf, hipSuccess);
-}
-
-#define EHIP(expr)                                                                                      \
-  do {                                                                                                  \
-    hipError_t e__ = (expr);                                                                            \
-    if (e__ != hipSuccess) return ssn::probe_fail(e__ == hipErrorOutOfMemory ? SSN_ENOMEM : SSN_EHIP, #expr, e__); \
-  } while (0)
-
-struct DevGuard {      // the encoder's device for the duration of a call, the caller's afterwards
-  int prev = -1;
-  explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 struct ssn_encoder {
@@ -193,9 +168,9 @@ int upload_tables(ssn_encoder* e, const double* M, const double* w) {
     cs[r] = std::cos(a);
     sn[r] = std::sin(a);
   }
-  EHIP(hipMalloc((void**)&e->M, (size_t)K * e->dim * 8));
-  EHIP(hipMemcpy(e->M, M, (size_t)K * e->dim * 8, hipMemcpyHostToDevice));
-  EHIP(hipMalloc(&e->B, (size_t)d * Kp * sizeof(T)));
+  SVC_HIP(hipMalloc((void**)&e->M, (size_t)K * e->dim * 8));
+  SVC_HIP(hipMemcpy(e->M, M, (size_t)K * e->dim * 8, hipMemcpyHostToDevice));
+  SVC_HIP(hipMalloc(&e->B, (size_t)d * Kp * sizeof(T)));
   const int64_t per = std::max<int64_t>(1, (int64_t)(8 << 20) / Kp);
   std::vector<T> stage((size_t)std::min(per, d) * Kp, T(0));
   for (int64_t c0 = 0; c0 < d; c0 += per) {
@@ -208,7 +183,7 @@ int upload_tables(ssn_encoder* e, const double* M, const double* w) {
         o[2 * k + 1] = (T)(-(w[k] * sn[r]));
       }
     }
-    EHIP(hipMemcpy((T*)e->B + (size_t)c0 * Kp, stage.data(), (size_t)nc * Kp * sizeof(T), hipMemcpyHostToDevice));
+    SVC_HIP(hipMemcpy((T*)e->B + (size_t)c0 * Kp, stage.data(), (size_t)nc * Kp * sizeof(T), hipMemcpyHostToDevice));
   }
   return SSN_OK;
 }
@@ -249,41 +224,41 @@ int encode(ssn_encoder* e, const void* pts, int on_device, int pts_dtype, int64_
     const void* src = (const char*)pts + (size_t)r0 * pts_ld * isz;
     int64_t ld = pts_ld;
     if (!on_device) {
-      if (pts_ld == e->dim) EHIP(hipMemcpyAsync(a.stage, src, (size_t)m * e->dim * isz, hipMemcpyHostToDevice, e->stream));
-      else EHIP(hipMemcpy2DAsync(a.stage, (size_t)e->dim * isz, src, (size_t)pts_ld * isz, (size_t)e->dim * isz, (size_t)m, hipMemcpyHostToDevice, e->stream));
+      if (pts_ld == e->dim) SVC_HIP(hipMemcpyAsync(a.stage, src, (size_t)m * e->dim * isz, hipMemcpyHostToDevice, e->stream));
+      else SVC_HIP(hipMemcpy2DAsync(a.stage, (size_t)e->dim * isz, src, (size_t)pts_ld * isz, (size_t)e->dim * isz, (size_t)m, hipMemcpyHostToDevice, e->stream));
       src = a.stage;
       ld = e->dim;
     }
-    EHIP(hipEventRecord(e->e0, e->stream));
-    if (f32) EHIP(phase_for<float>(e, src, pts_dtype, ld, m, (float*)a.P));
-    else EHIP(phase_for<double>(e, src, pts_dtype, ld, m, (double*)a.P));
-    EHIP(hipEventRecord(e->e1, e->stream));
+    SVC_HIP(hipEventRecord(e->e0, e->stream));
+    if (f32) SVC_HIP(phase_for<float>(e, src, pts_dtype, ld, m, (float*)a.P));
+    else SVC_HIP(phase_for<double>(e, src, pts_dtype, ld, m, (double*)a.P));
+    SVC_HIP(hipEventRecord(e->e1, e->stream));
     e->launches += 2;
     if (f32) {
       float* C = host_out ? (float*)a.out : (float*)dev_out + (size_t)r0 * out_ld;
       const int ldc = host_out ? (int)e->d : (int)out_ld;
-      EHIP(ssn::launch_gemm_nt<float>(e->stream, (const float*)a.P, (int)e->Kp, (const float*)e->B, (int)e->Kp, C, ldc, m, (int)e->d, (int)e->Kp, 1));
+      SVC_HIP(ssn::launch_gemm_nt<float>(e->stream, (const float*)a.P, (int)e->Kp, (const float*)e->B, (int)e->Kp, C, ldc, m, (int)e->d, (int)e->Kp, 1));
       if (host_out) {
         const long long count = (long long)m * e->d;
         hipLaunchKernelGGL(k_encode_widen, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream, (const float*)a.out, a.wide, count);
-        EHIP(hipGetLastError());
+        SVC_HIP(hipGetLastError());
         e->launches += 1;
       }
     } else if (host_out) {
-      EHIP(launch_product64<double>(e, (const double*)a.P, m, (double*)a.out, e->d));
+      SVC_HIP(launch_product64<double>(e, (const double*)a.P, m, (double*)a.out, e->d));
     } else if (osz == 8) {
-      EHIP(launch_product64<double>(e, (const double*)a.P, m, (double*)dev_out + (size_t)r0 * out_ld, out_ld));
+      SVC_HIP(launch_product64<double>(e, (const double*)a.P, m, (double*)dev_out + (size_t)r0 * out_ld, out_ld));
     } else {
-      EHIP(launch_product64<float>(e, (const double*)a.P, m, (float*)dev_out + (size_t)r0 * out_ld, out_ld));
+      SVC_HIP(launch_product64<float>(e, (const double*)a.P, m, (float*)dev_out + (size_t)r0 * out_ld, out_ld));
     }
-    EHIP(hipEventRecord(e->e2, e->stream));
+    SVC_HIP(hipEventRecord(e->e2, e->stream));
     if (host_out)
-      EHIP(hipMemcpyAsync(host_out + (size_t)r0 * e->d, f32 ? (const void*)a.wide : (const void*)a.out, (size_t)m * e->d * 8, hipMemcpyDeviceToHost, e->stream));
-    EHIP(hipStreamSynchronize(e->stream));      // the next chunk reuses the scratch area
+      SVC_HIP(hipMemcpyAsync(host_out + (size_t)r0 * e->d, f32 ? (const void*)a.wide : (const void*)a.out, (size_t)m * e->d * 8, hipMemcpyDeviceToHost, e->stream));
+    SVC_HIP(hipStreamSynchronize(e->stream));      // the next chunk reuses the scratch area
     float ms = 0.0f;
-    EHIP(hipEventElapsedTime(&ms, e->e0, e->e1));
+    SVC_HIP(hipEventElapsedTime(&ms, e->e0, e->e1));
     e->phase_ms += ms;
-    EHIP(hipEventElapsedTime(&ms, e->e1, e->e2));
+    SVC_HIP(hipEventElapsedTime(&ms, e->e1, e->e2));
     e->product_ms += ms;
   }
   return SSN_OK;
@@ -326,17 +301,13 @@ int ssn_encoder_create(int32_t dtype, int32_t device, int64_t d, int64_t K, int3
   if (e->scratch_bytes < e->min_scratch())
     return fail(SSN_EINVAL, "ssn_encoder_create: scratch_bytes %lld too small for one %d-point tile of d %lld, K %lld (%lld bytes)", (long long)scratch_bytes,
                 ROWS, (long long)d, (long long)K, (long long)e->min_scratch());
-  int ndev = 0;
-  const hipError_t dev_err = hipGetDeviceCount(&ndev);
-  if (dev_err != hipSuccess || ndev <= 0)
-    return fail(SSN_EHIP, "no HIP device available (there is no CPU fallback): hipGetDeviceCount -> %s, %d devices", hipGetErrorString(dev_err), ndev);
-  if (device < 0 || device >= ndev) return fail(SSN_EINVAL, "ssn_encoder_create: device %d out of range (%d devices)", device, ndev);
+  if (const int rc = check_device("ssn_encoder_create", device)) return rc;
   DevGuard g(device);
-  EHIP(hipStreamCreate(&e->stream));
-  EHIP(hipEventCreate(&e->e0));
-  EHIP(hipEventCreate(&e->e1));
-  EHIP(hipEventCreate(&e->e2));
-  EHIP(hipMalloc((void**)&e->scratch, (size_t)e->scratch_bytes));
+  SVC_HIP(hipStreamCreate(&e->stream));
+  SVC_HIP(hipEventCreate(&e->e0));
+  SVC_HIP(hipEventCreate(&e->e1));
+  SVC_HIP(hipEventCreate(&e->e2));
+  SVC_HIP(hipMalloc((void**)&e->scratch, (size_t)e->scratch_bytes));
   const int rc = dtype == SSN_F32 ? upload_tables<float>(e.get(), M, w) : upload_tables<double>(e.get(), M, w);
   if (rc != SSN_OK) return rc;
   *out = e.release();

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ssn.h"
+#include "ssn_service.hpp"      // ssn::probe_fail
 
 namespace {
 
@@ -111,10 +112,6 @@ hipError_t run_kind(int threads, int iters, int n_cu, float* sink, unsigned long
 }
 
 }  // namespace
-
-namespace ssn {
-int probe_fail(int code, const char* what, hipError_t e);      // ssn_host.hip: sets ssn_last_error
-}
 
 extern "C" int ssn_probe_issue_rate(int32_t device, int32_t kind, int32_t waves_per_simd, int32_t iters,
                                     double* ns_per_wave_instruction, double* shader_mhz) {

@@ -24,12 +24,13 @@
 #include <stdint.h>
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <memory>
 #include <vector>
 #include "../../include/ssn.h"
 #include "ssn_recall.hpp"
+#include "ssn_service.hpp"
+
+using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, check_device
 
 namespace {
 
@@ -191,33 +192,7 @@ __global__ __launch_bounds__(256) void k_recall_dec_ordered(const double* __rest
 
 }  // namespace
 
-namespace ssn {
-int probe_fail(int code, const char* what, hipError_t e);      // ssn_host.hip: sets ssn_last_error
-}
-
 namespace {
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return ssn::probe_fail(code, buf, hipSuccess);
-}
-
-#define RHIP(expr)                                                                                      \
-  do {                                                                                                  \
-    hipError_t e__ = (expr);                                                                            \
-    if (e__ != hipSuccess) return ssn::probe_fail(e__ == hipErrorOutOfMemory ? SSN_ENOMEM : SSN_EHIP, #expr, e__); \
-  } while (0)
-
-struct DevGuard {      // the simulator's device for the duration of a call, the caller's afterwards
-  int prev = -1;
-  explicit DevGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -263,8 +238,8 @@ template <typename T>
 int upload_vec(void** dst, const double* src, int64_t count) {
   std::vector<T> h((size_t)count);
   for (int64_t i = 0; i < count; ++i) h[(size_t)i] = (T)src[i];
-  RHIP(hipMalloc(dst, (size_t)count * sizeof(T)));
-  RHIP(hipMemcpy(*dst, h.data(), (size_t)count * sizeof(T), hipMemcpyHostToDevice));
+  SVC_HIP(hipMalloc(dst, (size_t)count * sizeof(T)));
+  SVC_HIP(hipMemcpy(*dst, h.data(), (size_t)count * sizeof(T), hipMemcpyHostToDevice));
   return SSN_OK;
 }
 
@@ -277,7 +252,7 @@ int set_keys(ssn_recall* rc, const double* keys, int64_t L) {
       if (rc->part) (void)hipFree(rc->part);
       rc->part = nullptr;
       rc->scratch_bytes = 0;
-      RHIP(hipMalloc((void**)&rc->part, (size_t)want));
+      SVC_HIP(hipMalloc((void**)&rc->part, (size_t)want));
       rc->scratch_bytes = want;
     }
   }
@@ -286,20 +261,20 @@ int set_keys(ssn_recall* rc, const double* keys, int64_t L) {
                 (long long)L, (long long)(Lp * rc->dvp * 4));
   if (Lp != rc->Lp) {
     rc->drop_keys();
-    RHIP(hipMalloc(&rc->keys, (size_t)(Lp * rc->Kp) * sizeof(T)));
-    RHIP(hipMalloc(&rc->act, (size_t)(Lp * rc->n_ld) * sizeof(T)));
-    RHIP(hipMemset(rc->act, 0, (size_t)(Lp * rc->n_ld) * sizeof(T)));
-    if (sizeof(T) == 4) RHIP(hipMalloc((void**)&rc->qacc, (size_t)(Lp * rc->dvp) * 4));
+    SVC_HIP(hipMalloc(&rc->keys, (size_t)(Lp * rc->Kp) * sizeof(T)));
+    SVC_HIP(hipMalloc(&rc->act, (size_t)(Lp * rc->n_ld) * sizeof(T)));
+    SVC_HIP(hipMemset(rc->act, 0, (size_t)(Lp * rc->n_ld) * sizeof(T)));
+    if (sizeof(T) == 4) SVC_HIP(hipMalloc((void**)&rc->qacc, (size_t)(Lp * rc->dvp) * 4));
     rc->Lp = Lp;
   } else if (rc->out) {
     (void)hipFree(rc->out);
     rc->out = nullptr;
   }
-  RHIP(hipMalloc((void**)&rc->out, (size_t)(L * rc->d_val) * 8));
+  SVC_HIP(hipMalloc((void**)&rc->out, (size_t)(L * rc->d_val) * 8));
   std::vector<T> h((size_t)(Lp * rc->Kp), T(0));
   for (int64_t l = 0; l < L; ++l)
     for (int64_t k = 0; k < rc->d_key; ++k) h[(size_t)(l * rc->Kp + k)] = (T)keys[l * rc->d_key + k];
-  RHIP(hipMemcpy(rc->keys, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  SVC_HIP(hipMemcpy(rc->keys, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   rc->L = L;
   return SSN_OK;
 }
@@ -325,7 +300,7 @@ int run_f32(ssn_recall* rc, const ssn::BufView& e, const ssn::BufView& w, hipStr
   hipLaunchKernelGGL(k_recall_act, dim3((unsigned)(rc->n_ld / TN), (unsigned)(rc->Lp / TL)), dim3(256), 0, st, (const float*)rc->keys, (int)rc->Kp,
                      (const float*)e.d, (long long)e.ld, (int)rc->n, (int)rc->d_key, (const float*)rc->scale, (const float*)rc->bias, rp.neuron,
                      (float)rp.tau_rc, (float)rp.tau_ref, (float)rp.amplitude, (float*)rc->act, (long long)rc->n_ld);
-  RHIP(hipGetLastError());
+  SVC_HIP(hipGetLastError());
   rc->launches = 1;
   const int64_t cpp = rc->chunks_per_pass();
   const long long ldw = w.transposed ? w.ldt : w.ld;
@@ -338,10 +313,10 @@ int run_f32(ssn_recall* rc, const ssn::BufView& e, const ssn::BufView& w, hipStr
     else
       hipLaunchKernelGGL(k_recall_partial<false>, grid, dim3(256), 0, st, (const float*)rc->act, (long long)rc->n_ld, (const float*)w.d, ldw, (int)rc->n,
                          (int)rc->d_val, (int)c0, rc->part, (int)rc->dvp, (int)rc->Lp);
-    RHIP(hipGetLastError());
+    SVC_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_recall_finish, dim3((unsigned)((rc->L * rc->d_val + 255) / 256)), dim3(256), 0, st, (const float*)rc->part, nc,
                        (long long)(rc->Lp * rc->dvp), (int)rc->dvp, (int)rc->L, (int)rc->d_val, c0 == 0 ? 1 : 0, rc->qacc, rc->out);
-    RHIP(hipGetLastError());
+    SVC_HIP(hipGetLastError());
     rc->launches += 2;
   }
   return SSN_OK;
@@ -352,10 +327,10 @@ int run_f64(ssn_recall* rc, const ssn::BufView& e, const ssn::BufView& w, hipStr
   hipLaunchKernelGGL(k_recall_act_ordered, dim3((unsigned)((rc->n + 255) / 256), (unsigned)rc->L), dim3(256), 0, st, (const double*)rc->keys, (int)rc->Kp,
                      (const double*)e.d, (long long)e.ld, (int)rc->n, (int)rc->d_key, (const double*)rc->scale, (const double*)rc->bias, rp.neuron, rp.tau_rc,
                      rp.tau_ref, rp.amplitude, (double*)rc->act, (long long)rc->n_ld);
-  RHIP(hipGetLastError());
+  SVC_HIP(hipGetLastError());
   hipLaunchKernelGGL(k_recall_dec_ordered, dim3((unsigned)((rc->d_val + 255) / 256), (unsigned)rc->L), dim3(256), 0, st, (const double*)rc->act,
                      (long long)rc->n_ld, (const double*)w.d, (long long)(w.transposed ? w.ldt : w.ld), w.transposed, (int)rc->n, (int)rc->d_val, rc->out);
-  RHIP(hipGetLastError());
+  SVC_HIP(hipGetLastError());
   rc->launches = 2;
   return SSN_OK;
 }
@@ -376,10 +351,7 @@ int ssn_recall_create(ssn_sim* sim, int32_t enc_buffer, int32_t dec_buffer, int6
                 (long long)d_val);
   if (neuron != SSN_LIF && neuron != SSN_LIFRATE && neuron != SSN_RELU) return fail(SSN_EINVAL, "ssn_recall_create: unknown neuron type %d", neuron);
   if (scratch_bytes < 0) return fail(SSN_EINVAL, "ssn_recall_create: negative scratch_bytes");
-  int ndev = 0;
-  const hipError_t dev_err = hipGetDeviceCount(&ndev);
-  if (dev_err != hipSuccess || ndev <= 0)
-    return fail(SSN_EHIP, "no HIP device available (there is no CPU fallback): hipGetDeviceCount -> %s, %d devices", hipGetErrorString(dev_err), ndev);
+  if (const int rc = check_device(nullptr, 0)) return rc;      // the device is the simulator's: only the count is tested, and before `sim`
   if (!sim) return fail(SSN_EINVAL, "ssn_recall_create: null simulator");
   std::unique_ptr<ssn_recall> rc(new ssn_recall);
   rc->sim = sim;
@@ -398,8 +370,8 @@ int ssn_recall_create(ssn_sim* sim, int32_t enc_buffer, int32_t dec_buffer, int6
   rc->dvp = round_up(d_val, TN);
   rc->n_chunks = rc->n_ld / CH;
   DevGuard g(rc->device);
-  RHIP(hipEventCreate(&rc->e0));
-  RHIP(hipEventCreate(&rc->e1));
+  SVC_HIP(hipEventCreate(&rc->e0));
+  SVC_HIP(hipEventCreate(&rc->e1));
   st = rc->dtype == SSN_F32 ? upload_vec<float>(&rc->scale, scale, n) : upload_vec<double>(&rc->scale, scale, n);
   if (st == SSN_OK) st = rc->dtype == SSN_F32 ? upload_vec<float>(&rc->bias, bias, n) : upload_vec<double>(&rc->bias, bias, n);
   if (st != SSN_OK) return st;
@@ -409,7 +381,7 @@ int ssn_recall_create(ssn_sim* sim, int32_t enc_buffer, int32_t dec_buffer, int6
     if (scratch_bytes < one)
       return fail(SSN_EINVAL, "ssn_recall_create: scratch_bytes %lld too small for one partial sum of %lld key rows (%lld bytes)", (long long)scratch_bytes,
                   (long long)n_keys, (long long)one);
-    RHIP(hipMalloc((void**)&rc->part, (size_t)scratch_bytes));
+    SVC_HIP(hipMalloc((void**)&rc->part, (size_t)scratch_bytes));
     rc->scratch_bytes = scratch_bytes;
   }
   st = rc->dtype == SSN_F32 ? set_keys<float>(rc.get(), keys, n_keys) : set_keys<double>(rc.get(), keys, n_keys);
@@ -437,14 +409,14 @@ int ssn_recall_run(ssn_recall* rc, double* dst) {
   if (st != SSN_OK) return st;
   DevGuard g(rc->device);
   hipStream_t s = e.stream;
-  RHIP(hipEventRecord(rc->e0, s));
+  SVC_HIP(hipEventRecord(rc->e0, s));
   st = rc->dtype == SSN_F32 ? run_f32(rc, e, w, s) : run_f64(rc, e, w, s);
   if (st != SSN_OK) return st;
-  RHIP(hipEventRecord(rc->e1, s));
-  RHIP(hipMemcpyAsync(dst, rc->out, (size_t)(rc->L * rc->d_val) * 8, hipMemcpyDeviceToHost, s));
-  RHIP(hipStreamSynchronize(s));
+  SVC_HIP(hipEventRecord(rc->e1, s));
+  SVC_HIP(hipMemcpyAsync(dst, rc->out, (size_t)(rc->L * rc->d_val) * 8, hipMemcpyDeviceToHost, s));
+  SVC_HIP(hipStreamSynchronize(s));
   float ms = 0.0f;
-  RHIP(hipEventElapsedTime(&ms, rc->e0, rc->e1));
+  SVC_HIP(hipEventElapsedTime(&ms, rc->e0, rc->e1));
   rc->kernel_ms = ms;
   rc->last_transposed = w.transposed;
   return SSN_OK;

@@ -65,8 +65,14 @@ class GridDecoder:
         self.ssp_space = ssp_space
         self.table_source = table
         self._encoder = None          # the SSPEncoder of clean_up(encode="device"), made on first use
+        # the box of refine(): the pitch of the space's own grid, or trust= beside samples=
+        grid = (num_samples, sampling_method) if samples is None else None
         if table == "device":
-            self._init_from_points(num_samples, sampling_method, dtype, device, scratch_bytes, trust)
+            from .encoding import tables
+            pts = np.ascontiguousarray(ssp_space.get_sample_points(num_samples, sampling_method), dtype=np.float64)
+            K, M, w = tables(ssp_space)
+            self._create(pts, grid, trust, pts.shape[0], ssp_space.ssp_dim, dtype, device, "ssn_decoder_create_from_points", pts,
+                         (K, int(ssp_space.domain_dim), M.ctypes.data, w.ctypes.data, int(scratch_bytes or 0), 0))
             return
         if samples is None:
             sample_ssps, sample_points = ssp_space.get_sample_pts_and_ssps(num_samples, sampling_method)
@@ -75,37 +81,22 @@ class GridDecoder:
         table = np.ascontiguousarray(np.asarray(sample_ssps, dtype=np.float64))
         if table.ndim != 2:
             raise ValueError(f"sample_ssps must be (n_samples, width), got shape {table.shape}")
-        self.sample_points = np.asarray(sample_points)
-        # the box of refine(): the pitch of the space's own grid, or trust= beside samples=
-        self._grid = (num_samples, sampling_method) if samples is None else None
-        self._trust, self._refine_key = trust, None
-        self.n_samples, self.width = int(table.shape[0]), int(table.shape[1])
-        self.dtype, self.device = dtype, int(device)
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        self.closed = True
-        rc = self._lib.ssn_decoder_create(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, table.ctypes.data,
-                                          self.n_samples, self.width, int(scratch_bytes or 0), C.byref(self._h))
-        if rc != 0:
-            raise fe.BuildError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
-        self.closed = False
+        self._create(np.asarray(sample_points), grid, trust, table.shape[0], table.shape[1], dtype, device, "ssn_decoder_create", table,
+                     (int(scratch_bytes or 0),))
 
-    def _init_from_points(self, num_samples, sampling_method, dtype, device, scratch_bytes, trust):
-        from .encoding import tables
-        space = self.ssp_space
-        pts = np.ascontiguousarray(space.get_sample_points(num_samples, sampling_method), dtype=np.float64)
-        K, M, w = tables(space)
-        self.sample_points = pts
-        self._grid = (num_samples, sampling_method)
+    def _create(self, sample_points, grid, trust, n_samples, width, dtype, device, create, source, rest):
+        """The tail of both constructors: the fields, then the ABI call named ``create`` - ``(dtype, device, source, n_samples,
+        width, *rest, handle)``, ``source`` the float64 array the table comes from - whose non-zero status is a BuildError."""
+        self.sample_points = sample_points
+        self._grid = grid
         self._trust, self._refine_key = trust, None
-        self.n_samples, self.width = int(pts.shape[0]), int(space.ssp_dim)
+        self.n_samples, self.width = int(n_samples), int(width)
         self.dtype, self.device = dtype, int(device)
         self._lib = _lib.load()
         self._h = C.c_void_p()
         self.closed = True
-        rc = self._lib.ssn_decoder_create_from_points(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, pts.ctypes.data,
-                                                      self.n_samples, self.width, K, int(space.domain_dim), M.ctypes.data, w.ctypes.data,
-                                                      int(scratch_bytes or 0), 0, C.byref(self._h))
+        rc = getattr(self._lib, create)(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, source.ctypes.data, self.n_samples,
+                                        self.width, *rest, C.byref(self._h))
         if rc != 0:
             raise fe.BuildError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
         self.closed = False

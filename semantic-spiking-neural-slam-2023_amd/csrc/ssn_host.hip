@@ -1157,6 +1157,7 @@ struct Sim final : ssn_sim {
         CHK(dft4_tables(sp.first, sp.second, &g1, &g2));
         a->src = (const float*)(sig + o.i[1]); a->dst = (float*)(sig + o.i[0]); a->tw = tw; a->N = d; a->kind = kind;
         a->set = (int)o.i[5]; a->nr = 0; a->N1 = sp.first; a->N2 = sp.second; a->g1 = g1; a->g2 = g2;
+        list_dft(*a);
         return SSN_OK;
       }
     }
@@ -1182,7 +1183,15 @@ struct Sim final : ssn_sim {
     a->src = (const float*)(sig + o.i[1]); a->dst = (float*)(sig + o.i[0]); a->tw = tw; a->N = d; a->kind = kind;
     a->set = (int)o.i[5]; a->nr = (int)rad.size();
     for (size_t i = 0; i < rad.size(); ++i) a->radix[i] = rad[i];
+    list_dft(*a);
     return SSN_OK;
+  }
+  // SSN_DEBUG_PLAN: what plan_dft planned, one line per transform (the caller may still keep the matrix: M >= 2048)
+  void list_dft(const ssn::DftArgs& a) const {
+    if (!opt.debug_plan) return;
+    fprintf(stderr, "[ssn] dft kind %d N %d M %d inplace %d split %dx%d radices", a.kind, a.N, a.M, a.inplace, a.N1, a.N2);
+    for (int i = 0; i < a.nr; ++i) fprintf(stderr, " %d", a.radix[i]);
+    fprintf(stderr, "\n");
   }
 
   // position of frequency k after the in-place decimation-in-frequency passes with radices rad[0], rad[1], ...

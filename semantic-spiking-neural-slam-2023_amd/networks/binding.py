@@ -11,6 +11,8 @@ w so that the element-wise product of ``tr_a @ a`` and ``tr_b @ b`` yields the f
 of the DC (and Nyquist) bins are identically zero and are kept, like the reference
 (its ``remove_imag_rows`` is a no-op).
 """
+import functools
+
 import numpy as np
 
 from .. import frontend as nengo
@@ -23,10 +25,14 @@ def circconv(a, b, invert_a=False, invert_b=False, axis=-1):
     return np.fft.ifft((A.conj() if invert_a else A) * (B.conj() if invert_b else B), axis=axis).real
 
 
+@functools.lru_cache(maxsize=2)
 def dft_half(n):
-    """(n//2+1, n) complex DFT rows ``exp(-2 pi i w x / n)`` of the non-redundant half spectrum."""
+    """(n//2+1, n) complex DFT rows ``exp(-2 pi i w x / n)`` of the non-redundant half spectrum (read-only: the last two lengths
+    are kept, since the builder's ``dft_structure`` asks for the same length up to five times per matrix)."""
     wx = np.outer(np.arange(n // 2 + 1), np.arange(n)) % n
-    return np.exp(-2j * np.pi * wx / n)
+    rows = np.exp(-2j * np.pi * wx / n)
+    rows.setflags(write=False)
+    return rows
 
 
 def transform_in(dims, align, invert):

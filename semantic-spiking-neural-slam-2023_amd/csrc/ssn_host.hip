@@ -108,7 +108,9 @@ enum MicroKindFlag {
   MK_BATCH_W = 128,     // time-batched stage: writes dst
   MK_BATCH_PRODUCT = 256 // time-batched stage: a matrix product - reads `cols` elements of src, not `len` (batch_read_len, run_batch)
 };
-// (a kind appended to ssn::MicroKind needs its row below: without one it would read as "no flags")
+// A kind appended to ssn::MicroKind takes: the enum (ssn_launch.hpp), one `case` in ssn_micro.hpp (what it computes - every
+// kernel that runs micro-operators calls that one definition), its row below (without one it would read as "no flags") and its
+// row in Sim::micro_access (what it reads and writes).
 static_assert(ssn::M_LINCOMB == 17, "MICRO_KINDS has a row for every MicroKind up to M_LINCOMB: add the new kind's");
 struct MicroKindTable {
   unsigned short f[ssn::M_LINCOMB + 1] = {};
@@ -129,6 +131,12 @@ struct MicroKindTable {
 };
 constexpr MicroKindTable MICRO_KINDS;
 constexpr bool kind_is(int kind, int flag) { return kind > 0 && kind <= ssn::M_LINCOMB && (MICRO_KINDS.f[kind] & flag) != 0; }
+// (the round kernel chunks an operator by ssn::micro_row_kind, the planner counts its blocks by MK_GLUE_ROW)
+constexpr bool glue_rows_agree() {
+  for (int k = 0; k <= ssn::M_LINCOMB + 1; ++k) if (kind_is(k, MK_GLUE_ROW) != ssn::micro_row_kind(k)) return false;
+  return true;
+}
+static_assert(glue_rows_agree(), "MK_GLUE_ROW and ssn::micro_row_kind name different kinds");
 
 // Plan options: ssn_model_desc.flags and the environment knobs, read once at ssn_create and constant for the simulator's
 // life.  PlanOptions::read is the only caller of getenv in the library.  One row per knob: how the variable is read, the

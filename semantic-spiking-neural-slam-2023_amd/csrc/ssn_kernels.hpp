@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "ssn_launch.hpp"
+#include "ssn_micro.hpp"
 
 namespace ssn {
 
@@ -85,13 +86,6 @@ __device__ inline T neuron_step(const NeuronParams<T>& p, T J, T& V, T& R) {
     return j > T(0) ? T(1) / (p.tau_ref + p.tau_rc * log1p_(T(1) / j)) : T(0);
   }
   return J > T(0) ? J : T(0);                          // ReLU
-}
-
-template <typename T>
-__device__ inline T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1058,7 +1052,7 @@ hipError_t launch_dft(hipStream_t s, const DftBatch& b, int count) {
 // workgroup barrier only where the host scheduler found a dependency (level change).  This turns
 // the dozen tiny nengo operators between two big kernels into a single launch.
 // ---------------------------------------------------------------------------------------------
-// for i = tid, tid + 1024, ... < len: store(i, load(i)), four elements per trip with all loads issued first
+// for i = tid, tid + 1024, ... < len: store(i, load(i)), U independent elements per trip with all loads issued first
 template <typename T, int U, typename L, typename S>
 __device__ inline void vecn_loop(int tid, int len, L load, S store) {
   for (int i0 = tid; i0 < len; i0 += U * 1024) {
@@ -1094,11 +1088,26 @@ inline hipError_t read_program_stamps(unsigned long long* out, int n) {
 #define SSN_STAMP(i) do {} while (0)
 #endif
 
+// k_program's walk over the elements or rows of an operator (ssn_micro.hpp): thread tid of the one workgroup takes every 1024th.  A
+// single workgroup hides memory latency only through loads in flight (the head program of a SLAM timestep moves ~120 k
+// elements: 48 -> 14 us).
+template <typename T>
+struct ProgramWalk {
+  int tid;
+  long long now;      // (the program counts the timesteps itself: k_program's `step`)
+  StepCtx* ctx;
+  template <typename L, typename S>
+  __device__ void operator()(long long len, L load, S store) const { vec4_loop<T>(tid, len, load, store); }
+  template <typename R>
+  __device__ void rows(long long len, R row) const { for (long long r = tid; r < len; r += 1024) row(r); }
+  __device__ void overflow() const { if (tid == 0) ctx->probe_overflow = 1; }
+  __device__ long long step() const { return now; }
+};
+
 template <typename T>
 __global__ __launch_bounds__(1024) void k_program(const MicroOp<T>* __restrict__ all_ops, const ProgDesc* __restrict__ progs, int n_progs,
                                                   T* __restrict__ gsig, StepCtx* __restrict__ ctx) {
-  __shared__ T sred[16];
-  __shared__ int sidx[16];
+  __shared__ __align__(16) unsigned char swave[16 * (sizeof(T) + sizeof(int))];      // one value and one index per wave (gate, argmax)
   const int tid = threadIdx.x;
   long long step = ctx->step;          // steps completed before the one being executed
  for (int pi = 0; pi < n_progs; ++pi) {
@@ -1111,173 +1120,29 @@ __global__ __launch_bounds__(1024) void k_program(const MicroOp<T>* __restrict__
   for (int o = 0; o < n_ops; ++o) {
     const MicroOp<T> op = ops[o];
     if (op.barrier) __syncthreads();
-    switch (op.kind) {
-      // element-wise operators: four independent elements per thread and trip, loads before stores - a single
-      // workgroup hides memory latency only through loads in flight (the head program of a SLAM timestep moves
-      // ~120 k elements: 48 -> 14 us)
-      case M_FILL:
-        { T* const d = sig + op.dst; for (int i = tid; i < (int)op.len; i += 1024) d[i] = op.a; }
+    const ProgramWalk<T> walk{tid, step, ctx};
+    switch (op.kind) {      // (what each kind computes: ssn_micro.hpp)
+      case M_LINCOMB:
+        for (int i = tid; i < (int)op.len; i += 1024) micro_lincomb<T, 1>(op, sig, i, 0);
         break;
-      case M_AXPY_INC:
-        { T* const d = sig + op.dst; const T* const x = sig + op.src;
-          vec4_loop<T>(tid, op.len, [&](int i) { return d[i] + op.a * x[i]; }, [&](int i, T v) { d[i] = v; }); }
-        break;
-      case M_AXPY_SET:
-        { T* const d = sig + op.dst; const T* const x = sig + op.src;
-          vec4_loop<T>(tid, op.len, [&](int i) { return op.a * x[i]; }, [&](int i, T v) { d[i] = v; }); }
-        break;
-      case M_LOWPASS:   // dst = a*dst + b*src, b = (1-a)*gain
-        { T* const d = sig + op.dst; const T* const x = sig + op.src;
-          vec4_loop<T>(tid, op.len, [&](int i) { return op.a * d[i] + op.b * x[i]; }, [&](int i, T v) { d[i] = v; }); }
-        break;
-      case M_LINCOMB: {   // dst = a * dst + b * (c + sum_k alpha_k * sig[src_k + i]); p0 = LinTerm[i0]
-        const LinTerm<T>* const t = (const LinTerm<T>*)op.p0;
-        T* const d = sig + op.dst;
-        for (int i = tid; i < (int)op.len; i += 1024) {
-          T acc = op.c;
-          for (int k = 0; k < (int)op.i0; ++k) acc += t[k].alpha * sig[t[k].src + i];
-          d[i] = (op.a != T(0) ? op.a * d[i] : T(0)) + op.b * acc;
-        }
-        break;
-      }
-      case M_TABLE: {   // p0 = TableSlot*
-        const TableSlot* t = (const TableSlot*)op.p0;
-        const long long rel = step - t->first_step;
-        int row = -1;
-        if (rel >= 0 && rel < t->n_idx) row = t->idx[rel];
-        const T* rows = (const T*)t->rows;
-        const bool have = row >= 0 && row < t->n_rows;
-        const T* const trow = rows + (have ? (size_t)row * t->width : 0);
-        T* const d = sig + op.dst;
-        vec4_loop<T>(tid, op.len, [&](int i) { return have ? trow[i] : T(0); }, [&](int i, T v) { d[i] = v; });
-        break;
-      }
-      case M_MATVEC_INC:
-      case M_MATVEC_SET: {   // p0 = W (rows x ld), i0 = cols, i1 = ld; len = rows
-        const T* Wm = (const T*)op.p0;
-        for (long long r = tid; r < op.len; r += 1024) {
-          T s = T(0);
-          for (int c = 0; c < (int)op.i0; ++c) s += Wm[(size_t)r * op.i1 + c] * sig[op.src + c];
-          if (op.kind == M_MATVEC_INC) sig[op.dst + r] += s; else sig[op.dst + r] = s;
-        }
-        break;
-      }
-      case M_ENS_FINISH: {   // p0 = partials [K][P][dout], p1 = dst_idx int32 [K*dout]; len = K*dout, i0 = P, i1 = dout
-        const T* part = (const T*)op.p0;
-        const int* didx = (const int*)op.p1;
-        const int P = (int)op.i0, dout = (int)op.i1;
-        for (long long i = tid; i < op.len; i += 1024) {
-          const long long k = i / dout, r = i - k * dout;
-          T s = T(0);
-          for (int p = 0; p < P; ++p) s += part[((size_t)k * P + p) * dout + r];
-          sig[didx[i]] = s;
-        }
-        break;
-      }
-      case M_GATE: {   // src = [est(d), cur(d), flag], len = d, a = thres, b = rate
-        T part = T(0);
-        for (long long i = tid; i < op.len; i += 1024) part += sig[op.src + i] * sig[op.src + op.len + i];
-        part = wave_sum(part);
-        if ((tid & 63) == 0) sred[tid >> 6] = part;
-        __syncthreads();
-        T dot = T(0);
-        for (int w = 0; w < 16; ++w) dot += sred[w];
-        const T flag = sig[op.src + 2 * op.len];
-        const bool open = (flag <= T(1e-3) && flag >= T(-1e-3)) && dot > op.a;
-        for (long long i = tid; i < op.len; i += 1024)
-          sig[op.dst + i] = open ? op.b * (sig[op.src + i] - sig[op.src + op.len + i]) : T(0);
+      case M_GATE:
+        micro_gate<T, 1024>(op, sig, swave);
         __syncthreads();
         break;
-      }
-      case M_ARGMAX_GATHER: {   // p1 = sims (i0 rows, scratch), p0 = table (i0 x ld=i1), len = cols: dst = table[argmax]
-        // src = P > 0: p1 holds the first maxima of P consecutive slices (k_argmax_partial): P values, then their P row indices
-        T best = T(-INFINITY);
-        int bi = 0x7fffffff;
-        const T* sims = (const T*)op.p1;
-        const int n_cand = op.src > 0 ? (int)op.src : (int)op.i0;
-        const int* cand_idx = op.src > 0 ? (const int*)(sims + op.src) : nullptr;
-        for (int i0 = tid; i0 < n_cand; i0 += 4096) {       // four reads in flight, examined in ascending order
-          T v[4];
-          int vi[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * 1024;
-            v[u] = i < n_cand ? sims[i] : T(-INFINITY);
-            vi[u] = (cand_idx && i < n_cand) ? cand_idx[i] : i;
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-            if (v[u] > best) { best = v[u]; bi = vi[u]; }     // first maximum within a thread (ascending i)
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          const T ov = __shfl_down(best, off, 64);
-          const int oi = __shfl_down(bi, off, 64);
-          if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
-        if ((tid & 63) == 0) { sred[tid >> 6] = best; sidx[tid >> 6] = bi; }
-        __syncthreads();
-        best = sred[0]; bi = sidx[0];
-        for (int w = 1; w < 16; ++w)
-          if (sred[w] > best || (sred[w] == best && sidx[w] < bi)) { best = sred[w]; bi = sidx[w]; }
-        if (bi == 0x7fffffff) bi = 0;
-        const T* tab = (const T*)op.p0;
-        { const T* const trow = tab + (size_t)bi * op.i1; T* const d = sig + op.dst;
-          vec4_loop<T>(tid, op.len, [&](int i) { return trow[i]; }, [&](int i, T v) { d[i] = v; }); }
+      case M_ARGMAX_GATHER:
+        micro_argmax_gather<T, 1024, 4>(op, sig, swave, walk);
         __syncthreads();
         break;
-      }
-      case M_PROBE: {   // p0 = ProbeSlot*; src, len = width
-        const ProbeSlot* ps = (const ProbeSlot*)op.p0;
-        const long long s1 = step + 1;
-        if (s1 % ps->every == 0) {
-          const long long slot = s1 / ps->every - 1 - ps->base_slot;
-          if (slot >= 0 && slot < ps->capacity) {
-            T* out = (T*)ps->data + (size_t)slot * op.len;
-            const T* const x = sig + op.src;
-            vec4_loop<T>(tid, op.len, [&](int i) { return x[i]; }, [&](int i, T v) { out[i] = v; });
-          } else if (tid == 0) {
-            ctx->probe_overflow = 1;
-          }
-        }
-        break;
-      }
-      case M_ROW_IN: {    // p0 = bsig, i0 = n_sig: sig[dst..] = bsig[row][dst..], row = step - block_start + 1
-        const T* row = (const T*)op.p0 + (size_t)(step - ctx->block_start + 1) * op.i0;
-        { const T* const x = row + op.i1; T* const d = sig + op.dst;                                  // i1 = offset in the signal vector
-          vec4_loop<T>(tid, op.len, [&](int i) { return x[i]; }, [&](int i, T v) { d[i] = v; }); }
-        break;
-      }
-      case M_ROW_OUT: {   // bsig[row][src..] = sig[src..]
-        T* row = (T*)op.p0 + (size_t)(step - ctx->block_start + 1) * op.i0;
-        { const T* const x = sig + op.src; T* const d = row + op.i1;
-          vec4_loop<T>(tid, op.len, [&](int i) { return x[i]; }, [&](int i, T v) { d[i] = v; }); }
-        break;
-      }
-      case M_REDUCE_SET:
-      case M_REDUCE_INC: {   // p0 = partial [i0 chunks][i1 rows_pad]: dst[r] (+)= sum_c partial[c][r], fixed order
-        const T* part = (const T*)op.p0;
-        const int nc = (int)op.i0;
-        for (long long r = tid; r < op.len; r += 1024) {
-          T s = T(0);
-          int c = 0;
-          for (; c + 8 <= nc; c += 8) {            // eight chunk reads in flight, added in chunk order
-            T v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = part[(size_t)(c + q) * op.i1 + r];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s += v[q];
-          }
-          for (; c < nc; ++c) s += part[(size_t)c * op.i1 + r];
-          if (op.kind == M_REDUCE_INC) sig[op.dst + r] += s; else sig[op.dst + r] = s;
-        }
-        break;
-      }
       case M_STEP_END:
         step += 1;
         if (tid == 0) ctx->step = step;
         break;
       default:
+        if (micro_row_kind(op.kind)) {
+          micro_rows<T>(op, sig, walk);
+        } else {
+          micro_elementwise<T>(op, sig, sig, ctx, walk);
+        }
         break;
     }
     SSN_STAMP(pd.op_begin + o);
@@ -1287,43 +1152,21 @@ __global__ __launch_bounds__(1024) void k_program(const MicroOp<T>* __restrict__
 
 // k_vecops: the first level of a timestep's head program when it is long (SLAM config 3: ~100 k elements of resets
 // and hand-offs from the pre stage) - independent element-wise operators, executed grid-wide instead of by the
-// program's single workgroup.
+// program's single workgroup.  (The planner moves no probe here: MK_VECOPS, ssn_host.hip.)
+template <typename T>
+struct GridWalk {
+  long long gtid, gsz, now;
+  template <typename L, typename S>
+  __device__ void operator()(long long len, L load, S store) const { for (long long i = gtid; i < len; i += gsz) store(i, load(i)); }
+  __device__ void overflow() const {}
+  __device__ long long step() const { return now; }
+};
 template <typename T>
 __global__ __launch_bounds__(256) void k_vecops(const MicroOp<T>* __restrict__ ops, int n_ops, T* __restrict__ sig, const StepCtx* __restrict__ ctx) {
-  const long long step = ctx->step;
-  const long long gtid = (long long)blockIdx.x * 256 + threadIdx.x, gsz = (long long)gridDim.x * 256;
+  const GridWalk<T> walk{(long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, ctx->step};
   for (int o = 0; o < n_ops; ++o) {
     const MicroOp<T> op = ops[o];
-    switch (op.kind) {
-      case M_FILL:
-        for (long long i = gtid; i < op.len; i += gsz) sig[op.dst + i] = op.a;
-        break;
-      case M_AXPY_INC:
-        for (long long i = gtid; i < op.len; i += gsz) sig[op.dst + i] += op.a * sig[op.src + i];
-        break;
-      case M_AXPY_SET:
-        for (long long i = gtid; i < op.len; i += gsz) sig[op.dst + i] = op.a * sig[op.src + i];
-        break;
-      case M_LOWPASS:
-        for (long long i = gtid; i < op.len; i += gsz) sig[op.dst + i] = op.a * sig[op.dst + i] + op.b * sig[op.src + i];
-        break;
-      case M_ROW_IN: {
-        const T* row = (const T*)op.p0 + (size_t)(step - ctx->block_start + 1) * op.i0;
-        for (long long i = gtid; i < op.len; i += gsz) sig[op.dst + i] = row[op.i1 + i];
-        break;
-      }
-      case M_TABLE: {
-        const TableSlot* t = (const TableSlot*)op.p0;
-        const long long rel = step - t->first_step;
-        int row = -1;
-        if (rel >= 0 && rel < t->n_idx) row = t->idx[rel];
-        const bool have = row >= 0 && row < t->n_rows;
-        const T* rows = (const T*)t->rows;
-        for (long long i = gtid; i < op.len; i += gsz) sig[op.dst + i] = have ? rows[(size_t)row * t->width + i] : T(0);
-        break;
-      }
-      default: break;
-    }
+    micro_elementwise<T>(op, sig, sig, ctx, walk);
   }
 }
 template <typename T>
@@ -1882,34 +1725,22 @@ hipError_t launch_voja(hipStream_t s, T* E, const T* spk, const T* key, const T*
 // block_start + r).  A per-step GEMV becomes one GEMM (the matrix is read once per block), a Lowpass
 // becomes a scan along time.
 // ---------------------------------------------------------------------------------------------
-// element i of row t (the signals after step block_start + t) of one element-wise operator
+// element i of row t (the signals after step block_start + t) of one element-wise operator: micro_elementwise on the rows
+// written and read, for that one element.  (A batched probe sample that finds no slot is dropped, not reported.)
+template <typename I>
+struct OneElement {
+  I i;
+  long long now;
+  template <typename L, typename S>
+  __device__ void operator()(long long, L load, S store) const { store(i, load(i)); }
+  __device__ void overflow() const {}
+  __device__ long long step() const { return now; }
+};
 template <typename T>
 __device__ inline void kb_elementwise_at(const BatchOp<T>& o, long long t, long long i) {
   T* drow = o.bsig + (size_t)(t + 1) * o.n_sig;
   const T* srow = o.bsig + (size_t)(t + 1 - o.src_prev) * o.n_sig;
-  switch (o.kind) {
-    case M_FILL: drow[o.dst + i] = o.a; break;
-    case M_AXPY_INC: drow[o.dst + i] += o.a * srow[o.src + i]; break;
-    case M_AXPY_SET: drow[o.dst + i] = o.a * srow[o.src + i]; break;
-    case M_TABLE: {
-      const TableSlot* tb = (const TableSlot*)o.p0;
-      const long long rel = o.step0 + t - tb->first_step;
-      int row = -1;
-      if (rel >= 0 && rel < tb->n_idx) row = tb->idx[rel];
-      drow[o.dst + i] = (row >= 0 && row < tb->n_rows) ? ((const T*)tb->rows)[(size_t)row * tb->width + i] : T(0);
-      break;
-    }
-    case M_PROBE: {
-      const ProbeSlot* ps = (const ProbeSlot*)o.p0;
-      const long long s1 = o.step0 + t + 1;
-      if (s1 % ps->every == 0) {
-        const long long slot = s1 / ps->every - 1 - ps->base_slot;
-        if (slot >= 0 && slot < ps->capacity) ((T*)ps->data)[(size_t)slot * o.len + i] = drow[o.src + i];
-      }
-      break;
-    }
-    default: break;
-  }
+  micro_elementwise<T>(o, drow, srow, nullptr, OneElement<long long>{i, o.step0 + t});
 }
 template <typename T>
 __device__ inline void kb_elementwise_body(const BatchOp<T>& o) {

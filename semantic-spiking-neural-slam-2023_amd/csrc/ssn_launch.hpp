@@ -206,6 +206,11 @@ enum MicroKind {
   M_LINCOMB            // dst = a * dst + b * (c + sum_k alpha_k * sig[src_k + i]); p0 = LinTerm[i0]
 };
 template <typename T> struct LinTerm { long long src; T alpha; };
+// Row kinds: one thread computes one output row (micro_row, ssn_micro.hpp), so a block of the round kernel takes GLUE_ROWS rows
+// of them where it takes GLUE_CHUNK elements of an element-wise kind.  Kernels and planner (MK_GLUE_ROW) both ask here.
+constexpr bool micro_row_kind(int kind) {
+  return kind == M_MATVEC_INC || kind == M_MATVEC_SET || kind == M_ENS_FINISH || kind == M_REDUCE_SET || kind == M_REDUCE_INC;
+}
 
 template <typename T>
 struct MicroOp {

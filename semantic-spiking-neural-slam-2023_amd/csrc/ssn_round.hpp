@@ -10,8 +10,11 @@
 //
 //   RK_GLUE     one chunk (GLUE_CHUNK elements / GLUE_ROWS reduction rows) of one micro-operator: fill, axpy, lowpass,
 //               table row, block-row hand-off, probe sample, partial-sum reductions, step counter.  The single-workgroup
-//               interpreter k_program ran these back to back (~0.4 us each, latency-bound); here they run side by side.
-//   RK_GATE, RK_ARGMAX   whole-vector micro-operators (a dot product / an argmax decide what is written): one block
+//               interpreter k_program runs these back to back (~0.4 us each, latency-bound); here they run side by side.
+//               What a kind computes is written once, in ssn_micro.hpp, for k_program, k_vecops, the time-batched stages and
+//               this kernel alike: glue_body below only supplies the walk over one chunk (GlueWalk).
+//   RK_GATE, RK_ARGMAX   whole-vector micro-operators (a dot product / an argmax decide what is written): one block;
+//               micro_gate / micro_argmax_gather of ssn_micro.hpp at 256 threads
 //   RK_MATVEC_*, RK_SPMV, RK_NEURONS, RK_DFT, RK_PES, RK_VOJA   the bodies of the stand-alone kernels (ssn_kernels.hpp)
 //   RK_ENS_*    k_ensarray's body for the variants a SLAM network uses: the path integrator's oscillators (3 inputs, 4 or 5
 //               decoded rows, spike-sparse decoders) and the product ensembles of the circular convolutions (1-D)
@@ -23,229 +26,51 @@
 
 namespace ssn {
 
-// One chunk of one micro-operator.  Element-wise kinds: elements [chunk * GLUE_CHUNK, ...) - four per thread,
-// loads before stores; row kinds (reductions, ensemble finish, small matvec): rows [chunk * GLUE_ROWS, ...), one per thread.
+// The walks of a 256-thread block (ssn_micro.hpp brings what the operators compute).  GlueWalk, one chunk of an operator:
+// U elements per thread from chunk * 256 U, loads before stores, or row chunk * GLUE_ROWS + tid; chunk 0 reports a probe overflow.
+template <typename T, int U>
+struct GlueWalk {
+  int chunk, tid, sub;
+  StepCtx* ctx;
+  template <typename L, typename S>
+  __device__ void operator()(long long len, L load, S store) const {
+    const long long base = (long long)chunk * (U * 256);
+    T v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) { const long long i = base + u * 256 + tid; if (i < len) v[u] = load(i); }
+#pragma unroll
+    for (int u = 0; u < U; ++u) { const long long i = base + u * 256 + tid; if (i < len) store(i, v[u]); }
+  }
+  template <typename R>
+  __device__ void rows(long long len, R row) const { const long long r = (long long)chunk * GLUE_ROWS + tid; if (r < len) row(r); }
+  __device__ void overflow() const { if (tid == 0 && chunk == 0) ctx->probe_overflow = 1; }
+  __device__ long long step() const { return ctx->step + sub; }
+};
+// the whole vector, one element per thread and trip (the row copy of the argmax)
+struct BlockWalk {
+  template <typename L, typename S>
+  __device__ void operator()(long long len, L load, S store) const { for (long long i = threadIdx.x; i < len; i += 256) store(i, load(i)); }
+};
+
+// One chunk of one micro-operator.  Element-wise kinds: elements [chunk * GLUE_CHUNK, ...) - four per thread; row kinds
+// (micro_row_kind: reductions, ensemble finish, small matvec): rows [chunk * GLUE_ROWS, ...), one per thread.
 template <typename T, bool ROWS = false>
 __device__ __forceinline__ void glue_body(const MicroOp<T>& op, const int chunk, const int sub, T* sig, StepCtx* __restrict__ ctx) {
   // sub: timestep offset of this instance inside a pipelined launch sequence (the clock advances once per sequence)
   // ROWS: member of a chain - element-wise kinds handle element chunk * GLUE_ROWS + tid only, like the row kinds
   const int tid = threadIdx.x;
   constexpr int U = ROWS ? 1 : 4;
-  auto ew = [&](auto load, auto store) {
-    const long long base = (long long)chunk * (ROWS ? GLUE_ROWS : GLUE_CHUNK);
-    T v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) { const long long i = base + u * 256 + tid; if (i < op.len) v[u] = load(i); }
-#pragma unroll
-    for (int u = 0; u < U; ++u) { const long long i = base + u * 256 + tid; if (i < op.len) store(i, v[u]); }
-  };
-  switch (op.kind) {
-    case M_FILL:
-      { T* const d = sig + op.dst; ew([&](long long) { return op.a; }, [&](long long i, T v) { d[i] = v; }); }
-      break;
-    case M_AXPY_INC:
-      { T* const d = sig + op.dst; const T* const x = sig + op.src;
-        ew([&](long long i) { return d[i] + op.a * x[i]; }, [&](long long i, T v) { d[i] = v; }); }
-      break;
-    case M_AXPY_SET:
-      { T* const d = sig + op.dst; const T* const x = sig + op.src;
-        ew([&](long long i) { return op.a * x[i]; }, [&](long long i, T v) { d[i] = v; }); }
-      break;
-    case M_LOWPASS:
-      { T* const d = sig + op.dst; const T* const x = sig + op.src;
-        ew([&](long long i) { return op.a * d[i] + op.b * x[i]; }, [&](long long i, T v) { d[i] = v; }); }
-      break;
-    case M_LINCOMB: {   // dst = a * dst + b * (c + sum_k alpha_k * sig[src_k + i]); p0 = LinTerm[i0], i1 bits of c
-      const LinTerm<T>* const t = (const LinTerm<T>*)op.p0;
-      const int nt = (int)op.i0;
-      T* const d = sig + op.dst;
-      const long long base = (long long)chunk * (ROWS ? GLUE_ROWS : GLUE_CHUNK);
-      T acc[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc[u] = op.c;
-      for (int k = 0; k < nt; ++k) {
-        const T alpha = t[k].alpha;
-        const T* const x = sig + t[k].src;
-#pragma unroll
-        for (int u = 0; u < U; ++u) { const long long i = base + u * 256 + tid; if (i < op.len) acc[u] += alpha * x[i]; }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long long i = base + u * 256 + tid;
-        if (i < op.len) d[i] = (op.a != T(0) ? op.a * d[i] : T(0)) + op.b * acc[u];
-      }
-      break;
-    }
-    case M_TABLE: {
-      const TableSlot* t = (const TableSlot*)op.p0;
-      const long long rel = ctx->step + sub - t->first_step;
-      int row = -1;
-      if (rel >= 0 && rel < t->n_idx) row = t->idx[rel];
-      const bool have = row >= 0 && row < t->n_rows;
-      const T* const trow = (const T*)t->rows + (have ? (size_t)row * t->width : 0);
-      T* const d = sig + op.dst;
-      ew([&](long long i) { return have ? trow[i] : T(0); }, [&](long long i, T v) { d[i] = v; });
-      break;
-    }
-    case M_ROW_IN: {
-      const T* const x = (const T*)op.p0 + (size_t)(ctx->step + sub - ctx->block_start + 1) * op.i0 + op.i1;
-      T* const d = sig + op.dst;
-      ew([&](long long i) { return x[i]; }, [&](long long i, T v) { d[i] = v; });
-      break;
-    }
-    case M_ROW_OUT: {
-      T* const d = (T*)op.p0 + (size_t)(ctx->step + sub - ctx->block_start + 1) * op.i0 + op.i1;
-      const T* const x = sig + op.src;
-      ew([&](long long i) { return x[i]; }, [&](long long i, T v) { d[i] = v; });
-      break;
-    }
-    case M_PROBE: {
-      const ProbeSlot* ps = (const ProbeSlot*)op.p0;
-      const long long s1 = ctx->step + sub + 1;
-      if (s1 % ps->every == 0) {
-        const long long slot = s1 / ps->every - 1 - ps->base_slot;
-        if (slot >= 0 && slot < ps->capacity) {
-          T* const out = (T*)ps->data + (size_t)slot * op.len;
-          const T* const x = sig + op.src;
-          ew([&](long long i) { return x[i]; }, [&](long long i, T v) { out[i] = v; });
-        } else if (tid == 0 && chunk == 0) {
-          ctx->probe_overflow = 1;
-        }
-      }
-      break;
-    }
-    case M_MATVEC_INC:
-    case M_MATVEC_SET: {
-      const T* Wm = (const T*)op.p0;
-      const long long r = (long long)chunk * GLUE_ROWS + tid;
-      if (r < op.len) {
-        T s = T(0);
-        for (int c = 0; c < (int)op.i0; ++c) s += Wm[(size_t)r * op.i1 + c] * sig[op.src + c];
-        if (op.kind == M_MATVEC_INC) sig[op.dst + r] += s; else sig[op.dst + r] = s;
-      }
-      break;
-    }
-    case M_ENS_FINISH: {
-      const T* part = (const T*)op.p0;
-      if (op.src > 0) part += (size_t)((ctx->step + sub) & 1) * (size_t)op.src;      // (the array keeps two sets of partial sums, by timestep parity)
-      const int* didx = (const int*)op.p1;
-      const int P = (int)op.i0, dout = (int)op.i1;
-      const long long i = (long long)chunk * GLUE_ROWS + tid;
-      if (i < op.len) {
-        const long long k = i / dout, r = i - k * dout;
-        const int dst = didx[i];                 // (fetched beside the partial sums, not behind them)
-        T s = T(0);
-        int p = 0;
-        for (; p + 8 <= P; p += 8) {             // eight partial sums in flight, added in workgroup order
-          T v[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = part[((size_t)k * P + p + q) * dout + r];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) s += v[q];
-        }
-        {
-          T v[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = p + q < P ? part[((size_t)k * P + p + q) * dout + r] : T(0);
-#pragma unroll
-          for (int q = 0; q < 8; ++q) if (p + q < P) s += v[q];
-        }
-        sig[dst] = s;
-      }
-      break;
-    }
-    case M_REDUCE_SET:
-    case M_REDUCE_INC: {
-      const T* part = (const T*)op.p0;
-      const int nc = (int)op.i0;
-      const long long r = (long long)chunk * GLUE_ROWS + tid;
-      if (r < op.len) {
-        T s = T(0);
-        int c = 0;
-        for (; c + 16 <= nc; c += 16) {          // sixteen chunk reads in flight (a reduction is one of the dependent trips of every
-          T v[16];                               // population hop: 40 chunks are three trips this way, five with eight), added in chunk order
-#pragma unroll
-          for (int q = 0; q < 16; ++q) v[q] = part[(size_t)(c + q) * op.i1 + r];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) s += v[q];
-        }
-        for (; c + 8 <= nc; c += 8) {
-          T v[8];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] = part[(size_t)(c + q) * op.i1 + r];
-#pragma unroll
-          for (int q = 0; q < 8; ++q) s += v[q];
-        }
-        for (; c < nc; ++c) s += part[(size_t)c * op.i1 + r];
-        if (op.kind == M_REDUCE_INC) sig[op.dst + r] += s; else sig[op.dst + r] = s;
-      }
-      break;
-    }
-    case M_STEP_END:
-      if (tid == 0 && chunk == 0) ctx->step = ctx->step + 1;
-      break;
-    default:
-      break;
+  static_assert(GLUE_CHUNK == 4 * 256 && GLUE_ROWS == 256, "a thread takes four elements of a chunk, or one of a chain's");
+  const GlueWalk<T, U> walk{chunk, tid, sub, ctx};
+  if (micro_row_kind(op.kind)) {
+    micro_rows<T>(op, sig, walk);
+  } else if (op.kind == M_LINCOMB) {
+    micro_lincomb<T, U>(op, sig, (long long)chunk * (U * 256) + tid, (long long)256);
+  } else if (op.kind == M_STEP_END) {
+    if (tid == 0 && chunk == 0) ctx->step = ctx->step + 1;
+  } else {
+    micro_elementwise<T>(op, sig, sig, ctx, walk);
   }
-}
-
-// GATE (reference slam.py:236-257's loop-closure correction): dst = open ? rate * (est - cur) : 0, open when the two
-// d-vectors agree (dot product above the threshold) and the flag input is 0.
-template <typename T>
-__device__ __forceinline__ void gate_body(const MicroOp<T>& op, T* __restrict__ sig, unsigned char* smem) {
-  T* sred = reinterpret_cast<T*>(smem);
-  const int tid = threadIdx.x;
-  T part = T(0);
-  for (long long i = tid; i < op.len; i += 256) part += sig[op.src + i] * sig[op.src + op.len + i];
-  part = wave_sum(part);
-  if ((tid & 63) == 0) sred[tid >> 6] = part;
-  __syncthreads();
-  const T dot = ((sred[0] + sred[1]) + sred[2]) + sred[3];
-  const T flag = sig[op.src + 2 * op.len];
-  const bool open = (flag <= T(1e-3) && flag >= T(-1e-3)) && dot > op.a;
-  for (long long i = tid; i < op.len; i += 256)
-    sig[op.dst + i] = open ? op.b * (sig[op.src + i] - sig[op.src + op.len + i]) : T(0);
-}
-
-// ARGMAX + row gather of the clean-up memory: dst = table[first argmax of sims]
-template <typename T>
-__device__ __forceinline__ void argmax_gather_body(const MicroOp<T>& op, T* __restrict__ sig, unsigned char* smem) {
-  T* sred = reinterpret_cast<T*>(smem);
-  int* sidx = reinterpret_cast<int*>(smem + 4 * sizeof(T));
-  const int tid = threadIdx.x;
-  T best = T(-INFINITY);
-  int bi = 0x7fffffff;
-  const T* sims = (const T*)op.p1;
-  const int n_cand = op.src > 0 ? (int)op.src : (int)op.i0;
-  const int* cand_idx = op.src > 0 ? (const int*)(sims + op.src) : nullptr;
-  for (int i0 = tid; i0 < n_cand; i0 += 2048) {       // eight reads in flight, examined in ascending order
-    T v[8];
-    int vi[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + u * 256;
-      v[u] = i < n_cand ? sims[i] : T(-INFINITY);
-      vi[u] = (cand_idx && i < n_cand) ? cand_idx[i] : i;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (v[u] > best) { best = v[u]; bi = vi[u]; }     // first maximum within a thread (ascending i)
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const T ov = __shfl_down(best, off, 64);
-    const int oi = __shfl_down(bi, off, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if ((tid & 63) == 0) { sred[tid >> 6] = best; sidx[tid >> 6] = bi; }
-  __syncthreads();
-  best = sred[0]; bi = sidx[0];
-  for (int w = 1; w < 4; ++w)
-    if (sred[w] > best || (sred[w] == best && sidx[w] < bi)) { best = sred[w]; bi = sidx[w]; }
-  if (bi == 0x7fffffff) bi = 0;
-  const T* const trow = (const T*)op.p0 + (size_t)bi * op.i1;
-  T* const d = sig + op.dst;
-  for (long long i = tid; i < op.len; i += 256) d[i] = trow[i];
 }
 
 // A serial chain (RK_SOLO): single-workgroup units in program order, a workgroup barrier between them.  At most one transform
@@ -277,10 +102,10 @@ __device__ __forceinline__ void solo_body(const RoundArgs<T>& ra, const int* __r
       const int sub = __builtin_amdgcn_readfirstlane(s_tab[2 * q + 1]);
       if (q) __syncthreads();
       const MicroOp<T>& op = reinterpret_cast<const MicroOp<T>*>(s_ops)[q];
-      if (op.kind == M_GATE) gate_body<T>(op, ra.sig, smem);
-      else if (op.kind == M_ARGMAX_GATHER) argmax_gather_body<T>(op, ra.sig, smem);
+      if (op.kind == M_GATE) micro_gate<T, 256>(op, ra.sig, smem);
+      else if (op.kind == M_ARGMAX_GATHER) micro_argmax_gather<T, 256, 8>(op, ra.sig, smem, BlockWalk{});
       else {
-        const bool rows = op.kind == M_MATVEC_INC || op.kind == M_MATVEC_SET || op.kind == M_ENS_FINISH || op.kind == M_REDUCE_SET || op.kind == M_REDUCE_INC;
+        const bool rows = micro_row_kind(op.kind);
         const int chunks = (int)((op.len + (rows ? GLUE_ROWS : GLUE_CHUNK) - 1) / (rows ? GLUE_ROWS : GLUE_CHUNK));
 #pragma unroll 1
         for (int c = 0; c < chunks; ++c) glue_body<T>(op, c, sub, ra.sig, ra.ctx);
@@ -324,8 +149,8 @@ __device__ __forceinline__ void round_block(const RoundArgs<T>& ra, int vb, unsi
       break;
     }
     case RK_SOLO: solo_body<T>(ra, (const int*)e.args, smem); break;
-    case RK_GATE: gate_body<T>(*(const MicroOp<T>*)e.args, ra.sig, smem); break;
-    case RK_ARGMAX: argmax_gather_body<T>(*(const MicroOp<T>*)e.args, ra.sig, smem); break;
+    case RK_GATE: micro_gate<T, 256>(*(const MicroOp<T>*)e.args, ra.sig, smem); break;
+    case RK_ARGMAX: micro_argmax_gather<T, 256, 8>(*(const MicroOp<T>*)e.args, ra.sig, smem, BlockWalk{}); break;
     case RK_MATVEC_R1: matvec_body<T, true, 1, 4>(*(const MatvecArgs<T>*)e.args, bx, smem); break;
     // (one copy of the 16-rows-per-workgroup product for both: a plain product's descriptor has nr.V == nullptr)
     case RK_MATVEC_R4: case RK_MATVEC_NEURONS: matvec_neurons_body<T>(*(const MatvecNeuronsArgs<T>*)e.args, bx, smem); break;

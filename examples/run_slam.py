@@ -13,7 +13,10 @@ is read back.  ``--map-every SECONDS`` also watches the map being learned: a ``M
 similarity maps over the N x N sample grid at every map sample (``harness.similarity_frames``; ``k_decode_map`` on the GPU with
 ``--decode-backend hip``): ``sim_grid`` of the probed trajectory (squared, raw rows) and ``landmark_sim_grid`` of the recalled
 frames (normalised, squared; a landmark not seen yet gives a zero map where the reference's ``q / norm`` gives NaN), written with
-``--save`` to ``<result file minus .npz>_maps.npz``; the map seconds are printed next to the decode seconds.
+``--save`` to ``<result file minus .npz>_maps.npz``; the map seconds are printed next to the decode seconds.  ``--inverse-memory``
+learns the inverse map beside the SLAM network (landmark SSP -> landmark SP, ``slam_map_new.py:243-250``) and ``--area-query X0 X1 Y0
+Y1`` (repeatable) asks it which landmarks lie in a box: ``harness.area_query``, the script's ``get_sims_for_area`` with the mesh sum
+in closed form (``SSPSpace.encode_region``) and the recall on the GPU.
 """
 import argparse
 import os
@@ -68,6 +71,11 @@ def parse(argv=None):
                    help="with --map-every: similarity maps over the N x ... x N sample grid at every map sample - sim_grid of the "
                         "probed trajectory (squared, raw rows) and landmark_sim_grid of the MapProbe frames (normalised, squared), "
                         "made by --decode-backend; with --save written to <result>_maps.npz")
+    p.add_argument("--inverse-memory", action="store_true",
+                   help="learn the inverse memory (landmark SSP -> landmark SP) beside the SLAM network, as slam_map_new.py does")
+    p.add_argument("--area-query", action="append", nargs="+", type=float, default=None, metavar="LO HI",
+                   help="with --inverse-memory: X0 X1 Y0 Y1 (lo hi per axis) of a box; prints every landmark's similarity to the recall "
+                        "of the box's region SSP beside whether the landmark lies in it.  Repeatable")
     return p.parse_args(argv)
 
 
@@ -76,6 +84,10 @@ def main(argv=None):
     dt = 0.001
     if args.save_maps > 0 and not args.map_every > 0:
         raise SystemExit("--save-maps needs --map-every: the maps are made at the map samples")
+    if args.area_query and not args.inverse_memory:
+        raise SystemExit("--area-query needs --inverse-memory: the boxes are recalled through the inverse memory")
+    if args.area_query and any(len(b) != 2 * args.domain_dim for b in args.area_query):
+        raise SystemExit("--area-query takes lo hi per axis: %d numbers" % (2 * args.domain_dim))
     if args.path_data is None:
         T = args.T
         path, vels = H.make_random_path(T, dt=dt, limit=args.limit, seed=args.seed, domain_dim=args.domain_dim)
@@ -88,6 +100,16 @@ def main(argv=None):
                            mem_n_neurons=args.mem_n_neurons, circonv_n_neurons=args.circonv_n_neurons, view_rad=args.view_rad,
                            update_thres=args.update_thres, shift_rate=args.shift_rate, seed=args.seed, dt=dt,
                            weights_sample_every=None if args.decode_backend == "hip" else T)
+    inv_memory = None
+    if args.inverse_memory:      # slam_map_new.py:243-250: keyed by the landmark's SSP, valued by its SP, gated by the in-view node
+        from sspslam_amd.networks import AssociativeMemory
+        d = space.ssp_dim
+        with sm.model:
+            inv_memory = AssociativeMemory(args.mem_n_neurons, d, d, 0.1, voja_learning_rate=5e-4, pes_learning_rate=1e-2, voja=True,
+                                           encoders=space.sample_grid_encoders(args.mem_n_neurons), radius=1.3, seed=args.seed)
+            nengo.Connection(sm.slam.landmark_ssp_ens.output, inv_memory.key_input, synapse=0.05)
+            nengo.Connection(sm.slam.landmark_id_input, inv_memory.value_input, synapse=None)
+            nengo.Connection(sm.slam.no_landmark_in_view, inv_memory.learning, synapse=None)
     map_probe = None
     if args.map_every > 0:
         with sm.model:
@@ -109,6 +131,14 @@ def main(argv=None):
         frames = sim.data[map_probe] if map_probe is not None else None
         map_ts = sim.trange(sample_every=args.map_every) if map_probe is not None else None
         recall_time, recall_kernel_ms = sim.recall_seconds, sim.recall_kernel_ms
+        if args.area_query:
+            boxes = np.asarray(args.area_query, dtype=float).reshape(len(args.area_query), space.domain_dim, 2)
+            backend = "hip" if dtype == "f32" else "hip-f64"
+            t0 = time.time()
+            space.encode_region(boxes, samples=20, normalize=True, backend=backend)
+            area_encode = time.time() - t0
+            area_sims = H.area_query(sim, inv_memory, space, boxes, sm.lm_space.vectors, samples=20, backend=backend)
+            area_time = time.time() - t0 - area_encode
     n = out.shape[0]
     t0 = time.time()
     real_ssp, table = sm.real_ssp[:n], args.decode_table or "host"
@@ -152,6 +182,15 @@ def main(argv=None):
           "%.4f, final position error %.4f; recalled landmark positions: median error %.3f" % (
               space.ssp_dim, T, build_time, elapsed, T / elapsed, decode_time, args.decode_backend, sims[min(200, n - 1):].mean(),
               err[-1], float(np.median(lm_err))))
+    if args.area_query:
+        print("area queries: %d boxes, region encode %.4f s (%s, the first call makes the encoder); harness.area_query - encode, recall "
+              "through the inverse memory on the GPU, compare - %.4f s" % (
+            len(boxes), area_encode, backend, area_time))
+        for box, row in zip(boxes, area_sims):
+            inside = np.all((sm.obj_locs >= box[:, 0]) & (sm.obj_locs <= box[:, 1]), axis=1)
+            print("  box %s: %s" % (" x ".join("[%g, %g]" % tuple(ax) for ax in box),
+                                    "  ".join("%d%s %+.3f" % (j, "*" if inside[j] else "", row[j]) for j in range(len(row)))))
+        print("  (* the landmark lies in the box)")
     if args.decode_refine:
         t0 = time.time()
         _, _, err_r = H.pathint_metrics(space, out, real_ssp, path[:n], backend=args.decode_backend, refine=True, table=table)

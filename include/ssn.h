@@ -475,6 +475,27 @@ int ssn_encoder_encode(ssn_encoder* enc, const double* points, int64_t n, double
 int ssn_encoder_encode_device(ssn_encoder* enc, const void* points, int32_t points_on_device, int32_t points_dtype, int64_t points_ld,
                               int64_t n, void* out_dev, int64_t out_ld);
 int ssn_encoder_get_info(ssn_encoder* enc, int64_t n, ssn_encoder_info* out);
+/* Region SSPs (additive to ABI 11): the SSP of an axis-aligned box in closed form.  A box row is lo_0, hi_0, lo_1,
+ * hi_1, ... (2 dim values, the layout of domain_bounds).  With centre c, side lengths L and th_k = M_k . c, bin k of the box is
+ * encode(c)'s bin times a real amplitude A_k, so a region is the same product on [A cos th, A sin th]:
+ *   samples == NULL, mean == 0   the integral of encode over the box:  A_k = prod_a L_a sinc(M_ka L_a / 2),  sinc(y) = sin(y) / y
+ *   samples == NULL, mean != 0   its mean (no L_a): a zero-width axis contributes 1, a zero-width box is encode(c) bit for bit
+ *   samples (dim counts >= 2)    the sum of encode over the linspace mesh of samples[a] points per axis, both ends included:
+ *                                A_k = prod_a sin(n_a y_a) / sin(y_a),  y_a = M_ka L_a / (2 (n_a - 1))
+ * th, the amplitude and the sincos are float64 in both dtypes, the removable singularities (y = 0, which bin 0 of every box hits, and
+ * y_a at a multiple of pi) go to their series below fixed thresholds; the product, the chunks and the determinism are those of the point
+ * calls.  The box calls stage 2 dim doubles per row, so they need min_scratch_bytes + 64 * 8 * dim bytes of scratch.
+ * ssn_encoder_encode_boxes: n x 2 dim host doubles (dense) -> n x d host doubles.
+ * ssn_encoder_encode_boxes_device: boxes on the host or on the encoder's device, boxes_dtype SSN_F32 / SSN_F64, leading dimension
+ * boxes_ld >= 2 dim -> a device buffer of the encoder's dtype with leading dimension out_ld >= d; normalize != 0 divides every row by
+ * max(its norm, 1e-8) on the device (the sum of squares in float64, in a fixed order).
+ * SSN_EINVAL beyond the point calls': "hi < lo" for a box with a negative side, "below 2" for a mesh count under 2, "mean given
+ * together with samples", "too small for one 64-box tile" with the bytes needed. */
+int ssn_encoder_encode_boxes(ssn_encoder* enc, const double* boxes, int64_t n, const int32_t* samples /* NULL: no mesh */, int32_t mean,
+                             double* out);
+int ssn_encoder_encode_boxes_device(ssn_encoder* enc, const void* boxes, int32_t boxes_on_device, int32_t boxes_dtype, int64_t boxes_ld,
+                                    int64_t n, const int32_t* samples /* NULL: no mesh */, int32_t mean, int32_t normalize, void* out_dev,
+                                    int64_t out_ld);
 /* A decoder whose table is made on the device: the n_samples x dim sample points (host doubles) are encoded by a float64 encoder
  * (d = width, K, dim, M, w as above; enc_scratch_bytes its scratch area, 0 = default) chunk by chunk, each chunk written straight
  * into the decoder's padded table in the decoder's dtype.  The table never exists on the host; device memory peaks at the table

@@ -159,6 +159,9 @@ EXPORTS = {
     "ssn_encoder_destroy": (None, [C.c_void_p]),
     "ssn_encoder_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ssn_encoder_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "ssn_encoder_encode_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ssn_encoder_encode_boxes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                                  C.c_void_p, C.c_int64]),
     "ssn_encoder_get_info": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(EncoderInfo)]),
     "ssn_decoder_create_from_points": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                                  C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),

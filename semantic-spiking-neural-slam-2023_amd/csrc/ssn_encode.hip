@@ -15,6 +15,26 @@
 //                      every entry one fma chain in k order.  Its output type may be float: the float64 entry rounded once.
 //   k_encode_widen     f32 entries to the doubles the host-output call returns.
 //
+// Regions.  The SSP of an axis-aligned box - its integral, its mean, or the sum over a linspace mesh of n_a points
+// per axis (slam_map_new.py:412-416) - is encode(centre)'s bin k times a real amplitude A_k(box), so a region is the same product on
+// P = [A cos th, A sin th]:
+//   integral  A_k = prod_a L_a sinc(y_a),  y_a = M_ka L_a / 2           mean  the same without the L_a
+//   mesh      A_k = prod_a sin(n_a y_a) / sin(y_a),  y_a = M_ka L_a / (2 (n_a - 1))
+//   k_encode_phase_box one thread per (box, bin): a box row is lo_0, hi_0, lo_1, hi_1, ...; th_k the same fma chain on
+//                      c_a = 0.5 (lo_a + hi_a), the amplitude and the sincos float64 in both dtypes, (A cos th, A sin th) rounded
+//                      once.  The removable singularities are selected away in float64, never branched on:
+//                        sinc(y)      |y| < 2^-10: 1 - y^2/6 + y^4/120, which leaves y^6/5040 < 2^-72; else sin(y) / y.  Bin 0 has
+//                                     M_0 = 0, so every box takes the series there.
+//                        mesh ratio   y = q pi + r with q = rint(y / pi) and pi in two parts (|r| <= pi/2, the reduction exact to
+//                                     |q| 2^-107), sin(n y) / sin(y) = (-1)^(q (n - 1)) sin(n r) / sin(r).  |r| < 2^-26: sin(r) = r to
+//                                     r^2/6 < 2^-54 relative, and the ratio is n sinc(n r) with the sinc above (at r = 0: +-n); else
+//                                     sin(n r) / sin(r).
+//                      A box with hi_a < lo_a raises a flag word (a plain store of 1 by every thread that sees one).
+//   k_encode_rownorm   one wave per row: sum x^2 in float64, lane l over the columns l, l + 64, ... in order, then a fixed xor butterfly
+//                      (every lane ends with the same bits); the row divided in place by max(norm, 1e-8) - SSPSpace.normalize's
+//                      rule - in float64 and rounded once.  Only for a normalised result that stays on the device.
+// The box path stages 2 dim doubles per row and sizes its own chunks from that; the point path's sizes are untouched.
+//
 // B is made on the host in float64 at creation, the angle reduced exactly ((k c) mod d), and converted once.  Scratch (fixed at
 // creation, default 64 MB): per point dim doubles of staging, Kp values of P, d values of the result and, in f32, d doubles of
 // the widened result.  Points are cut into chunks that fit; an entry never depends on the chunk it is in, and there are no
@@ -60,6 +80,89 @@ __global__ __launch_bounds__(256) void k_encode_phase(const TI* __restrict__ pts
   T* __restrict__ p = P + (size_t)row * Kp + 2 * k;
   p[0] = cs_t;
   p[1] = sn_t;
+}
+
+enum { BOX_INTEGRAL = 0, BOX_MEAN = 1, BOX_MESH = 2 };
+
+__device__ __forceinline__ double sinc_guarded(double y) {
+  const bool small = fabs(y) < 0x1p-10;
+  const double y2 = y * y;
+  const double series = fma(y2, fma(y2, 1.0 / 120.0, -1.0 / 6.0), 1.0);
+  const double ratio = sin(y) / (small ? 1.0 : y);
+  return small ? series : ratio;
+}
+
+// sin(n y) / sin(y) for an integer n >= 2 held in nd
+__device__ __forceinline__ double dirichlet_guarded(double y, double nd, bool n_even) {
+  constexpr double PI_HI = 0x1.921fb54442d18p+1, PI_LO = 0x1.1a62633145c07p-53, INV_PI = 0x1.45f306dc9c883p-2;
+  const double q = rint(y * INV_PI);
+  const double r = fma(-q, PI_LO, fma(-q, PI_HI, y));
+  const bool small = fabs(r) < 0x1p-26;
+  const double nr = nd * r;
+  const double near = nd * sinc_guarded(nr);
+  const double away = sin(nr) / sin(small ? 1.0 : r);
+  const double v = small ? near : away;
+  const bool q_odd = fmod(fabs(q), 2.0) == 1.0;
+  return (q_odd && n_even) ? -v : v;
+}
+
+// tab: per axis (n_a, 0.5 / (n_a - 1)) for the mesh; unused otherwise
+template <typename TI, typename T>
+__global__ __launch_bounds__(256) void k_encode_phase_box(const TI* __restrict__ boxes, long long ld, int n, int dim, int K, int Kp,
+                                                          const double* __restrict__ M, int mode, const double* __restrict__ tab,
+                                                          int* __restrict__ flag, T* __restrict__ P) {
+  const int half = Kp >> 1;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long row = i / half;
+  if (row >= n) return;
+  const int k = (int)(i - row * half);
+  T cs_t = T(0), sn_t = T(0);
+  if (k < K) {
+    const TI* __restrict__ b = boxes + (size_t)row * ld;
+    const double* __restrict__ m = M + (size_t)k * dim;
+    double th = 0.0, amp = 1.0;
+    bool bad = false;
+    for (int a = 0; a < dim; ++a) {
+      const double lo = (double)b[2 * a], hi = (double)b[2 * a + 1];
+      const double c = 0.5 * (lo + hi), L = hi - lo;
+      bad |= hi < lo;
+      th = a == 0 ? m[0] * c : fma(m[a], c, th);
+      const double mL = m[a] * L;
+      double f;
+      if (mode == BOX_MESH) {
+        const double nd = tab[2 * a];
+        f = dirichlet_guarded(mL * tab[2 * a + 1], nd, fmod(nd, 2.0) == 0.0);
+      } else {
+        f = sinc_guarded(0.5 * mL);
+        if (mode == BOX_INTEGRAL) f *= L;
+      }
+      amp *= f;
+    }
+    if (bad) *flag = 1;
+    double sn, cs;
+    sincos(th, &sn, &cs);
+    cs_t = (T)(amp * cs);
+    sn_t = (T)(amp * sn);
+  }
+  T* __restrict__ p = P + (size_t)row * Kp + 2 * k;
+  p[0] = cs_t;
+  p[1] = sn_t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_encode_rownorm(T* __restrict__ X, long long ld, int n, int d) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= n) return;      // a whole wave at a time
+  T* __restrict__ x = X + (size_t)row * ld;
+  double s = 0.0;
+  for (int c = lane; c < d; c += 64) {
+    const double v = (double)x[c];
+    s = fma(v, v, s);
+  }
+  for (int w = 32; w >= 1; w >>= 1) s += __shfl_xor(s, w, 64);
+  const double nrm = fmax(sqrt(s), 1e-8);
+  for (int c = lane; c < d; c += 64) x[c] = (T)((double)x[c] / nrm);
 }
 
 template <typename TO>
@@ -135,6 +238,16 @@ struct ssn_encoder {
     tiles = std::min<int64_t>(tiles, std::max<int64_t>(1, ((int64_t)1 << 30) / (ROWS * widest)));
     return std::min<int64_t>(tiles, 1 << 15) * ROWS;
   }
+  // the box path: 2 dim doubles of staging per row in place of dim
+  double* box_tab = nullptr;       // per axis (n_a, 0.5 / (n_a - 1)), then the flag word of k_encode_phase_box; made by the first box call
+  int64_t box_row_bytes() const { return row_bytes() + dim * 8; }
+  int64_t box_min_scratch() const { return ROWS * box_row_bytes(); }
+  int64_t box_chunk_rows() const {
+    int64_t tiles = std::max<int64_t>(1, scratch_bytes / (ROWS * box_row_bytes()));
+    const int64_t widest = std::max(Kp, d);
+    tiles = std::min<int64_t>(tiles, std::max<int64_t>(1, ((int64_t)1 << 30) / (ROWS * widest)));
+    return std::min<int64_t>(tiles, 1 << 15) * ROWS;
+  }
 
   ~ssn_encoder() {
     DevGuard g(device);
@@ -142,17 +255,18 @@ struct ssn_encoder {
     if (stream) (void)hipStreamDestroy(stream);
     if (M) (void)hipFree(M);
     if (B) (void)hipFree(B);
+    if (box_tab) (void)hipFree(box_tab);
     if (scratch) (void)hipFree(scratch);
   }
 };
 
 namespace {
 
-struct Areas {      // the regions of the scratch area for a chunk capacity of `rows` points
+struct Areas {      // the regions of the scratch area for a chunk capacity of `rows` input rows of `width` values
   char* stage; double* wide; void* P; void* out;
-  Areas(const ssn_encoder* e, int64_t rows) {
+  Areas(const ssn_encoder* e, int64_t rows, int64_t width) {
     char* p = e->scratch;
-    stage = p; p += (size_t)rows * e->dim * 8;
+    stage = p; p += (size_t)rows * width * 8;
     wide = (double*)p; if (e->esz == 4) p += (size_t)rows * e->d * 8;
     P = p; p += (size_t)rows * e->Kp * e->esz;
     out = p;
@@ -196,9 +310,40 @@ hipError_t launch_phase(ssn_encoder* e, const TI* pts, int64_t ld, int n, T* P) 
   return hipGetLastError();
 }
 
+template <typename TI, typename T>
+hipError_t launch_phase_box(ssn_encoder* e, int mode, const TI* boxes, int64_t ld, int n, T* P) {
+  const long long total = (long long)n * (e->Kp / 2);
+  hipLaunchKernelGGL((k_encode_phase_box<TI, T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, e->stream, boxes, (long long)ld, n, (int)e->dim,
+                     (int)e->K, (int)e->Kp, (const double*)e->M, mode, (const double*)e->box_tab, (int*)(e->box_tab + 2 * e->dim), P);
+  return hipGetLastError();
+}
+
+// The phase launcher of a call: the rows of a chunk (dtype in_dtype, leading dimension ld, on the device by then) into P of the encoder's dtype.
+struct PointPhase {
+  static constexpr int per_dim = 1;      // values per row and axis
+  hipError_t operator()(ssn_encoder* e, const void* rows, int in_dtype, int64_t ld, int n, void* P) const {
+    if (e->dtype == SSN_F32)
+      return in_dtype == SSN_F32 ? launch_phase<float, float>(e, (const float*)rows, ld, n, (float*)P) : launch_phase<double, float>(e, (const double*)rows, ld, n, (float*)P);
+    return in_dtype == SSN_F32 ? launch_phase<float, double>(e, (const float*)rows, ld, n, (double*)P) : launch_phase<double, double>(e, (const double*)rows, ld, n, (double*)P);
+  }
+};
+
+struct BoxPhase {
+  static constexpr int per_dim = 2;
+  int mode;
+  hipError_t operator()(ssn_encoder* e, const void* rows, int in_dtype, int64_t ld, int n, void* P) const {
+    if (e->dtype == SSN_F32)
+      return in_dtype == SSN_F32 ? launch_phase_box<float, float>(e, mode, (const float*)rows, ld, n, (float*)P)
+                                 : launch_phase_box<double, float>(e, mode, (const double*)rows, ld, n, (float*)P);
+    return in_dtype == SSN_F32 ? launch_phase_box<float, double>(e, mode, (const float*)rows, ld, n, (double*)P)
+                               : launch_phase_box<double, double>(e, mode, (const double*)rows, ld, n, (double*)P);
+  }
+};
+
 template <typename T>
-hipError_t phase_for(ssn_encoder* e, const void* pts, int pts_dtype, int64_t ld, int n, T* P) {
-  return pts_dtype == SSN_F32 ? launch_phase<float, T>(e, (const float*)pts, ld, n, P) : launch_phase<double, T>(e, (const double*)pts, ld, n, P);
+hipError_t launch_rownorm(ssn_encoder* e, T* X, int64_t ld, int n) {
+  hipLaunchKernelGGL((k_encode_rownorm<T>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, e->stream, X, (long long)ld, n, (int)e->d);
+  return hipGetLastError();
 }
 
 template <typename TO>
@@ -208,13 +353,15 @@ hipError_t launch_product64(ssn_encoder* e, const double* P, int n, TO* C, int64
   return hipGetLastError();
 }
 
-// Points: host (on_device == 0) or device rows of pts_dtype with leading dimension pts_ld.  Output: host doubles (dense), or a device
-// buffer of out_dtype with leading dimension out_ld.
-int encode(ssn_encoder* e, const void* pts, int on_device, int pts_dtype, int64_t pts_ld, int64_t n, double* host_out, void* dev_out, int out_dtype,
-           int64_t out_ld) {
+// Rows (points, or boxes with phase.per_dim == 2): host (on_device == 0) or device rows of pts_dtype with leading dimension pts_ld, `cap`
+// of them per chunk, through the phase launcher `phase`.  Output: host doubles (dense), or a device buffer of out_dtype with leading
+// dimension out_ld, its rows scaled to unit length with `normalize`.
+template <typename Phase>
+int encode(ssn_encoder* e, const Phase& phase, int64_t cap, const void* pts, int on_device, int pts_dtype, int64_t pts_ld, int64_t n, double* host_out,
+           void* dev_out, int out_dtype, int64_t out_ld, bool normalize = false) {
   DevGuard g(e->device);
-  const int64_t cap = e->chunk_rows();
-  const Areas a(e, cap);
+  const int64_t width = e->dim * Phase::per_dim;
+  const Areas a(e, cap, width);
   const size_t isz = pts_dtype == SSN_F32 ? 4 : 8, osz = out_dtype == SSN_F32 ? 4 : 8;
   const bool f32 = e->dtype == SSN_F32;
   e->phase_ms = e->product_ms = 0.0;
@@ -224,14 +371,13 @@ int encode(ssn_encoder* e, const void* pts, int on_device, int pts_dtype, int64_
     const void* src = (const char*)pts + (size_t)r0 * pts_ld * isz;
     int64_t ld = pts_ld;
     if (!on_device) {
-      if (pts_ld == e->dim) SVC_HIP(hipMemcpyAsync(a.stage, src, (size_t)m * e->dim * isz, hipMemcpyHostToDevice, e->stream));
-      else SVC_HIP(hipMemcpy2DAsync(a.stage, (size_t)e->dim * isz, src, (size_t)pts_ld * isz, (size_t)e->dim * isz, (size_t)m, hipMemcpyHostToDevice, e->stream));
+      if (pts_ld == width) SVC_HIP(hipMemcpyAsync(a.stage, src, (size_t)m * width * isz, hipMemcpyHostToDevice, e->stream));
+      else SVC_HIP(hipMemcpy2DAsync(a.stage, (size_t)width * isz, src, (size_t)pts_ld * isz, (size_t)width * isz, (size_t)m, hipMemcpyHostToDevice, e->stream));
       src = a.stage;
-      ld = e->dim;
+      ld = width;
     }
     SVC_HIP(hipEventRecord(e->e0, e->stream));
-    if (f32) SVC_HIP(phase_for<float>(e, src, pts_dtype, ld, m, (float*)a.P));
-    else SVC_HIP(phase_for<double>(e, src, pts_dtype, ld, m, (double*)a.P));
+    SVC_HIP(phase(e, src, pts_dtype, ld, m, a.P));
     SVC_HIP(hipEventRecord(e->e1, e->stream));
     e->launches += 2;
     if (f32) {
@@ -251,6 +397,11 @@ int encode(ssn_encoder* e, const void* pts, int on_device, int pts_dtype, int64_
     } else {
       SVC_HIP(launch_product64<float>(e, (const double*)a.P, m, (float*)dev_out + (size_t)r0 * out_ld, out_ld));
     }
+    if (normalize) {
+      if (osz == 4) SVC_HIP(launch_rownorm<float>(e, (float*)dev_out + (size_t)r0 * out_ld, out_ld, m));
+      else SVC_HIP(launch_rownorm<double>(e, (double*)dev_out + (size_t)r0 * out_ld, out_ld, m));
+      e->launches += 1;
+    }
     SVC_HIP(hipEventRecord(e->e2, e->stream));
     if (host_out)
       SVC_HIP(hipMemcpyAsync(host_out + (size_t)r0 * e->d, f32 ? (const void*)a.wide : (const void*)a.out, (size_t)m * e->d * 8, hipMemcpyDeviceToHost, e->stream));
@@ -264,6 +415,50 @@ int encode(ssn_encoder* e, const void* pts, int on_device, int pts_dtype, int64_
   return SSN_OK;
 }
 
+// The amplitude mode of a box call from (samples, mean); named errors for what the two exclude.
+int box_mode(const ssn_encoder* e, const char* who, const int32_t* samples, int32_t mean, int* mode) {
+  if (samples && mean) return fail(SSN_EINVAL, "%s: mean given together with samples (the mean of a mesh is its sum over the number of points)", who);
+  if (samples)
+    for (int64_t a = 0; a < e->dim; ++a)
+      if (samples[a] < 2) return fail(SSN_EINVAL, "%s: samples[%lld] = %d below 2 (a linspace mesh has both ends)", who, (long long)a, samples[a]);
+  *mode = samples ? BOX_MESH : mean ? BOX_MEAN : BOX_INTEGRAL;
+  return SSN_OK;
+}
+
+template <typename TI>
+int64_t first_inverted(const TI* boxes, int64_t ld, int64_t n, int64_t dim) {
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t a = 0; a < dim; ++a)
+      if (boxes[i * ld + 2 * a + 1] < boxes[i * ld + 2 * a]) return i;
+  return -1;
+}
+
+int encode_boxes(ssn_encoder* e, const char* who, int mode, const int32_t* samples, const void* boxes, int on_device, int dtype, int64_t ld, int64_t n,
+                 double* host_out, void* dev_out, int64_t out_ld, bool normalize) {
+  if (e->scratch_bytes < e->box_min_scratch())
+    return fail(SSN_EINVAL, "%s: scratch_bytes %lld too small for one %d-box tile of d %lld, K %lld (%lld bytes)", who, (long long)e->scratch_bytes, ROWS,
+                (long long)e->d, (long long)e->K, (long long)e->box_min_scratch());
+  if (!on_device) {
+    const int64_t bad = dtype == SSN_F32 ? first_inverted((const float*)boxes, ld, n, e->dim) : first_inverted((const double*)boxes, ld, n, e->dim);
+    if (bad >= 0) return fail(SSN_EINVAL, "%s: box %lld has hi < lo on an axis", who, (long long)bad);
+  }
+  DevGuard g(e->device);
+  const size_t tab_bytes = (size_t)(2 * e->dim + 1) * 8;      // the table and, in its last word, the flag
+  if (!e->box_tab) SVC_HIP(hipMalloc((void**)&e->box_tab, tab_bytes));
+  std::vector<double> tab((size_t)(2 * e->dim + 1), 0.0);
+  for (int64_t a = 0; a < e->dim && samples; ++a) {
+    tab[2 * a] = (double)samples[a];
+    tab[2 * a + 1] = 0.5 / (double)(samples[a] - 1);
+  }
+  SVC_HIP(hipMemcpy(e->box_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice));
+  const int rc = encode(e, BoxPhase{mode}, e->box_chunk_rows(), boxes, on_device, dtype, ld, n, host_out, dev_out, e->dtype, out_ld, normalize);
+  if (rc != SSN_OK) return rc;
+  int flag = 0;
+  SVC_HIP(hipMemcpy(&flag, e->box_tab + 2 * e->dim, sizeof flag, hipMemcpyDeviceToHost));
+  if (flag) return fail(SSN_EINVAL, "%s: a box has hi < lo on an axis", who);
+  return SSN_OK;
+}
+
 }  // namespace
 
 namespace ssn {
@@ -272,7 +467,7 @@ int encoder_encode_into(ssn_encoder* enc, const double* points, int64_t n, void*
   if (!enc || !points || !out_dev || n <= 0) return fail(SSN_EINVAL, "encoder_encode_into: null or empty argument");
   if (out_ld < enc->d) return fail(SSN_EINVAL, "encoder_encode_into: leading dimension %lld below the width %lld", (long long)out_ld, (long long)enc->d);
   if (enc->dtype == SSN_F32 && out_dtype != SSN_F32) return fail(SSN_EINVAL, "encoder_encode_into: an f32 encoder writes f32 only");
-  return encode(enc, points, 0, SSN_F64, enc->dim, n, nullptr, out_dev, out_dtype, out_ld);
+  return encode(enc, PointPhase(), enc->chunk_rows(), points, 0, SSN_F64, enc->dim, n, nullptr, out_dev, out_dtype, out_ld);
 }
 
 }  // namespace ssn
@@ -321,7 +516,7 @@ int ssn_encoder_encode(ssn_encoder* enc, const double* points, int64_t n, double
   if (n < 0) return fail(SSN_EINVAL, "ssn_encoder_encode: negative n");
   if (n == 0) return SSN_OK;
   if (!points || !out) return fail(SSN_EINVAL, "ssn_encoder_encode: null argument");
-  return encode(enc, points, 0, SSN_F64, enc->dim, n, out, nullptr, SSN_F64, enc->d);
+  return encode(enc, PointPhase(), enc->chunk_rows(), points, 0, SSN_F64, enc->dim, n, out, nullptr, SSN_F64, enc->d);
 }
 
 int ssn_encoder_encode_device(ssn_encoder* enc, const void* points, int32_t points_on_device, int32_t points_dtype, int64_t points_ld, int64_t n,
@@ -335,7 +530,35 @@ int ssn_encoder_encode_device(ssn_encoder* enc, const void* points, int32_t poin
   if (out_ld > INT32_MAX) return fail(SSN_EINVAL, "ssn_encoder_encode_device: leading dimension %lld of the output above 2^31 - 1", (long long)out_ld);
   if (n == 0) return SSN_OK;
   if (!points || !out_dev) return fail(SSN_EINVAL, "ssn_encoder_encode_device: null argument");
-  return encode(enc, points, points_on_device != 0, points_dtype, points_ld, n, nullptr, out_dev, enc->dtype, out_ld);
+  return encode(enc, PointPhase(), enc->chunk_rows(), points, points_on_device != 0, points_dtype, points_ld, n, nullptr, out_dev, enc->dtype, out_ld);
+}
+
+int ssn_encoder_encode_boxes(ssn_encoder* enc, const double* boxes, int64_t n, const int32_t* samples, int32_t mean, double* out) {
+  const char* who = "ssn_encoder_encode_boxes";
+  if (!enc) return fail(SSN_EINVAL, "%s: null encoder", who);
+  if (n < 0) return fail(SSN_EINVAL, "%s: negative n", who);
+  int mode = 0;
+  if (const int rc = box_mode(enc, who, samples, mean, &mode)) return rc;
+  if (n == 0) return SSN_OK;
+  if (!boxes || !out) return fail(SSN_EINVAL, "%s: null argument", who);
+  return encode_boxes(enc, who, mode, samples, boxes, 0, SSN_F64, 2 * enc->dim, n, out, nullptr, enc->d, false);
+}
+
+int ssn_encoder_encode_boxes_device(ssn_encoder* enc, const void* boxes, int32_t boxes_on_device, int32_t boxes_dtype, int64_t boxes_ld, int64_t n,
+                                    const int32_t* samples, int32_t mean, int32_t normalize, void* out_dev, int64_t out_ld) {
+  const char* who = "ssn_encoder_encode_boxes_device";
+  if (!enc) return fail(SSN_EINVAL, "%s: null encoder", who);
+  if (n < 0) return fail(SSN_EINVAL, "%s: negative n", who);
+  if (boxes_dtype != SSN_F32 && boxes_dtype != SSN_F64) return fail(SSN_EINVAL, "%s: unknown boxes_dtype %d", who, boxes_dtype);
+  if (boxes_ld < 2 * enc->dim)
+    return fail(SSN_EINVAL, "%s: leading dimension %lld of the boxes below 2 dim = %lld", who, (long long)boxes_ld, (long long)(2 * enc->dim));
+  if (out_ld < enc->d) return fail(SSN_EINVAL, "%s: leading dimension %lld of the output below the width %lld", who, (long long)out_ld, (long long)enc->d);
+  if (out_ld > INT32_MAX) return fail(SSN_EINVAL, "%s: leading dimension %lld of the output above 2^31 - 1", who, (long long)out_ld);
+  int mode = 0;
+  if (const int rc = box_mode(enc, who, samples, mean, &mode)) return rc;
+  if (n == 0) return SSN_OK;
+  if (!boxes || !out_dev) return fail(SSN_EINVAL, "%s: null argument", who);
+  return encode_boxes(enc, who, mode, samples, boxes, boxes_on_device != 0, boxes_dtype, boxes_ld, n, nullptr, out_dev, out_ld, normalize != 0);
 }
 
 int ssn_encoder_get_info(ssn_encoder* enc, int64_t n, ssn_encoder_info* out) {

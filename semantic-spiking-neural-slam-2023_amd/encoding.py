@@ -100,32 +100,54 @@ class SSPEncoder:
     def _points_arg(self, x):
         """(points, n, (pointer, on_device, dtype code, leading dimension)): host points as a C-contiguous float32 / float64 array,
         device tensors as they are."""
+        return self._rows_arg(x, self.dim, "points")
+
+    def _boxes_arg(self, boxes):
+        """``_points_arg`` for boxes ``(N, dim, 2)`` (or one ``(dim, 2)``): rows of ``lo_0, hi_0, lo_1, hi_1, ...``; a device tensor
+        whose last two axes are dense is read in place, whatever its row stride."""
+        tensor = hasattr(boxes, "is_cuda") and hasattr(boxes, "data_ptr")
+        if not tensor:
+            boxes = np.asarray(boxes)
+            if boxes.dtype != np.float32:
+                boxes = boxes.astype(np.float64)
+        if boxes.ndim == 2:
+            boxes = boxes[None]
+        if boxes.ndim != 3 or tuple(boxes.shape[1:]) != (self.dim, 2):
+            raise ValueError(f"boxes must be (N, {self.dim}, 2), got {tuple(boxes.shape)}")
+        n = int(boxes.shape[0])
+        if tensor and boxes.is_cuda and n > 1 and boxes.stride(2) == 1 and boxes.stride(1) == 2 and boxes.stride(0) >= 2 * self.dim:
+            flat = boxes.as_strided((n, 2 * self.dim), (boxes.stride(0), 1))
+        else:
+            flat = boxes.reshape(n, 2 * self.dim)
+        return self._rows_arg(flat, 2 * self.dim, "boxes")
+
+    def _rows_arg(self, x, width, what):
         tensor = hasattr(x, "is_cuda") and hasattr(x, "data_ptr")
         if tensor and not x.is_cuda:
             x, tensor = x.detach().numpy(), False
         if tensor:
             import torch
             if x.device.index != self.device:
-                raise ValueError(f"points live on {x.device}, the encoder on device {self.device}")
+                raise ValueError(f"{what} live on {x.device}, the encoder on device {self.device}")
             x = x.detach()
             if x.dim() == 1:
                 x = x[None, :]
             if x.dtype not in (torch.float32, torch.float64):
                 x = x.to(torch.float64)
-            if x.dim() != 2 or x.shape[1] != self.dim:
-                raise ValueError(f"points must be (N, {self.dim}), got {tuple(x.shape)}")
+            if x.dim() != 2 or x.shape[1] != width:
+                raise ValueError(f"{what} must be (N, {width}), got {tuple(x.shape)}")
             n = int(x.shape[0])
-            if x.stride(1) != 1 or (n > 1 and x.stride(0) < self.dim):
+            if x.stride(1) != 1 or (n > 1 and x.stride(0) < width):
                 x = x.contiguous()
-            ld = max(int(x.stride(0)), self.dim) if n > 1 else self.dim
-            torch.cuda.current_stream(x.device).synchronize()          # the points are complete before the encoder's stream reads them
+            ld = max(int(x.stride(0)), width) if n > 1 else width
+            torch.cuda.current_stream(x.device).synchronize()          # the rows are complete before the encoder's stream reads them
             return x, n, (x.data_ptr() if n else None, 1, _lib.SSN_F32 if x.dtype == torch.float32 else _lib.SSN_F64, ld)
         x = np.atleast_2d(np.asarray(x))
         x = np.ascontiguousarray(x, dtype=np.float32 if x.dtype == np.float32 else np.float64)
-        if x.ndim != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"points must be (N, {self.dim}), got {x.shape}")
+        if x.ndim != 2 or x.shape[1] != width:
+            raise ValueError(f"{what} must be (N, {width}), got {x.shape}")
         n = int(x.shape[0])
-        return x, n, (x.ctypes.data if n else None, 0, _lib.SSN_F32 if x.dtype == np.float32 else _lib.SSN_F64, self.dim)
+        return x, n, (x.ctypes.data if n else None, 0, _lib.SSN_F32 if x.dtype == np.float32 else _lib.SSN_F64, width)
 
     def encode(self, x, out="host"):
         """SSPs of the points ``x``: array-like ``(N, dim)`` (or one point), or a torch tensor on the encoder's device (float32 /
@@ -145,3 +167,58 @@ class SSPEncoder:
         torch.cuda.current_stream(res.device).synchronize()
         self._check(self._lib.ssn_encoder_encode_device(self._h, ptr, on_device, code, ld, n, res.data_ptr() if n else None, self.width))
         return res if out == "device" else res.cpu().to(torch.float64).numpy()
+
+    @property
+    def region_min_scratch(self):
+        """The smallest ``scratch_bytes`` ``encode_region`` accepts: one 64-box tile (a box row stages ``2 dim`` doubles)."""
+        return int(self.info()["min_scratch_bytes"]) + 64 * 8 * self.dim
+
+    def encode_region(self, boxes, samples=None, mean=False, normalize=False, out="host"):
+        """SSPs of axis-aligned boxes in closed form (``k_encode_phase_box``).  ``boxes``: ``(N, dim, 2)`` rows of
+        ``[lo, hi]`` per axis (the layout of ``domain_bounds``) or one ``(dim, 2)``, array-like or a torch tensor on the encoder's
+        device.  ``samples=None``: the integral of ``encode`` over each box, or with ``mean=True`` its mean (a zero-width box is then
+        ``encode(centre)``).  ``samples``: an int or one per axis (>= 2) - the sum of ``encode`` over that linspace mesh, both ends
+        included (``get_sims_for_area`` of slam_map_new.py with 20).  ``normalize``: every row divided by ``max(norm, 1e-8)`` like
+        ``SSPSpace.normalize`` (on the device for ``out="device"``).  Returns as ``encode`` does."""
+        if self.closed:
+            raise fe.SimulationError("the encoder is closed")
+        if out not in ("host", "device"):
+            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+        counts = region_samples(self.dim, samples, mean)
+        sp = counts.ctypes.data if counts is not None else None
+        x, n, (ptr, on_device, code, ld) = self._boxes_arg(boxes)
+        if out == "host" and not on_device and code == _lib.SSN_F64:
+            res = np.empty((n, self.width), dtype=np.float64)
+            self._check(self._lib.ssn_encoder_encode_boxes(self._h, ptr, n, sp, int(bool(mean)), res.ctypes.data))
+            return unit_rows(res) if normalize else res
+        import torch
+        res = torch.empty((n, self.width), dtype=torch.float32 if self.dtype == "f32" else torch.float64, device=f"cuda:{self.device}")
+        torch.cuda.current_stream(res.device).synchronize()
+        self._check(self._lib.ssn_encoder_encode_boxes_device(self._h, ptr, on_device, code, ld, n, sp, int(bool(mean)),
+                                                              int(bool(normalize) and out == "device"), res.data_ptr() if n else None, self.width))
+        if out == "device":
+            return res
+        res = res.cpu().to(torch.float64).numpy()
+        return unit_rows(res) if normalize else res
+
+
+def region_samples(dim, samples, mean):
+    """The per-axis mesh counts of ``encode_region`` as an int32 array (None without a mesh); ValueError for a count below 2, a
+    wrong number of counts, or ``mean`` beside ``samples``."""
+    if samples is None:
+        return None
+    if mean:
+        raise ValueError("mean given together with samples: the mean of a mesh is its sum over the number of points")
+    counts = np.asarray(samples)
+    if counts.ndim == 0:
+        counts = np.full(dim, counts)
+    if counts.shape != (dim,) or not np.issubdtype(counts.dtype, np.integer):
+        raise ValueError(f"samples must be an int or {dim} ints, got {samples!r}")
+    if np.any(counts < 2):
+        raise ValueError(f"samples {counts.tolist()} below 2: a linspace mesh has both ends")
+    return np.ascontiguousarray(counts, dtype=np.int32)
+
+
+def unit_rows(v):
+    """Every row over ``max(norm, 1e-8)``: ``SSPSpace.normalize`` applied per row."""
+    return v / np.maximum(np.sqrt(np.sum(v * v, axis=1, keepdims=True)), 1e-8)

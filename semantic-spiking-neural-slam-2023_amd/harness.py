@@ -380,3 +380,19 @@ def similarity_frames(ssp_space, rows_or_frames, num_samples=100, power=2, norma
         return np.zeros(lead + (n,) * dim)
     maps = ssp_space.similarity_map(arr.reshape(-1, d), n, "grid", power=power, normalize=normalize, backend=backend, **_table_arg(table))
     return maps.reshape(lead + (n,) * dim)
+
+
+def region_ssps(ssp_space, boxes, backend=None):
+    """Unit-length SSPs of axis-aligned boxes: the integral of ``encode`` over each box, normalised - ``wall_ssps`` of
+    slam_map_new.py:73-80, where every entry is a ``dblquad`` at ``epsabs=1e-4``, in closed form (``SSPSpace.encode_region``).
+    ``boxes``: ``(N, dim, 2)`` like ``wall_boundaries``.  ``backend``: None for NumPy, "hip" / "hip-f64" for the GPU."""
+    return ssp_space.encode_region(boxes, normalize=True, backend=backend)
+
+
+def area_query(sim, memory, ssp_space, boxes, vocab, samples=20, mode="reference", backend=None):
+    """"Which landmarks lie in this area" - ``get_sims_for_area`` of slam_map_new.py:412-423 without reading either learned matrix
+    back: the SSPs of a ``samples`` x ``samples`` mesh over each box, summed and normalised (``encode_region``, closed form), recalled
+    through the learned inverse memory on the device (``sim.recall(memory, q, mode)``) and compared with the rows of ``vocab``
+    (``(n_vocab, d_val)``, e.g. the landmark SPs).  -> ``(N_boxes, n_vocab)`` similarities."""
+    q = ssp_space.encode_region(boxes, samples=samples, normalize=True, backend=backend)
+    return sim.recall(memory, q, mode) @ np.asarray(vocab, dtype=float).T

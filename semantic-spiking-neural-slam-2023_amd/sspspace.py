@@ -44,6 +44,28 @@ def _unit_rows(v, eps):
     return v / np.maximum(nrm, eps)
 
 
+def _sinc(y):
+    """sin(y) / y, below 2^-10 its series 1 - y^2/6 + y^4/120 (which leaves y^6/5040 < 2^-72): the guard of ``k_encode_phase_box``."""
+    small = np.abs(y) < 2.0 ** -10
+    y2 = y * y
+    return np.where(small, 1.0 + y2 * (y2 / 120.0 - 1.0 / 6.0), np.sin(y) / np.where(small, 1.0, y))
+
+
+_PI_A = float(np.float32(np.pi))                                  # pi in three parts: q _PI_A and q _PI_B are exact for |q| < 2^29
+_PI_B = float(np.float32(np.pi - _PI_A))
+_PI_C = (np.pi - _PI_A - _PI_B) + 1.2246467991473532e-16
+
+
+def _dirichlet(y, n):
+    """sin(n y) / sin(y) for an integer n: y = q pi + r with |r| <= pi/2, the ratio (-1)^(q (n - 1)) sin(n r) / sin(r); for
+    |r| < 2^-26, where sin(r) = r to 2^-54, n sinc(n r) - the removable singularity at every multiple of pi."""
+    q = np.rint(y / np.pi)
+    r = ((y - q * _PI_A) - q * _PI_B) - q * _PI_C
+    small = np.abs(r) < 2.0 ** -26
+    v = np.where(small, n * _sinc(n * r), np.sin(n * r) / np.sin(np.where(small, 1.0, r)))
+    return np.where((np.mod(np.abs(q), 2.0) == 1.0) & (n % 2 == 0), -v, v)
+
+
 class SPSpace:
     """Discrete semantic-pointer vocabulary (reference ``sspspace.py:11-182``).
 
@@ -163,6 +185,43 @@ class SSPSpace:
         with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
             list(pool.map(slab, range(0, x.shape[0], rows)))
         return out
+
+    def encode_region(self, boxes, samples=None, mean=False, normalize=False, backend=None):
+        """SSPs of axis-aligned boxes in closed form: ``boxes`` ``(N, domain_dim, 2)`` rows of ``[lo, hi]`` per axis
+        (the layout of ``domain_bounds``; or one box) -> ``(N, ssp_dim)``.
+
+        With ``(K, M, w) = refine_tables()``, centre ``c`` and side lengths ``L``, bin ``k`` of a box is ``encode(c)``'s bin times a
+        real amplitude: ``prod_a L_a sinc(M_ka L_a / 2)`` for the integral of ``encode`` over the box (``samples=None``), the same
+        without the ``L_a`` for its mean (``mean=True``; a zero-width box is the point encode of its centre), and
+        ``prod_a sin(n_a y_a) / sin(y_a)``, ``y_a = M_ka L_a / (2 (n_a - 1))``, for the sum of ``encode`` over a linspace mesh of
+        ``samples`` points per axis (an int or one per axis, >= 2) - slam_map_new.py:412-416 with 20.  ``normalize``: every row over
+        ``max(norm, 1e-8)``.  ``backend``: None (or "numpy") is float64 NumPy; "hip" / "hip-f64" run ``k_encode_phase_box`` through
+        the cached ``SSPEncoder``."""
+        from .encoding import backend_dtype, region_samples, unit_rows
+        dtype = backend_dtype(backend)
+        if dtype is not None:
+            return self._ssp_encoder(dtype).encode_region(boxes, samples=samples, mean=mean, normalize=normalize)
+        counts = region_samples(self.domain_dim, samples, mean)
+        b = np.asarray(boxes, dtype=float)
+        if b.ndim == 2:
+            b = b[None]
+        if b.ndim != 3 or b.shape[1:] != (self.domain_dim, 2):
+            raise ValueError(f"boxes must be (N, {self.domain_dim}, 2), got {b.shape}")
+        lo, hi = b[:, :, 0], b[:, :, 1]
+        if np.any(hi < lo):
+            raise ValueError(f"box {int(np.argwhere(hi < lo)[0, 0])} has hi < lo on an axis")
+        K, M, _ = self.refine_tables()
+        L = hi - lo
+        amp = np.ones((b.shape[0], K))
+        for a in range(self.domain_dim):
+            mL = L[:, a:a + 1] * M[None, :, a]
+            if counts is None:
+                amp *= _sinc(0.5 * mL) * (1.0 if mean else L[:, a:a + 1])
+            else:
+                amp *= _dirichlet(mL * (0.5 / (counts[a] - 1.0)), float(counts[a]))
+        F = amp * np.exp(1j * ((0.5 * (lo + hi)) @ M.T))
+        out = np.fft.ifft(F, axis=1).real if K == self.ssp_dim else np.fft.irfft(F, n=self.ssp_dim, axis=1)
+        return unit_rows(out) if normalize else out
 
     def update_lengthscale(self, scale):
         scale = np.asarray(scale, dtype=float)

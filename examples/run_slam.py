@@ -16,7 +16,10 @@ frames (normalised, squared; a landmark not seen yet gives a zero map where the 
 ``--save`` to ``<result file minus .npz>_maps.npz``; the map seconds are printed next to the decode seconds.  ``--inverse-memory``
 learns the inverse map beside the SLAM network (landmark SSP -> landmark SP, ``slam_map_new.py:243-250``) and ``--area-query X0 X1 Y0
 Y1`` (repeatable) asks it which landmarks lie in a box: ``harness.area_query``, the script's ``get_sims_for_area`` with the mesh sum
-in closed form (``SSPSpace.encode_region``) and the recall on the GPU.
+in closed form (``SSPSpace.encode_region``) and the recall on the GPU.  ``--vector-queries`` (with ``--map-every``) asks where every
+landmark lies relative to the agent at every map sample (``slam_map_new.py:453-485``, ``harness.vector_query``): the pose estimate
+cleaned up on the grid, inverted and unbound from the recalled landmark SSPs - on the GPU with ``--decode-backend hip``
+(``SSPBinder``) -, its cosine and distance errors printed for the last sample and saved as ``landmark_vec_*``.
 """
 import argparse
 import os
@@ -71,6 +74,10 @@ def parse(argv=None):
                    help="with --map-every: similarity maps over the N x ... x N sample grid at every map sample - sim_grid of the "
                         "probed trajectory (squared, raw rows) and landmark_sim_grid of the MapProbe frames (normalised, squared), "
                         "made by --decode-backend; with --save written to <result>_maps.npz")
+    p.add_argument("--vector-queries", action="store_true",
+                   help="with --map-every: where every landmark lies relative to the agent at every map sample (slam_map_new.py:453-485) - "
+                        "the cleaned-up pose estimate unbound from the recalled landmark SSPs, decoded (harness.vector_query, made by "
+                        "--decode-backend); with --save written as landmark_vec_est, landmark_vec_cos_err, landmark_vec_dist_err")
     p.add_argument("--inverse-memory", action="store_true",
                    help="learn the inverse memory (landmark SSP -> landmark SP) beside the SLAM network, as slam_map_new.py does")
     p.add_argument("--area-query", action="append", nargs="+", type=float, default=None, metavar="LO HI",
@@ -84,6 +91,8 @@ def main(argv=None):
     dt = 0.001
     if args.save_maps > 0 and not args.map_every > 0:
         raise SystemExit("--save-maps needs --map-every: the maps are made at the map samples")
+    if args.vector_queries and not args.map_every > 0:
+        raise SystemExit("--vector-queries needs --map-every: the queries are made at the map samples")
     if args.area_query and not args.inverse_memory:
         raise SystemExit("--area-query needs --inverse-memory: the boxes are recalled through the inverse memory")
     if args.area_query and any(len(b) != 2 * args.domain_dim for b in args.area_query):
@@ -155,7 +164,7 @@ def main(argv=None):
     else:
         lm_ssps, lm_locs = H.map_recall(space, sm.lm_space, built_memory, nengo.LIF(), decoders, backend=args.decode_backend)
     decode_time = time.time() - t0
-    lm_over_time = sim_grid = landmark_sim_grid = None
+    lm_over_time = sim_grid = landmark_sim_grid = vector_fields = None
     if frames is not None:
         t0 = time.time()
         lm_over_time = H.map_over_time(space, frames, backend=None if args.decode_backend == "numpy" else args.decode_backend, table=table)
@@ -175,6 +184,18 @@ def main(argv=None):
             print("similarity maps: %d path and %d x %d landmark maps over %s samples, %.1f MB: maps %.2f s (%s), decode %.2f s" % (
                 rows.shape[0], frames.shape[0], frames.shape[1], " x ".join(["%d" % args.save_maps] * space.domain_dim),
                 (sim_grid.nbytes + landmark_sim_grid.nbytes) / 1e6, time.time() - t1, args.decode_backend, t1 - t0))
+        if args.vector_queries:
+            t1 = time.time()
+            at = np.searchsorted(ts, map_ts - 0.5 * dt)
+            vq_backend = None if args.decode_backend == "numpy" else ("hip" if dtype == "f32" else "hip-f64")
+            vq = H.vector_query(space, out[at], frames, backend=vq_backend, table=table)
+            true_vecs = sm.obj_locs[None, :, :] - path[at][:, None, :]
+            vec_cos_err, vec_dist_err = H.vector_query_errors(space, vq, true_vecs)
+            vector_fields = dict(landmark_vec_est=vq["vec_est"], landmark_vec_cos_err=vec_cos_err, landmark_vec_dist_err=vec_dist_err)
+            print("vector queries: %d samples x %d landmarks in %.3f s (%s); last sample: cosine error median %.3f (max %.3f), distance error "
+                  "median %.3f (max %.3f)" % (frames.shape[0], frames.shape[1], time.time() - t1, vq_backend or "numpy",
+                                               float(np.median(vec_cos_err[-1])), float(np.max(vec_cos_err[-1])),
+                                               float(np.median(vec_dist_err[-1])), float(np.max(vec_dist_err[-1]))))
     elif recall_time:
         print("map recall: final map on the GPU in %.4f s (kernels %.2f ms)" % (recall_time, recall_kernel_ms))
     lm_err = np.linalg.norm(lm_locs - sm.obj_locs, axis=1)
@@ -208,7 +229,8 @@ def main(argv=None):
             args.backend, args.save_name_extra, space.ssp_dim, args.pi_n_neurons, args.mem_n_neurons, args.circonv_n_neurons,
             int(T), args.limit, args.seed)
         H.save_slam_results(os.path.join(args.save_dir, name), space, ts, path, sm.real_ssp, sm.obj_locs, args.view_rad, out,
-                            lm_ssps, lm_locs, elapsed, args=args, landmark_loc_over_time=lm_over_time, landmark_loc_over_time_ts=map_ts)
+                            lm_ssps, lm_locs, elapsed, args=args, landmark_loc_over_time=lm_over_time, landmark_loc_over_time_ts=map_ts,
+                            extra_fields=vector_fields)
         print("saved", os.path.join(args.save_dir, name))
         if sim_grid is not None:
             maps_name = name[:-len(".npz")] + "_maps.npz"

@@ -541,6 +541,47 @@ int ssn_recall_set_keys(ssn_recall* rc, const double* keys, int64_t n_keys);
 int ssn_recall_run(ssn_recall* rc, double* dst);
 int ssn_recall_get_info(ssn_recall* rc, ssn_recall_info* out);
 
+/* Binding of rows on the device (additive to ABI 11; csrc/ssn_bind.hip): out[r] = a[ra] (*) b[rb], the circular
+ * convolution SSPSpace.bind / SPSpace.bind compute as ifft(fft(a) * fft(b)).real.  A binder depends on d and the dtype only, has a
+ * stream and a scratch area of its own (0 = 64 MB; at least ssn_binder_info.min_scratch_bytes, one row) and is independent of
+ * ssn_sim.  SSN_F32: one workgroup per row runs the whole convolution in LDS - both rows packed into one complex transform after
+ * their norms are balanced by a power of two, the spectra separated and multiplied, one transform back (k_bind_rows); d with prime
+ * factors <= 32 up to 6400 directly, any other d through the chirp-z form of a smooth length M >= 2 d - 1, M <= 6400.  SSN_F64 (the
+ * parity mode): every entry the fma chain over i = 0 .. d - 1 of a_i b_{(j - i) mod d}, d <= 10000 (k_bind_direct).  Any other d is
+ * SSN_EUNSUPPORTED.  flags: SSN_BIND_INVERT_A / _B read that operand at (d - i) mod d; SSN_BIND_NORMALIZE divides every output row
+ * by max(its norm, norm_floor).  Pairing: an operand with a_n (b_n) rows gives output row r its row 0 (count 1), r (count n) or
+ * r / (n / count) (count a divisor of n: one pose row for the L landmark rows of its sample); any other count is SSN_EINVAL.
+ * ssn_binder_bind: dense host doubles in and out (the binder's dtype widened).  ssn_binder_bind_device: operands on the host or on
+ * the binder's device, SSN_F32 / SSN_F64, leading dimensions >= d (elements) -> a device buffer of the binder's dtype with leading
+ * dimension out_ld >= d, complete when the call returns; nothing outside the n x d entries is written.  n == 0 succeeds and writes
+ * nothing.  The bits are the same for any scratch size, for host and device operands of the same values and from run to run.
+ * Without a GPU: SSN_EHIP "no HIP device available (there is no CPU fallback)". */
+enum ssn_bind_flag { SSN_BIND_INVERT_A = 1, SSN_BIND_INVERT_B = 2, SSN_BIND_NORMALIZE = 4 };
+typedef struct ssn_binder ssn_binder;
+typedef struct ssn_binder_info {
+  int64_t row_chunk;          /* output rows per chunk                                                           */
+  int64_t n_chunks;           /* chunks of a call with n rows                                                    */
+  int64_t scratch_bytes;
+  int64_t min_scratch_bytes;  /* one row: two staged operands and the host output, d doubles each                */
+  int64_t d;
+  int64_t transform_length;   /* L: points of the transforms run (M, or d); d for SSN_F64, which runs none       */
+  int64_t bluestein_m;        /* M of the chirp-z form, 0 when d is transformed directly                         */
+  int64_t n_radices;
+  int64_t radices[12];        /* the Stockham passes of one transform of L points                                */
+  int64_t threads;            /* per workgroup                                                                   */
+  int64_t lds_bytes;          /* dynamic LDS per workgroup                                                       */
+  int64_t last_launches;      /* kernel launches of the last bind call                                           */
+  double last_kernel_ms;      /* their device time (HIP events around the kernels, copies outside)               */
+} ssn_binder_info;
+int ssn_binder_create(int32_t dtype, int32_t device, int64_t d, int64_t scratch_bytes /* 0 = default */, ssn_binder** out);
+void ssn_binder_destroy(ssn_binder* binder);
+int ssn_binder_bind(ssn_binder* binder, const double* a, int64_t a_n, const double* b, int64_t b_n, int64_t n, int32_t flags,
+                    double norm_floor, double* out);
+int ssn_binder_bind_device(ssn_binder* binder, const void* a, int32_t a_on_device, int32_t a_dtype, int64_t a_ld, int64_t a_n,
+                           const void* b, int32_t b_on_device, int32_t b_dtype, int64_t b_ld, int64_t b_n, int64_t n, int32_t flags,
+                           double norm_floor, void* out_dev, int64_t out_ld);
+int ssn_binder_get_info(ssn_binder* binder, int64_t n, ssn_binder_info* out);
+
 int ssn_get_counters(ssn_sim* sim, ssn_counters* out);
 /* Fills at most `capacity` entries; returns the number of kernels with timed launches (or a negative status). */
 int ssn_get_kernel_times(ssn_sim* sim, ssn_kernel_time* out, int32_t capacity);

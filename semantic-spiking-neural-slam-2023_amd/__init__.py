@@ -13,9 +13,11 @@ Import as ``sspslam_amd`` (alias of this hyphen-named directory).  Sub-modules:
 * ``simulator``  ``Simulator(model)`` / ``run`` / ``data[probe]`` over ctypes -> libssn_hip.so
 * ``decoding``   ``GridDecoder``: grid decode / refinement of SSP trajectories on the GPU
 * ``encoding``   ``SSPEncoder``: SSPs of points on the GPU
+* ``binding``    ``SSPBinder``: binding (circular convolution) of rows on the GPU
 """
 __version__ = "0.1.0"
 
 from .sspspace import SPSpace, SSPSpace, HexagonalSSPSpace, RandomSSPSpace  # noqa: F401
 from .frontend import MapProbe  # noqa: F401
 from .encoding import SSPEncoder  # noqa: F401
+from .binding import SSPBinder  # noqa: F401

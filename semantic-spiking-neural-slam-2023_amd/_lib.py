@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SSN_HIP_LIB") or os.path.join(_HERE, "libssn_hip.so")
 SSN_ABI_VERSION = 11
 SSN_F32, SSN_F64 = 0, 1
 SSN_MAP_NORMALIZE, SSN_MAP_SQUARE = 1, 2          # flags of ssn_decoder_map
+SSN_BIND_INVERT_A, SSN_BIND_INVERT_B, SSN_BIND_NORMALIZE = 1, 2, 4          # flags of ssn_binder_bind
 SSN_BUF_REAL, SSN_BUF_I32, SSN_BUF_TAPS, SSN_BUF_DRIVES = 0, 1, 2, 3
 NEURON_CODE = {"lif": 0, "lifrate": 1, "relu": 2}
 OP_CODE = {"fill": 1, "table": 2, "axpy": 3, "matvec": 4, "lowpass": 5, "ensarray": 6, "neurons": 7,
@@ -111,6 +112,13 @@ class RecallInfo(C.Structure):
                 ("last_kernel_ms", C.c_double)]
 
 
+class BinderInfo(C.Structure):
+    _fields_ = [("row_chunk", C.c_int64), ("n_chunks", C.c_int64), ("scratch_bytes", C.c_int64), ("min_scratch_bytes", C.c_int64),
+                ("d", C.c_int64), ("transform_length", C.c_int64), ("bluestein_m", C.c_int64), ("n_radices", C.c_int64),
+                ("radices", C.c_int64 * 12), ("threads", C.c_int64), ("lds_bytes", C.c_int64), ("last_launches", C.c_int64),
+                ("last_kernel_ms", C.c_double)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("ms_total", C.c_double)]
 
@@ -171,6 +179,12 @@ EXPORTS = {
     "ssn_recall_set_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "ssn_recall_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ssn_recall_get_info": (C.c_int, [C.c_void_p, C.POINTER(RecallInfo)]),
+    "ssn_binder_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "ssn_binder_destroy": (None, [C.c_void_p]),
+    "ssn_binder_bind": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p]),
+    "ssn_binder_bind_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_void_p, C.c_int64]),
+    "ssn_binder_get_info": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(BinderInfo)]),
     "ssn_get_counters": (C.c_int, [C.c_void_p, C.POINTER(Counters)]),
     "ssn_get_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(KernelTime), C.c_int32]),
     "ssn_n_steps": (C.c_int64, [C.c_void_p]),

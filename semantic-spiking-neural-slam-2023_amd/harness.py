@@ -302,11 +302,13 @@ def save_pathint_results(filename, ssp_space, ts, path, real_ssp, pi_sim_out, el
 
 def save_slam_results(filename, ssp_space, ts, path, real_ssp, obj_locs, view_rad, slam_sim_out, landmark_ssps_est,
                       landmark_loc_est, elapsed_time, args=None, elapsed_thread_time=None, landmark_loc_over_time=None,
-                      landmark_loc_over_time_ts=None):
+                      landmark_loc_over_time_ts=None, extra_fields=None):
     """Field names of ``run_slam.py:282-293``; ``landmark_loc_over_time`` (samples, L, domain_dim) and its sample times
-    ``landmark_loc_over_time_ts`` are added when given (``map_over_time`` of a ``MapProbe``).  Returns the decoded path estimate."""
+    ``landmark_loc_over_time_ts`` are added when given (``map_over_time`` of a ``MapProbe``), and so is every array of
+    ``extra_fields`` under its own name (``vector_query`` results).  Returns the decoded path estimate."""
     extra = {} if landmark_loc_over_time is None else dict(landmark_loc_over_time=landmark_loc_over_time,
                                                            landmark_loc_over_time_ts=landmark_loc_over_time_ts)
+    extra.update(extra_fields or {})
     slam_path, slam_sims, slam_error = pathint_metrics(ssp_space, slam_sim_out, real_ssp, path)
     n = slam_sim_out.shape[0]
     path, real_ssp = path[:n], real_ssp[:n]
@@ -396,3 +398,57 @@ def area_query(sim, memory, ssp_space, boxes, vocab, samples=20, mode="reference
     (``(n_vocab, d_val)``, e.g. the landmark SPs).  -> ``(N_boxes, n_vocab)`` similarities."""
     q = ssp_space.encode_region(boxes, samples=samples, normalize=True, backend=backend)
     return sim.recall(memory, q, mode) @ np.asarray(vocab, dtype=float).T
+
+
+def vector_query(ssp_space, pose_rows, frames, num_samples=100, clean_up=True, norm_floor=1e-6, backend=None, refine=False, table="host"):
+    """"Where is landmark j relative to me, over time" - the landmark vector queries of slam_map_new.py:453-485:
+
+        inv_ssps = ssp_space.invert(clean_up_fun2(pose_rows))            # pose estimate, cleaned up on the grid, inverted
+        res1 = ssp_space.bind(inv_ssps, frames[:, j])                    # unbound from landmark j's recalled SSP
+        res1 = res1 / np.maximum(norm_floor, norm(res1))
+        res = decode(res1)
+
+    for all landmarks at once.  ``pose_rows``: ``(S, d)`` (``sim.data[ssp_p][::every]``); ``frames``: ``(S, L, d)``, what a ``MapProbe``
+    records (``allitem_hat`` with the sample axis first).  -> ``{"vec_ssps": (S, L, d) the normalised unbound rows, "vec_est":
+    (S, L, dim) their grid decode}`` (``refine=True``: 'grid-refine').  ``clean_up=False`` takes the pose rows as they are.
+    ``backend=None`` is the script's computation in float64 NumPy.  ``backend="hip"`` / ``"hip-f64"`` keeps the cleaned-up poses
+    (``GridDecoder.clean_up(out="device")``), the unbound rows (``SSPBinder.bind(invert_a=True, normalize=True)``) and their decode
+    on the device; ``vec_ssps`` comes back once."""
+    from .binding import SSPBinder, backend_dtype
+    dtype = backend_dtype(backend)
+    poses, frames = np.asarray(pose_rows, dtype=float), np.asarray(frames, dtype=float)
+    d, dim = ssp_space.ssp_dim, ssp_space.domain_dim
+    if poses.ndim != 2 or frames.ndim != 3 or poses.shape[1] != d or frames.shape[2] != d or frames.shape[0] != poses.shape[0]:
+        raise ValueError(f"pose_rows must be (S, {d}) and frames (S, L, {d}), got {poses.shape} and {frames.shape}")
+    s, n_keys = frames.shape[:2]
+    if s * n_keys == 0:
+        return {"vec_ssps": np.zeros((s, n_keys, d)), "vec_est": np.zeros((s, n_keys, dim))}
+    method = "grid-refine" if refine else "from-set"
+    if dtype is None:
+        if table != "host":
+            raise ValueError("table='device' needs a hip backend: the NumPy decode has no device table")
+        if clean_up:
+            poses = ssp_space.encode(ssp_space.decode(poses, "from-set", "grid", num_samples))
+        inv = ssp_space.invert(poses)
+        res = ssp_space.bind(np.repeat(inv, n_keys, axis=0), frames.reshape(s * n_keys, d))
+        res = res / np.maximum(norm_floor, np.sqrt(np.sum(res ** 2, axis=1))).reshape(-1, 1)
+        est = ssp_space.decode(res, method, "grid", num_samples)
+        return {"vec_ssps": res.reshape(s, n_keys, d), "vec_est": np.asarray(est).reshape(s, n_keys, dim)}
+    dec = ssp_space._grid_decoder(num_samples, "grid", dtype, table)
+    clean = dec.clean_up(poses, encode="device", out="device") if clean_up else poses
+    with SSPBinder(d, dtype=dtype, device=dec.device) as binder:
+        rows = binder.bind(clean, frames, invert_a=True, normalize=True, norm_floor=norm_floor, out="device").reshape(s * n_keys, d)
+    est = dec.decode(rows, refine=refine)
+    return {"vec_ssps": rows.cpu().double().numpy().reshape(s, n_keys, d), "vec_est": np.asarray(est).reshape(s, n_keys, dim)}
+
+
+def vector_query_errors(ssp_space, result, true_vectors):
+    """The two curves of slam_map_new.py:482-485 for a ``vector_query`` result: ``true_vectors`` ``(S, L, dim)`` are
+    ``item - path`` per sample and landmark.  -> ``(cosine error 1 - <vec_ssps, encode(true)>, distance error |vec_est - true|)``,
+    both ``(S, L)``."""
+    true = np.asarray(true_vectors, dtype=float)
+    s, n_keys, dim = true.shape
+    real = ssp_space.encode(true.reshape(s * n_keys, dim)).reshape(s, n_keys, -1)
+    cos_err = 1.0 - np.sum(np.asarray(result["vec_ssps"]) * real, axis=2)
+    dist_err = np.sqrt(np.sum((np.asarray(result["vec_est"]) - true) ** 2, axis=2))
+    return cos_err, dist_err

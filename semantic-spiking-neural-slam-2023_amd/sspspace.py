@@ -66,6 +66,19 @@ def _dirichlet(y, n):
     return np.where((np.mod(np.abs(q), 2.0) == 1.0) & (n % 2 == 0), -v, v)
 
 
+def _cached_binder(space, d, backend, device=0):
+    """The SSPBinder of ``bind(backend="hip")``, one per (dtype, device), kept on the space; None for the NumPy backends."""
+    from .binding import SSPBinder, backend_dtype
+    dtype = backend_dtype(backend)
+    if dtype is None:
+        return None
+    cache = space.__dict__.setdefault("_binder_cache", {})
+    key = (dtype, int(device))
+    if key not in cache:
+        cache[key] = SSPBinder(int(d), dtype=dtype, device=device)
+    return cache[key]
+
+
 class SPSpace:
     """Discrete semantic-pointer vocabulary (reference ``sspspace.py:11-182``).
 
@@ -116,9 +129,20 @@ class SPSpace:
         s[0] = 1.0
         return s
 
-    def bind(self, a, b):
+    def bind(self, a, b, backend=None):
+        """``backend``: None (or "numpy") is the float64 host transform below; "hip" / "hip-f64" bind on the GPU through a
+        ``binding.SSPBinder`` cached on the space."""
+        if backend is not None:
+            binder = _cached_binder(self, self.dim, backend)
+            if binder is not None:
+                return binder.bind(a, b)
         a, b = np.atleast_2d(a), np.atleast_2d(b)
         return np.fft.ifft(np.fft.fft(a, axis=1) * np.fft.fft(b, axis=1), axis=1).real
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_binder_cache", None)           # device handles stay with the object they were made for
+        return state
 
     def invert(self, a):
         a = np.atleast_2d(a)
@@ -299,6 +323,7 @@ class SSPSpace:
         state = dict(self.__dict__)
         state.pop("_decoder_cache", None)          # device handles stay with the object they were made for
         state.pop("_encoder_cache", None)
+        state.pop("_binder_cache", None)
         return state
 
     def _drop_decoders(self):
@@ -306,6 +331,8 @@ class SSPSpace:
             dec.close()
         for enc in self.__dict__.pop("_encoder_cache", {}).values():
             enc.close()
+        for binder in self.__dict__.pop("_binder_cache", {}).values():
+            binder.close()
 
     def _grid_decoder(self, num_samples, sampling_method, dtype, table="host"):
         """The GridDecoder of backend="hip" for this sample set, kept next to ``_grid_cache`` (one at a time: it holds the table on
@@ -542,7 +569,13 @@ class SSPSpace:
         s[0] = 1.0
         return s
 
-    def bind(self, a, b):
+    def bind(self, a, b, backend=None):
+        """``backend``: None (or "numpy") is the float64 host transform below; "hip" / "hip-f64" bind on the GPU through a
+        ``binding.SSPBinder`` cached on the space (``k_bind_rows`` / the f64 parity mode)."""
+        if backend is not None:
+            binder = _cached_binder(self, self.ssp_dim, backend)
+            if binder is not None:
+                return binder.bind(a, b)
         a, b = np.atleast_2d(a), np.atleast_2d(b)
         return np.fft.ifft(np.fft.fft(a, axis=1) * np.fft.fft(b, axis=1), axis=1).real
 

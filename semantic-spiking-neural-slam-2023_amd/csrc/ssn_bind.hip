@@ -36,7 +36,7 @@
 #include "ssn_kernels.hpp"      // dft_stockham, cmulf
 #include "ssn_service.hpp"
 
-using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, check_device
+using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, Lane, elapsed, stage_rows, check_rows
 
 namespace {
 
@@ -328,20 +328,16 @@ void chirp_tables(int d, int M, std::vector<float2>* w, std::vector<float2>* fb)
 
 }  // namespace
 
-struct ssn_binder {
-  int dtype = 0, device = 0;
-  int64_t d = 0, scratch_bytes = 0;
+struct ssn_binder : Lane {
+  int dtype = 0;
+  int64_t d = 0;
   int M = 0, L = 0, threads = 0;
   int64_t lds_bytes = 0;
   std::vector<int> radix;
   float2* tw = nullptr;
   float2* chirp = nullptr;
   float2* fb = nullptr;
-  char* scratch = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   double kernel_ms = 0.0;      // of the last call
-  int64_t launches = 0;
 
   int64_t row_bytes() const { return 3 * d * 8; }      // two staged operands and the host output, doubles
   int64_t min_scratch() const { return row_bytes(); }
@@ -349,12 +345,7 @@ struct ssn_binder {
 
   ~ssn_binder() {
     DevGuard g(device);
-    for (hipEvent_t e : {e0, e1}) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (tw) (void)hipFree(tw);
-    if (chirp) (void)hipFree(chirp);
-    if (fb) (void)hipFree(fb);
-    if (scratch) (void)hipFree(scratch);
+    for (float2* p : {tw, chirp, fb}) if (p) (void)hipFree(p);
   }
 };
 
@@ -416,7 +407,7 @@ int bind(ssn_binder* bd, const char* who, const Operand& a, const Operand& b, in
   g.tw = bd->tw; g.chirp = bd->chirp; g.fb = bd->fb;
   bd->kernel_ms = 0.0;
   bd->launches = 0;
-  if (!staged) SVC_HIP(hipEventRecord(bd->e0, bd->stream));
+  if (!staged) SVC_HIP(hipEventRecord(bd->ev[0], bd->stream));
   for (int64_t r0 = 0; r0 < n; r0 += cap) {
     const int64_t m = std::min(cap, n - r0);
     const Operand* ops[2] = {&a, &b};
@@ -428,8 +419,7 @@ int bind(ssn_binder* bd, const char* who, const Operand& a, const Operand& b, in
       if (ops[o]->on_device) continue;
       const size_t esz = ops[o]->dtype == SSN_F64 ? 8 : 4;
       const int64_t first = r0 / divs[o], count = (r0 + m - 1) / divs[o] - first + 1;      // count <= m <= cap
-      SVC_HIP(hipMemcpy2DAsync(stages[o], (size_t)d * esz, (const char*)ops[o]->p + (size_t)first * ops[o]->ld * esz, (size_t)ops[o]->ld * esz, (size_t)d * esz,
-                               (size_t)count, hipMemcpyHostToDevice, bd->stream));
+      if (const int rc = stage_rows(bd->stream, stages[o], (const char*)ops[o]->p + (size_t)first * ops[o]->ld * esz, ops[o]->ld, d, esz, count)) return rc;
       ptr[o] = stages[o]; ld[o] = d; first_row[o] = first;
     }
     g.a = ptr[0]; g.a_ld = ld[0]; g.a_row0 = first_row[0];
@@ -437,23 +427,19 @@ int bind(ssn_binder* bd, const char* who, const Operand& a, const Operand& b, in
     g.row0 = r0;
     if (host_out) { g.out = stage_out; g.out_ld = d; g.out64 = 1; }
     else { g.out = (char*)dev_out + (size_t)r0 * out_ld * osz; g.out_ld = out_ld; g.out64 = osz == 8; }
-    if (staged) SVC_HIP(hipEventRecord(bd->e0, bd->stream));
+    if (staged) SVC_HIP(hipEventRecord(bd->ev[0], bd->stream));
     SVC_HIP(launch_bind(bd, g, (int)m));
     bd->launches += 1;
     if (!staged) continue;
-    SVC_HIP(hipEventRecord(bd->e1, bd->stream));
+    SVC_HIP(hipEventRecord(bd->ev[1], bd->stream));
     if (host_out) SVC_HIP(hipMemcpyAsync(host_out + (size_t)r0 * d, stage_out, (size_t)m * d * 8, hipMemcpyDeviceToHost, bd->stream));
     SVC_HIP(hipStreamSynchronize(bd->stream));      // the next chunk reuses the scratch area
-    float ms = 0.0f;
-    SVC_HIP(hipEventElapsedTime(&ms, bd->e0, bd->e1));
-    bd->kernel_ms += ms;
+    if (const int rc = elapsed(bd->ev[0], bd->ev[1], &bd->kernel_ms)) return rc;
   }
   if (!staged) {
-    SVC_HIP(hipEventRecord(bd->e1, bd->stream));
+    SVC_HIP(hipEventRecord(bd->ev[1], bd->stream));
     SVC_HIP(hipStreamSynchronize(bd->stream));
-    float ms = 0.0f;
-    SVC_HIP(hipEventElapsedTime(&ms, bd->e0, bd->e1));
-    bd->kernel_ms = ms;
+    if (const int rc = elapsed(bd->ev[0], bd->ev[1], &bd->kernel_ms)) return rc;
   }
   return SSN_OK;
 }
@@ -467,10 +453,8 @@ int ssn_binder_create(int32_t dtype, int32_t device, int64_t d, int64_t scratch_
   *out = nullptr;
   if (dtype != SSN_F32 && dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_binder_create: unknown dtype %d", dtype);
   if (d < 2) return fail(SSN_EINVAL, "ssn_binder_create: d %lld below 2", (long long)d);
-  if (scratch_bytes < 0) return fail(SSN_EINVAL, "ssn_binder_create: negative scratch_bytes");
   std::unique_ptr<ssn_binder> b(new ssn_binder);
   b->dtype = dtype;
-  b->device = device;
   b->d = d;
   if (dtype == SSN_F32) {
     if (!plan_bind(d, &b->M, &b->radix))
@@ -487,16 +471,8 @@ int ssn_binder_create(int32_t dtype, int32_t device, int64_t d, int64_t scratch_
     b->threads = std::min(1024, std::max(64, ((int)d + 63) / 64 * 64));
     b->lds_bytes = d * 16;
   }
-  b->scratch_bytes = scratch_bytes ? scratch_bytes : std::max<int64_t>((int64_t)64 << 20, b->min_scratch());
-  if (b->scratch_bytes < b->min_scratch())
-    return fail(SSN_EINVAL, "ssn_binder_create: scratch_bytes %lld too small for one row of d %lld (%lld bytes)", (long long)scratch_bytes, (long long)d,
-                (long long)b->min_scratch());
-  if (const int rc = check_device("ssn_binder_create", device)) return rc;
+  if (const int rc = b->open("ssn_binder_create", device, scratch_bytes, b->min_scratch(), "row of d %lld", (long long)d)) return rc;
   DevGuard g(device);
-  SVC_HIP(hipStreamCreate(&b->stream));
-  SVC_HIP(hipEventCreate(&b->e0));
-  SVC_HIP(hipEventCreate(&b->e1));
-  SVC_HIP(hipMalloc((void**)&b->scratch, (size_t)b->scratch_bytes));
   if (dtype == SSN_F32) {
     if (const int rc = upload(&b->tw, twiddles(b->L))) return rc;
     if (b->M > 0) {
@@ -529,10 +505,8 @@ int ssn_binder_bind_device(ssn_binder* binder, const void* a, int32_t a_on_devic
   if (!binder) return fail(SSN_EINVAL, "%s: null binder", who);
   if (n < 0) return fail(SSN_EINVAL, "%s: negative n", who);
   if (flags & ~7) return fail(SSN_EINVAL, "%s: unknown flags %d", who, flags);
-  if (a_dtype != SSN_F32 && a_dtype != SSN_F64) return fail(SSN_EINVAL, "%s: unknown a_dtype %d", who, a_dtype);
-  if (b_dtype != SSN_F32 && b_dtype != SSN_F64) return fail(SSN_EINVAL, "%s: unknown b_dtype %d", who, b_dtype);
-  if (a_ld < binder->d) return fail(SSN_EINVAL, "%s: leading dimension %lld of a below the width %lld", who, (long long)a_ld, (long long)binder->d);
-  if (b_ld < binder->d) return fail(SSN_EINVAL, "%s: leading dimension %lld of b below the width %lld", who, (long long)b_ld, (long long)binder->d);
+  if (const int rc = check_rows(who, "a", a_dtype, a_ld, binder->d, " of a")) return rc;
+  if (const int rc = check_rows(who, "b", b_dtype, b_ld, binder->d, " of b")) return rc;
   if (out_ld < binder->d) return fail(SSN_EINVAL, "%s: leading dimension %lld of the output below the width %lld", who, (long long)out_ld, (long long)binder->d);
   if (n == 0) return SSN_OK;
   if (!a || !b || !out_dev) return fail(SSN_EINVAL, "%s: null argument", who);

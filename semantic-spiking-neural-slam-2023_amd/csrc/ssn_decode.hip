@@ -42,8 +42,8 @@
 // Scratch (fixed at creation, default 64 MB): per row K doubles of upload staging, Kp converted values, one (value, column)
 // partial per strip slot and the (double similarity, best) result.  The host cuts n_rows into chunks of whole row tiles that fit and the
 // column walk into at most `slots` strips (ssn_decoder::plan: cut_rows, tiles_per_part); the smallest scratch holds one row tile with
-// one strip.  The error reporting, the device guard and the device check at creation are csrc/ssn_service.hpp's, shared with the
-// encoder and the recall.
+// one strip.  The error reporting, the device guard and the Lane (device check, stream, events, scratch area) are
+// csrc/ssn_service.hpp's, shared with the encoder and the binder.
 //
 // The table comes from the host (ssn_decoder_create: converted and uploaded) or is made here from the sample points
 // (ssn_decoder_create_from_points: a float64 ssn_encoder of csrc/ssn_encode.hip writes it chunk by chunk in the decoder's dtype).
@@ -60,7 +60,7 @@
 #include "ssn_kernels.hpp"      // launch_gemm_nt / launch_argmax_partial: the materialising composition ssn_decoder_rows_composed times
 #include "ssn_service.hpp"
 
-using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, check_device
+using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, Lane, elapsed, stage_rows, check_rows
 
 namespace {
 
@@ -548,16 +548,12 @@ int64_t tiles_per_part(int64_t col_tiles, int64_t max_parts, int64_t chunk_tiles
 
 }  // namespace
 
-struct ssn_decoder {
-  int dtype = 0, device = 0, n_cu = 1;
-  int64_t S = 0, K = 0, Kp = 0, col_tiles = 0, scratch_bytes = 0;
+struct ssn_decoder : Lane {
+  int dtype = 0, n_cu = 1;
+  int64_t S = 0, K = 0, Kp = 0, col_tiles = 0;
   size_t esz = 4;
   void* table = nullptr;
-  char* scratch = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   double kernel_ms = 0.0;          // of the last ssn_decoder_rows* call
-  int64_t launches = 0;
   // refinement (ssn_decoder_set_refine): buffers of its own, beside the scratch area, so the plan stays what it was
   int r_dim = 0;
   int64_t r_K = 0, r_rows = 0;     // bins; rows the work area holds
@@ -604,13 +600,9 @@ struct ssn_decoder {
 
   ~ssn_decoder() {
     DevGuard g(device);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (stream) (void)hipStreamDestroy(stream);
     drop_refine();
     drop_map_stage();
     if (table) (void)hipFree(table);
-    if (scratch) (void)hipFree(scratch);
   }
 };
 
@@ -657,13 +649,14 @@ hipError_t launch_prepare(ssn_decoder* d, const TI* src, int64_t ld, int n, int 
 }
 
 // The start of a chunk, rows [r0, r0 + n) of a call.  Rows: host doubles (dense, width K), copied to the staging area first, or
-// device rows of dtype rows_dtype with leading dimension ld, read where they are.  Records e0 - after the upload, so the timed span
+// device rows of dtype rows_dtype with leading dimension ld, read where they are.  Records ev[0] - after the upload, so the timed span
 // holds kernels only - and launches k_decode_prepare into a.conv, scaling the rows or not.
 template <typename T>
 int prepare_chunk(ssn_decoder* d, const Areas<T>& a, const double* host, const void* dev, int rows_dtype, int64_t ld, int64_t r0, int n, int n_pad,
                   bool scale) {
-  if (host) SVC_HIP(hipMemcpyAsync(a.stage, host + (size_t)r0 * d->K, (size_t)n * d->K * 8, hipMemcpyHostToDevice, d->stream));
-  SVC_HIP(hipEventRecord(d->e0, d->stream));
+  if (host)
+    if (const int rc = stage_rows(d->stream, a.stage, host + (size_t)r0 * d->K, d->K, d->K, 8, n)) return rc;
+  SVC_HIP(hipEventRecord(d->ev[0], d->stream));
   if (host) SVC_HIP(launch_prepare<T>(d, (const double*)a.stage, d->K, n, n_pad, a.conv, scale));
   else if (rows_dtype == SSN_F32) SVC_HIP(launch_prepare<T>(d, (const float*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv, scale));
   else SVC_HIP(launch_prepare<T>(d, (const double*)dev + (size_t)r0 * ld, ld, n, n_pad, a.conv, scale));
@@ -741,7 +734,7 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
                        n, (const T*)a.conv, (const T*)d->table, (int)d->Kp, a.sims, a.best);
     SVC_HIP(hipGetLastError());
     if (ro) SVC_HIP(refine_chunk<T>(d, ra, (const T*)a.conv, a.best, n, ro->iterations));
-    SVC_HIP(hipEventRecord(d->e1, d->stream));
+    SVC_HIP(hipEventRecord(d->ev[1], d->stream));
     if (best) SVC_HIP(hipMemcpyAsync(best + r0, a.best, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
     if (sims) SVC_HIP(hipMemcpyAsync(sims + r0, a.sims, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
     if (ro) {
@@ -750,9 +743,7 @@ int decode_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dt
       if (ro->status) SVC_HIP(hipMemcpyAsync(ro->status + r0, ra.status, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
     }
     SVC_HIP(hipStreamSynchronize(d->stream));
-    float ms = 0.0f;
-    SVC_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
-    d->kernel_ms += ms;
+    if (const int rc = elapsed(d->ev[0], d->ev[1], &d->kernel_ms)) return rc;
     d->launches += ro ? 5 : 3;
   }
   return SSN_OK;
@@ -798,7 +789,7 @@ int map_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype
     hipLaunchKernelGGL((k_decode_map<T, TO>), dim3((unsigned)(n_pad / TILE), (unsigned)n_runs), dim3(256), 0, d->stream, (const T*)a.conv, (const T*)d->table,
                        (int)d->Kp, n, (unsigned)S, (int)d->col_tiles, (int)tpr, square, dst, (long long)(out_on_device ? out_ld : S));
     SVC_HIP(hipGetLastError());
-    SVC_HIP(hipEventRecord(d->e1, d->stream));
+    SVC_HIP(hipEventRecord(d->ev[1], d->stream));
     if (!out_on_device) SVC_HIP(hipMemcpyAsync(d->m_pin, d->m_dev, (size_t)n * S * sizeof(TO), hipMemcpyDeviceToHost, d->stream));
     SVC_HIP(hipStreamSynchronize(d->stream));
     if (!out_on_device) {
@@ -806,9 +797,7 @@ int map_rows(ssn_decoder* d, const double* host, const void* dev, int rows_dtype
       if (out_ld == S) memcpy(out + (size_t)r0 * S, src, (size_t)n * S * sizeof(TO));
       else for (int64_t r = 0; r < n; ++r) memcpy(out + (size_t)(r0 + r) * out_ld, src + (size_t)r * S, (size_t)S * sizeof(TO));
     }
-    float ms = 0.0f;
-    SVC_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
-    d->kernel_ms += ms;
+    if (const int rc = elapsed(d->ev[0], d->ev[1], &d->kernel_ms)) return rc;
     d->launches += 2;
   }
   return SSN_OK;
@@ -852,12 +841,11 @@ int decode_rows_composed(ssn_decoder* d, const double* host, int64_t n_rows, int
     if (const int rc = prepare_chunk<float>(d, a, host, nullptr, 0, d->K, 0, n, n_pad, true)) return rc;      // host rows from row 0, scaled
     SVC_HIP(ssn::launch_gemm_nt<float>(d->stream, a.conv, (int)d->Kp, (const float*)d->table, (int)d->Kp, C, (int)d->S, n, (int)d->S, (int)d->Kp, 1));
     SVC_HIP(ssn::launch_argmax_partial<float>(d->stream, C, (long long)n_rows * d->S, part, n, 1));
-    SVC_HIP(hipEventRecord(d->e1, d->stream));
+    SVC_HIP(hipEventRecord(d->ev[1], d->stream));
     SVC_HIP(hipMemcpyAsync(idx.data(), part + n_rows, (size_t)n_rows * 4, hipMemcpyDeviceToHost, d->stream));
     SVC_HIP(hipStreamSynchronize(d->stream));
-    float ms = 0.0f;
-    SVC_HIP(hipEventElapsedTime(&ms, d->e0, d->e1));
-    d->kernel_ms = ms;
+    d->kernel_ms = 0.0;
+    if (const int rc = elapsed(d->ev[0], d->ev[1], &d->kernel_ms)) return rc;
     d->launches = 3;
     return SSN_OK;
   };
@@ -889,28 +877,18 @@ int create_decoder(const char* who, int32_t dtype, int32_t device, int64_t n_sam
   if (width <= 0 || width > (1 << 20)) return fail(SSN_EINVAL, "%s: width %lld outside 1 .. 2^20", who, (long long)width);
   if (n_samples <= 0 || n_samples > INT32_MAX)
     return fail(SSN_EINVAL, "%s: n_samples %lld outside 1 .. 2^31 - 1", who, (long long)n_samples);
-  if (scratch_bytes < 0) return fail(SSN_EINVAL, "%s: negative scratch_bytes", who);
   std::unique_ptr<ssn_decoder> d(new ssn_decoder);
   d->dtype = dtype;
-  d->device = device;
   d->esz = dtype == SSN_F32 ? 4 : 8;
   d->S = n_samples;
   d->K = width;
   d->Kp = (width + KPAD - 1) / KPAD * KPAD;
   d->col_tiles = (n_samples + TILE - 1) / TILE;
-  d->scratch_bytes = scratch_bytes ? scratch_bytes : std::max<int64_t>((int64_t)64 << 20, d->min_scratch());
-  if (d->scratch_bytes < d->min_scratch())
-    return fail(SSN_EINVAL, "%s: scratch_bytes %lld too small for one %d-row tile of width %lld (%lld bytes)", who, (long long)scratch_bytes,
-                TILE, (long long)width, (long long)d->min_scratch());
-  if (const int rc = check_device(who, device)) return rc;
+  if (const int rc = d->open(who, device, scratch_bytes, d->min_scratch(), "%d-row tile of width %lld", TILE, (long long)width)) return rc;
   DevGuard g(device);
   hipDeviceProp_t prop;
   SVC_HIP(hipGetDeviceProperties(&prop, device));
   d->n_cu = std::max(1, prop.multiProcessorCount);
-  SVC_HIP(hipStreamCreate(&d->stream));
-  SVC_HIP(hipEventCreate(&d->e0));
-  SVC_HIP(hipEventCreate(&d->e1));
-  SVC_HIP(hipMalloc((void**)&d->scratch, (size_t)d->scratch_bytes));
   const int rc = fill(d.get());
   if (rc != SSN_OK) return rc;
   *out = d.release();
@@ -955,8 +933,7 @@ int ssn_decoder_rows(ssn_decoder* dec, const double* rows, int64_t n_rows, int32
 int ssn_decoder_rows_device(ssn_decoder* dec, const void* rows_dev, int32_t rows_dtype, int64_t ld, int64_t n_rows, int32_t* best, double* sims) {
   if (!dec) return fail(SSN_EINVAL, "ssn_decoder_rows_device: null decoder");
   if (n_rows < 0) return fail(SSN_EINVAL, "ssn_decoder_rows_device: negative n_rows");
-  if (rows_dtype != SSN_F32 && rows_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_rows_device: unknown rows_dtype %d", rows_dtype);
-  if (ld < dec->K) return fail(SSN_EINVAL, "ssn_decoder_rows_device: leading dimension %lld below the width %lld", (long long)ld, (long long)dec->K);
+  if (const int rc = check_rows("ssn_decoder_rows_device", "rows", rows_dtype, ld, dec->K)) return rc;
   if (n_rows == 0) return SSN_OK;
   if (!rows_dev || !best) return fail(SSN_EINVAL, "ssn_decoder_rows_device: null argument");
   return dec->dtype == SSN_F32 ? decode_rows<float>(dec, nullptr, rows_dev, rows_dtype, ld, n_rows, best, sims)
@@ -1000,8 +977,7 @@ int ssn_decoder_refine_rows_device(ssn_decoder* dec, const void* rows_dev, int32
                                    double* x, int32_t* best, double* f, int32_t* status) {
   const int rc = refine_args("ssn_decoder_refine_rows_device", dec, n_rows, iterations);
   if (rc != SSN_OK) return rc;
-  if (rows_dtype != SSN_F32 && rows_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_refine_rows_device: unknown rows_dtype %d", rows_dtype);
-  if (ld < dec->K) return fail(SSN_EINVAL, "ssn_decoder_refine_rows_device: leading dimension %lld below the width %lld", (long long)ld, (long long)dec->K);
+  if (const int rc = check_rows("ssn_decoder_refine_rows_device", "rows", rows_dtype, ld, dec->K)) return rc;
   if (n_rows == 0) return SSN_OK;
   if (!rows_dev || !x) return fail(SSN_EINVAL, "ssn_decoder_refine_rows_device: null argument");
   const RefineOut ro{iterations, x, f, status};
@@ -1020,9 +996,8 @@ int ssn_decoder_map(ssn_decoder* dec, const void* rows, int32_t rows_on_device, 
   if (!dec) return fail(SSN_EINVAL, "ssn_decoder_map: null decoder");
   if (n_rows < 0) return fail(SSN_EINVAL, "ssn_decoder_map: negative n_rows");
   if (flags & ~(SSN_MAP_NORMALIZE | SSN_MAP_SQUARE)) return fail(SSN_EINVAL, "ssn_decoder_map: unknown flags 0x%x", flags);
-  if (rows_on_device && rows_dtype != SSN_F32 && rows_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_map: unknown rows_dtype %d", rows_dtype);
-  if (rows_on_device && rows_ld < dec->K)
-    return fail(SSN_EINVAL, "ssn_decoder_map: leading dimension %lld of the rows below the width %lld", (long long)rows_ld, (long long)dec->K);
+  if (rows_on_device)      // (host rows are dense doubles)
+    if (const int rc = check_rows("ssn_decoder_map", "rows", rows_dtype, rows_ld, dec->K, " of the rows")) return rc;
   if (out_dtype != SSN_F32 && out_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_decoder_map: unknown out_dtype %d", out_dtype);
   if (out_dtype == SSN_F32 && dec->dtype == SSN_F64)
     return fail(SSN_EINVAL, "ssn_decoder_map: out_dtype f32 is narrower than the f64 decoder's (narrowing is not offered)");

@@ -50,7 +50,7 @@
 #include "ssn_encode.hpp"
 #include "ssn_service.hpp"
 
-using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, check_device
+using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, Lane, elapsed, stage_rows, check_rows
 
 namespace {
 
@@ -217,17 +217,13 @@ __global__ __launch_bounds__(256) void k_encode_widen(const float* __restrict__ 
 
 }  // namespace
 
-struct ssn_encoder {
-  int dtype = 0, device = 0;
-  int64_t d = 0, K = 0, Kp = 0, dim = 0, scratch_bytes = 0;
+struct ssn_encoder : Lane {
+  int dtype = 0;
+  int64_t d = 0, K = 0, Kp = 0, dim = 0;
   size_t esz = 4;
   double* M = nullptr;             // (K x dim)
   void* B = nullptr;               // (d x Kp) in the encoder's dtype
-  char* scratch = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
   double phase_ms = 0.0, product_ms = 0.0;      // of the last encode call
-  int64_t launches = 0;
 
   int64_t row_bytes() const { return dim * 8 + Kp * (int64_t)esz + d * (int64_t)esz + (esz == 4 ? d * 8 : 0); }
   int64_t min_scratch() const { return ROWS * row_bytes(); }
@@ -251,12 +247,7 @@ struct ssn_encoder {
 
   ~ssn_encoder() {
     DevGuard g(device);
-    for (hipEvent_t e : {e0, e1, e2}) if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (M) (void)hipFree(M);
-    if (B) (void)hipFree(B);
-    if (box_tab) (void)hipFree(box_tab);
-    if (scratch) (void)hipFree(scratch);
+    for (void* p : {(void*)M, B, (void*)box_tab}) if (p) (void)hipFree(p);
   }
 };
 
@@ -371,14 +362,13 @@ int encode(ssn_encoder* e, const Phase& phase, int64_t cap, const void* pts, int
     const void* src = (const char*)pts + (size_t)r0 * pts_ld * isz;
     int64_t ld = pts_ld;
     if (!on_device) {
-      if (pts_ld == width) SVC_HIP(hipMemcpyAsync(a.stage, src, (size_t)m * width * isz, hipMemcpyHostToDevice, e->stream));
-      else SVC_HIP(hipMemcpy2DAsync(a.stage, (size_t)width * isz, src, (size_t)pts_ld * isz, (size_t)width * isz, (size_t)m, hipMemcpyHostToDevice, e->stream));
+      if (const int rc = stage_rows(e->stream, a.stage, src, pts_ld, width, isz, m)) return rc;
       src = a.stage;
       ld = width;
     }
-    SVC_HIP(hipEventRecord(e->e0, e->stream));
+    SVC_HIP(hipEventRecord(e->ev[0], e->stream));
     SVC_HIP(phase(e, src, pts_dtype, ld, m, a.P));
-    SVC_HIP(hipEventRecord(e->e1, e->stream));
+    SVC_HIP(hipEventRecord(e->ev[1], e->stream));
     e->launches += 2;
     if (f32) {
       float* C = host_out ? (float*)a.out : (float*)dev_out + (size_t)r0 * out_ld;
@@ -402,15 +392,12 @@ int encode(ssn_encoder* e, const Phase& phase, int64_t cap, const void* pts, int
       else SVC_HIP(launch_rownorm<double>(e, (double*)dev_out + (size_t)r0 * out_ld, out_ld, m));
       e->launches += 1;
     }
-    SVC_HIP(hipEventRecord(e->e2, e->stream));
+    SVC_HIP(hipEventRecord(e->ev[2], e->stream));
     if (host_out)
       SVC_HIP(hipMemcpyAsync(host_out + (size_t)r0 * e->d, f32 ? (const void*)a.wide : (const void*)a.out, (size_t)m * e->d * 8, hipMemcpyDeviceToHost, e->stream));
     SVC_HIP(hipStreamSynchronize(e->stream));      // the next chunk reuses the scratch area
-    float ms = 0.0f;
-    SVC_HIP(hipEventElapsedTime(&ms, e->e0, e->e1));
-    e->phase_ms += ms;
-    SVC_HIP(hipEventElapsedTime(&ms, e->e1, e->e2));
-    e->product_ms += ms;
+    if (const int rc = elapsed(e->ev[0], e->ev[1], &e->phase_ms)) return rc;
+    if (const int rc = elapsed(e->ev[1], e->ev[2], &e->product_ms)) return rc;
   }
   return SSN_OK;
 }
@@ -483,26 +470,16 @@ int ssn_encoder_create(int32_t dtype, int32_t device, int64_t d, int64_t K, int3
   if (dim < 1) return fail(SSN_EINVAL, "ssn_encoder_create: dim %d below 1", dim);
   if (d < 1 || d > (1 << 20)) return fail(SSN_EINVAL, "ssn_encoder_create: d %lld outside 1 .. 2^20", (long long)d);
   if (K < 1 || K > d) return fail(SSN_EINVAL, "ssn_encoder_create: K %lld outside 1 .. d = %lld", (long long)K, (long long)d);
-  if (scratch_bytes < 0) return fail(SSN_EINVAL, "ssn_encoder_create: negative scratch_bytes");
   std::unique_ptr<ssn_encoder> e(new ssn_encoder);
   e->dtype = dtype;
-  e->device = device;
   e->esz = dtype == SSN_F32 ? 4 : 8;
   e->d = d;
   e->K = K;
   e->dim = dim;
   e->Kp = (2 * K + KPAD - 1) / KPAD * KPAD;
-  e->scratch_bytes = scratch_bytes ? scratch_bytes : std::max<int64_t>((int64_t)64 << 20, e->min_scratch());
-  if (e->scratch_bytes < e->min_scratch())
-    return fail(SSN_EINVAL, "ssn_encoder_create: scratch_bytes %lld too small for one %d-point tile of d %lld, K %lld (%lld bytes)", (long long)scratch_bytes,
-                ROWS, (long long)d, (long long)K, (long long)e->min_scratch());
-  if (const int rc = check_device("ssn_encoder_create", device)) return rc;
+  if (const int rc = e->open("ssn_encoder_create", device, scratch_bytes, e->min_scratch(), "%d-point tile of d %lld, K %lld", ROWS, (long long)d, (long long)K))
+    return rc;
   DevGuard g(device);
-  SVC_HIP(hipStreamCreate(&e->stream));
-  SVC_HIP(hipEventCreate(&e->e0));
-  SVC_HIP(hipEventCreate(&e->e1));
-  SVC_HIP(hipEventCreate(&e->e2));
-  SVC_HIP(hipMalloc((void**)&e->scratch, (size_t)e->scratch_bytes));
   const int rc = dtype == SSN_F32 ? upload_tables<float>(e.get(), M, w) : upload_tables<double>(e.get(), M, w);
   if (rc != SSN_OK) return rc;
   *out = e.release();
@@ -523,9 +500,7 @@ int ssn_encoder_encode_device(ssn_encoder* enc, const void* points, int32_t poin
                               void* out_dev, int64_t out_ld) {
   if (!enc) return fail(SSN_EINVAL, "ssn_encoder_encode_device: null encoder");
   if (n < 0) return fail(SSN_EINVAL, "ssn_encoder_encode_device: negative n");
-  if (points_dtype != SSN_F32 && points_dtype != SSN_F64) return fail(SSN_EINVAL, "ssn_encoder_encode_device: unknown points_dtype %d", points_dtype);
-  if (points_ld < enc->dim)
-    return fail(SSN_EINVAL, "ssn_encoder_encode_device: leading dimension %lld of the points below dim %lld", (long long)points_ld, (long long)enc->dim);
+  if (const int rc = check_rows("ssn_encoder_encode_device", "points", points_dtype, points_ld, enc->dim, " of the points", "dim")) return rc;
   if (out_ld < enc->d) return fail(SSN_EINVAL, "ssn_encoder_encode_device: leading dimension %lld of the output below the width %lld", (long long)out_ld, (long long)enc->d);
   if (out_ld > INT32_MAX) return fail(SSN_EINVAL, "ssn_encoder_encode_device: leading dimension %lld of the output above 2^31 - 1", (long long)out_ld);
   if (n == 0) return SSN_OK;
@@ -549,9 +524,7 @@ int ssn_encoder_encode_boxes_device(ssn_encoder* enc, const void* boxes, int32_t
   const char* who = "ssn_encoder_encode_boxes_device";
   if (!enc) return fail(SSN_EINVAL, "%s: null encoder", who);
   if (n < 0) return fail(SSN_EINVAL, "%s: negative n", who);
-  if (boxes_dtype != SSN_F32 && boxes_dtype != SSN_F64) return fail(SSN_EINVAL, "%s: unknown boxes_dtype %d", who, boxes_dtype);
-  if (boxes_ld < 2 * enc->dim)
-    return fail(SSN_EINVAL, "%s: leading dimension %lld of the boxes below 2 dim = %lld", who, (long long)boxes_ld, (long long)(2 * enc->dim));
+  if (const int rc = check_rows(who, "boxes", boxes_dtype, boxes_ld, 2 * enc->dim, " of the boxes", "2 dim =")) return rc;
   if (out_ld < enc->d) return fail(SSN_EINVAL, "%s: leading dimension %lld of the output below the width %lld", who, (long long)out_ld, (long long)enc->d);
   if (out_ld > INT32_MAX) return fail(SSN_EINVAL, "%s: leading dimension %lld of the output above 2^31 - 1", who, (long long)out_ld);
   int mode = 0;

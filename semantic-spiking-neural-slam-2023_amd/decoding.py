@@ -14,28 +14,19 @@ wanted - the maps the reference's figure scripts draw - ``GridDecoder.similarity
 
         sims = dec.similarity(sim.data[probe], power=2)    # == (sim.data[probe] @ sample_ssps.T) ** 2, (T, n_samples)
 """
-import ctypes as C
+import functools
 
 import numpy as np
 
-from . import _lib
-from . import frontend as fe
+from . import _lib, service
+from .service import BACKENDS
 
 __all__ = ["GridDecoder", "BACKENDS", "backend_dtype"]
 
-# decode backends of SSPSpace.decode / clean_up and the harness: None is the NumPy path
-BACKENDS = {None: None, "numpy": None, "hip": "f32", "hip-f32": "f32", "hip-f64": "f64"}
+backend_dtype = functools.partial(service.backend_dtype, what="decode")      # (backend) -> the GridDecoder's dtype, None: NumPy
 
 
-def backend_dtype(backend):
-    """dtype of the GridDecoder behind a backend name, None for the NumPy path; ValueError for an unknown name."""
-    try:
-        return BACKENDS[backend]
-    except (KeyError, TypeError):
-        raise ValueError(f"unknown decode backend {backend!r}: one of None, 'numpy', 'hip', 'hip-f64'") from None
-
-
-class GridDecoder:
+class GridDecoder(service.DeviceService):
     """Best sample per row, on the GPU.
 
     ``GridDecoder(ssp_space, num_samples, sampling_method)`` takes its table from ``ssp_space.get_sample_pts_and_ssps``;
@@ -52,10 +43,11 @@ class GridDecoder:
     index is some value inside ``[0, n_samples)``.
     """
 
+    noun, destroy = "decoder", "ssn_decoder_destroy"
+
     def __init__(self, ssp_space=None, num_samples=100, sampling_method="grid", samples=None, dtype="f32", device=0,
                  scratch_bytes=None, trust=None, table="host"):
-        if dtype not in ("f32", "f64"):
-            raise ValueError(f"dtype must be 'f32' or 'f64', got {dtype!r}")
+        super().__init__(dtype, device)
         if table not in ("host", "device"):
             raise ValueError(f"table must be 'host' or 'device', got {table!r}")
         if table == "device" and samples is not None:
@@ -66,13 +58,15 @@ class GridDecoder:
         self.table_source = table
         self._encoder = None          # the SSPEncoder of clean_up(encode="device"), made on first use
         # the box of refine(): the pitch of the space's own grid, or trust= beside samples=
-        grid = (num_samples, sampling_method) if samples is None else None
+        self._grid = (num_samples, sampling_method) if samples is None else None
+        self._trust, self._refine_key = trust, None
         if table == "device":
             from .encoding import tables
             pts = np.ascontiguousarray(ssp_space.get_sample_points(num_samples, sampling_method), dtype=np.float64)
             K, M, w = tables(ssp_space)
-            self._create(pts, grid, trust, pts.shape[0], ssp_space.ssp_dim, dtype, device, "ssn_decoder_create_from_points", pts,
-                         (K, int(ssp_space.domain_dim), M.ctypes.data, w.ctypes.data, int(scratch_bytes or 0), 0))
+            self.sample_points, self.n_samples, self.width = pts, int(pts.shape[0]), int(ssp_space.ssp_dim)
+            self._create("ssn_decoder_create_from_points", pts.ctypes.data, self.n_samples, self.width, K, int(ssp_space.domain_dim),
+                         M.ctypes.data, w.ctypes.data, int(scratch_bytes or 0), 0)
             return
         if samples is None:
             sample_ssps, sample_points = ssp_space.get_sample_pts_and_ssps(num_samples, sampling_method)
@@ -81,113 +75,45 @@ class GridDecoder:
         table = np.ascontiguousarray(np.asarray(sample_ssps, dtype=np.float64))
         if table.ndim != 2:
             raise ValueError(f"sample_ssps must be (n_samples, width), got shape {table.shape}")
-        self._create(np.asarray(sample_points), grid, trust, table.shape[0], table.shape[1], dtype, device, "ssn_decoder_create", table,
-                     (int(scratch_bytes or 0),))
-
-    def _create(self, sample_points, grid, trust, n_samples, width, dtype, device, create, source, rest):
-        """The tail of both constructors: the fields, then the ABI call named ``create`` - ``(dtype, device, source, n_samples,
-        width, *rest, handle)``, ``source`` the float64 array the table comes from - whose non-zero status is a BuildError."""
-        self.sample_points = sample_points
-        self._grid = grid
-        self._trust, self._refine_key = trust, None
-        self.n_samples, self.width = int(n_samples), int(width)
-        self.dtype, self.device = dtype, int(device)
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        self.closed = True
-        rc = getattr(self._lib, create)(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, source.ctypes.data, self.n_samples,
-                                        self.width, *rest, C.byref(self._h))
-        if rc != 0:
-            raise fe.BuildError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
-        self.closed = False
-
-    # -- plumbing ------------------------------------------------------------------------------
-    def _check(self, rc):
-        if rc != 0:
-            raise fe.SimulationError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self.sample_points, self.n_samples, self.width = np.asarray(sample_points), int(table.shape[0]), int(table.shape[1])
+        self._create("ssn_decoder_create", table.ctypes.data, self.n_samples, self.width, int(scratch_bytes or 0))
 
     def close(self):
         enc = self.__dict__.pop("_encoder", None)
         if enc is not None:
             enc.close()
-        if not self.closed:
-            self._lib.ssn_decoder_destroy(self._h)
-            self.closed = True
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def info(self, n_rows=0):
         """How a call with ``n_rows`` rows is cut (row_chunk, n_chunks, n_strips, tiles_per_strip), the scratch sizes, and the
         launches / device milliseconds of the last call, as a dict."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
-        out = _lib.DecoderInfo()
-        self._check(self._lib.ssn_decoder_get_info(self._h, int(n_rows), C.byref(out)))
-        return {name: getattr(out, name) for name, _ in _lib.DecoderInfo._fields_}
+        return self._info(_lib.DecoderInfo, "ssn_decoder_get_info", n_rows)
 
     # -- decoding ------------------------------------------------------------------------------
-    def _rows_arg(self, rows):
-        """(rows, n, device call arguments or None): host rows as a C-contiguous float64 array, device tensors as they are."""
-        tensor = hasattr(rows, "is_cuda") and hasattr(rows, "data_ptr")
-        if tensor and not rows.is_cuda:
-            rows, tensor = rows.detach().numpy(), False
-        if tensor:
-            import torch
-            if rows.device.index != self.device:
-                raise ValueError(f"rows live on {rows.device}, the decoder on device {self.device}")
-            rows = rows.detach()
-            if rows.dim() == 1:
-                rows = rows[None, :]
-            if rows.dtype not in (torch.float32, torch.float64):
-                rows = rows.to(torch.float64)
-            if rows.dim() != 2 or rows.shape[1] != self.width:
-                raise ValueError(f"rows must be (T, {self.width}), got {tuple(rows.shape)}")
-            n = int(rows.shape[0])
-            if rows.stride(1) != 1 or (n > 1 and rows.stride(0) < self.width):
-                rows = rows.contiguous()
-            ld = max(int(rows.stride(0)), self.width) if n > 1 else self.width
-            torch.cuda.current_stream(rows.device).synchronize()          # the rows are complete before the decoder's stream reads them
-        else:
-            rows = np.ascontiguousarray(np.atleast_2d(np.asarray(rows, dtype=np.float64)))
-            if rows.ndim != 2 or rows.shape[1] != self.width:
-                raise ValueError(f"rows must be (T, {self.width}), got {rows.shape}")
-            n = int(rows.shape[0])
-        if tensor:
-            return rows, n, (rows.data_ptr() if n else None, _lib.SSN_F32 if rows.dtype == torch.float32 else _lib.SSN_F64, ld)
-        return rows, n, None
+    def _rows(self, rows):
+        """``service.rows_operand`` for rows of the decoder's width; host rows as float64, what ``ssn_decoder_rows`` takes."""
+        return service.rows_operand(rows, self.width, "rows", self.device, who="decoder", keep_f32=False, count="T")
 
     def indices(self, rows, return_sims=False):
         """Index of the best sample of every row (int64, lowest index on ties); with ``return_sims`` also the similarity of the
         scaled row to it.  ``rows``: array-like ``(T, width)`` (or one row), or a torch tensor on the decoder's device (float32 /
         float64, any row stride), which is read in place."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
-        rows, n, dev = self._rows_arg(rows)
-        best = np.empty(n, dtype=np.int32)
-        sims = np.empty(n, dtype=np.float64) if return_sims else None
+        self._open()
+        rows, _, op = self._rows(rows)
+        best = np.empty(op.n, dtype=np.int32)
+        sims = np.empty(op.n, dtype=np.float64) if return_sims else None
         sims_p = sims.ctypes.data if return_sims else None
-        if dev:
-            self._check(self._lib.ssn_decoder_rows_device(self._h, dev[0], dev[1], dev[2], n, best.ctypes.data, sims_p))
+        if op.on_device:
+            self._check(self._lib.ssn_decoder_rows_device(self._h, op.ptr, op.code, op.ld, op.n, best.ctypes.data, sims_p))
         else:
-            self._check(self._lib.ssn_decoder_rows(self._h, rows.ctypes.data, n, best.ctypes.data, sims_p))
+            self._check(self._lib.ssn_decoder_rows(self._h, rows.ctypes.data, op.n, best.ctypes.data, sims_p))
         best = best.astype(np.int64)
         return (best, sims) if return_sims else best
 
     def set_map_stage(self, nbytes=0):
         """Size of the device + pinned staging of host maps (0: the default, 64 MB or one tile of doubles); at least one 128-row
         tile, ``128 * n_samples`` values.  Never changes a result."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
+        self._open()
         self._check(self._lib.ssn_decoder_set_map_stage(self._h, int(nbytes)))
 
     def similarity(self, rows, power=1, normalize=False, out="host", out_dtype=None, into=None):
@@ -198,43 +124,27 @@ class GridDecoder:
         f32 decoder - half the copy); ``out="device"`` a torch tensor in the decoder's dtype; ``into=`` a caller's 2-D device tensor
         of that dtype, ``(T, n_samples)`` with unit column stride and any row stride >= n_samples, written in place (nothing outside
         ``[:T, :n_samples]`` is touched) and returned.  With ``normalize=True, power=1`` the argmax of a row is ``indices(rows)``."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
+        self._open()
         if power not in (1, 2) or isinstance(power, bool):
             raise ValueError(f"power must be 1 or 2, got {power!r}")
-        if out not in ("host", "device"):
-            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+        service.check_out(out)
         if out_dtype not in (None, "f32", "f64"):
             raise ValueError(f"out_dtype must be None, 'f32' or 'f64', got {out_dtype!r}")
         if out_dtype == "f32" and self.dtype == "f64":
             raise ValueError("out_dtype='f32' from an f64 decoder is not offered: the map is never narrowed")
         if (out == "device" or into is not None) and out_dtype not in (None, self.dtype):
             raise ValueError(f"a device map has the decoder's dtype {self.dtype!r}, not out_dtype={out_dtype!r}")
-        rows, n, dev = self._rows_arg(rows)
+        rows, _, op = self._rows(rows)
+        n = op.n
         flags = (_lib.SSN_MAP_NORMALIZE if normalize else 0) | (_lib.SSN_MAP_SQUARE if power == 2 else 0)
-        rows_args = (dev[0], 1, dev[1], dev[2]) if dev else (rows.ctypes.data, 0, 0, self.width)
-        code = {"f32": _lib.SSN_F32, "f64": _lib.SSN_F64}
+        rows_args = (op.ptr, 1, op.code, op.ld) if op.on_device else (rows.ctypes.data, 0, 0, self.width)
         if out == "host" and into is None:
             dt = out_dtype or "f64"
             res = np.empty((n, self.n_samples), dtype=np.float32 if dt == "f32" else np.float64)
-            self._check(self._lib.ssn_decoder_map(self._h, *rows_args, n, flags, res.ctypes.data, 0, code[dt], self.n_samples))
+            self._check(self._lib.ssn_decoder_map(self._h, *rows_args, n, flags, res.ctypes.data, 0, service.CODE[dt], self.n_samples))
             return res
-        import torch
-        tdt = torch.float32 if self.dtype == "f32" else torch.float64
-        if into is None:
-            into = torch.empty((n, self.n_samples), dtype=tdt, device=f"cuda:{self.device}")
-        else:
-            if not (hasattr(into, "is_cuda") and into.is_cuda and into.device.index == self.device):
-                raise ValueError(f"into= must be a tensor on the decoder's device {self.device}")
-            if into.dtype != tdt:
-                raise ValueError(f"into= must be {tdt}, the decoder's dtype, got {into.dtype}")
-            if into.dim() != 2 or tuple(into.shape) != (n, self.n_samples):
-                raise ValueError(f"into= must be ({n}, {self.n_samples}), got {tuple(into.shape)}")
-            if into.stride(1) != 1 or (n > 1 and into.stride(0) < self.n_samples):
-                raise ValueError(f"into= needs unit column stride and a row stride >= {self.n_samples}, got strides {tuple(into.stride())}")
-            torch.cuda.current_stream(into.device).synchronize()          # whatever filled it is complete before the decoder's stream writes
-        ld = max(int(into.stride(0)), self.n_samples) if n > 1 else self.n_samples
-        self._check(self._lib.ssn_decoder_map(self._h, *rows_args, n, flags, into.data_ptr() if n else None, 1, code[self.dtype], ld))
+        into, ld = service.result(self, n, self.n_samples, into, exact=True)
+        self._check(self._lib.ssn_decoder_map(self._h, *rows_args, n, flags, into.data_ptr() if n else None, 1, service.CODE[self.dtype], ld))
         return into
 
     def _set_refine(self, trust=None):
@@ -270,19 +180,18 @@ class GridDecoder:
         ``x0 +- pitch`` (``k_decode_refine``): ``(T, dim)`` float64 points; with ``return_info`` also ``f`` (the
         similarity at x), ``status`` (bit 1: on a box face, 2: Hessian not negative definite at x, 4: last step above
         1e-6 pitch) and ``best`` (the grid index).  Rows as ``indices`` takes them.  ``iterations=0`` is the grid decode."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
+        self._open()
         iterations = int(iterations)
         if iterations < 0:
             raise ValueError(f"iterations must be >= 0, got {iterations}")
         self._set_refine(trust)
-        rows, n, dev = self._rows_arg(rows)
-        dim = self.sample_points.shape[1]
+        rows, _, op = self._rows(rows)
+        n, dim = op.n, self.sample_points.shape[1]
         x = np.empty((n, dim), dtype=np.float64)
         best, f, status = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int32)
         out = (x.ctypes.data, best.ctypes.data, f.ctypes.data, status.ctypes.data)
-        if dev:
-            self._check(self._lib.ssn_decoder_refine_rows_device(self._h, dev[0], dev[1], dev[2], n, iterations, *out))
+        if op.on_device:
+            self._check(self._lib.ssn_decoder_refine_rows_device(self._h, op.ptr, op.code, op.ld, n, iterations, *out))
         else:
             self._check(self._lib.ssn_decoder_refine_rows(self._h, rows.ctypes.data, n, iterations, *out))
         return (x, f, status, best.astype(np.int64)) if return_info else x
@@ -291,13 +200,10 @@ class GridDecoder:
         """Measurement aid (tools/bench_decode.py): the same indices from the composition this decoder replaces - the similarity
         matrix written out by ``k_gemm_nt_mfma_f32``, then ``k_argmax_partial`` over it.  f32, host rows, one chunk, at most 2 GB
         of similarities; ``info()["last_kernel_ms"]`` is its device time afterwards."""
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
-        rows = np.ascontiguousarray(np.atleast_2d(np.asarray(rows, dtype=np.float64)))
-        if rows.ndim != 2 or rows.shape[1] != self.width:
-            raise ValueError(f"rows must be (T, {self.width}), got {rows.shape}")
-        best = np.empty(rows.shape[0], dtype=np.int32)
-        self._check(self._lib.ssn_decoder_rows_composed(self._h, rows.ctypes.data, rows.shape[0], best.ctypes.data))
+        self._open()
+        rows, _, op = self._rows(np.asarray(rows, dtype=np.float64))
+        best = np.empty(op.n, dtype=np.int32)
+        self._check(self._lib.ssn_decoder_rows_composed(self._h, rows.ctypes.data, op.n, best.ctypes.data))
         return best.astype(np.int64)
 
     def decode(self, rows, return_sims=False, refine=False, iterations=8):
@@ -318,15 +224,13 @@ class GridDecoder:
             raise ValueError("clean_up needs the decoder's ssp_space")
         if encode not in ("host", "device", "hip"):
             raise ValueError(f"encode must be 'host', 'device' or 'hip', got {encode!r}")
-        if out not in ("host", "device"):
-            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+        service.check_out(out)
         if encode == "host" and out == "device":
             raise ValueError("out='device' needs encode='device': the host encode returns a NumPy array")
         points = self.decode(rows, refine=refine, iterations=iterations)
         if encode == "host":
             return self.ssp_space.encode(points)
-        if self.closed:
-            raise fe.SimulationError("the decoder is closed")
+        self._open()
         if self._encoder is None:
             from .encoding import SSPEncoder
             self._encoder = SSPEncoder(self.ssp_space, dtype=self.dtype, device=self.device)

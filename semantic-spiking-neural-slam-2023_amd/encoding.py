@@ -15,25 +15,16 @@ without a GPU the constructor raises.
 
 ``SSPSpace.encode(x, backend="hip")`` does the same through an encoder cached on the space.
 """
-import ctypes as C
+import functools
 
 import numpy as np
 
-from . import _lib
-from . import frontend as fe
+from . import _lib, service
+from .service import BACKENDS
 
 __all__ = ["SSPEncoder", "BACKENDS", "backend_dtype"]
 
-# encode backends of SSPSpace.encode / clean_up: None is the NumPy path
-BACKENDS = {None: None, "numpy": None, "hip": "f32", "hip-f32": "f32", "hip-f64": "f64"}
-
-
-def backend_dtype(backend):
-    """dtype of the SSPEncoder behind a backend name, None for the NumPy path; ValueError for an unknown name."""
-    try:
-        return BACKENDS[backend]
-    except (KeyError, TypeError):
-        raise ValueError(f"unknown encode backend {backend!r}: one of None, 'numpy', 'hip', 'hip-f64'") from None
+backend_dtype = functools.partial(service.backend_dtype, what="encode")      # (backend) -> the SSPEncoder's dtype, None: NumPy
 
 
 def tables(space):
@@ -42,7 +33,7 @@ def tables(space):
     return int(K), np.ascontiguousarray(M, dtype=np.float64), np.ascontiguousarray(w, dtype=np.float64)
 
 
-class SSPEncoder:
+class SSPEncoder(service.DeviceService):
     """SSPs of points, on the GPU.
 
     ``SSPEncoder(space, dtype="f64", device=0, scratch_bytes=None)`` takes the phase matrix and length scale the space has at that
@@ -50,66 +41,27 @@ class SSPEncoder:
     ``scratch_bytes``: size of the device work area (default 64 MB); a smaller one only means more chunks, never another bit.
     """
 
+    noun, destroy = "encoder", "ssn_encoder_destroy"
+
     def __init__(self, space, dtype="f64", device=0, scratch_bytes=None):
-        if dtype not in ("f32", "f64"):
-            raise ValueError(f"dtype must be 'f32' or 'f64', got {dtype!r}")
+        super().__init__(dtype, device)
         if space is None or not hasattr(space, "refine_tables"):
             raise ValueError("SSPEncoder needs an SSPSpace")
         K, M, w = tables(space)
         self.dim, self.width = int(space.domain_dim), int(space.ssp_dim)
-        self.dtype, self.device = dtype, int(device)
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        self.closed = True
-        rc = self._lib.ssn_encoder_create(_lib.SSN_F32 if dtype == "f32" else _lib.SSN_F64, self.device, self.width, K, self.dim,
-                                          M.ctypes.data, w.ctypes.data, int(scratch_bytes or 0), C.byref(self._h))
-        if rc != 0:
-            raise fe.BuildError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
-        self.closed = False
-
-    def _check(self, rc):
-        if rc != 0:
-            raise fe.SimulationError(f"{_lib.STATUS.get(rc, rc)}: {_lib.last_error()}")
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        if not self.closed:
-            self._lib.ssn_encoder_destroy(self._h)
-            self.closed = True
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create("ssn_encoder_create", self.width, K, self.dim, M.ctypes.data, w.ctypes.data, int(scratch_bytes or 0))
 
     def info(self, n=0):
         """How a call with ``n`` points is cut (row_chunk, n_chunks), the scratch sizes, and the launches / device milliseconds
         (phase and product apart) of the last call, as a dict."""
-        if self.closed:
-            raise fe.SimulationError("the encoder is closed")
-        out = _lib.EncoderInfo()
-        self._check(self._lib.ssn_encoder_get_info(self._h, int(n), C.byref(out)))
-        return {name: getattr(out, name) for name, _ in _lib.EncoderInfo._fields_}
+        return self._info(_lib.EncoderInfo, "ssn_encoder_get_info", n)
 
-    def _points_arg(self, x):
-        """(points, n, (pointer, on_device, dtype code, leading dimension)): host points as a C-contiguous float32 / float64 array,
-        device tensors as they are."""
-        return self._rows_arg(x, self.dim, "points")
-
-    def _boxes_arg(self, boxes):
-        """``_points_arg`` for boxes ``(N, dim, 2)`` (or one ``(dim, 2)``): rows of ``lo_0, hi_0, lo_1, hi_1, ...``; a device tensor
-        whose last two axes are dense is read in place, whatever its row stride."""
+    def _boxes(self, boxes):
+        """``service.rows_operand`` for boxes ``(N, dim, 2)`` (or one ``(dim, 2)``) as rows of ``lo_0, hi_0, lo_1, hi_1, ...``; a
+        device tensor whose last two axes are dense is read in place, whatever its row stride."""
         tensor = hasattr(boxes, "is_cuda") and hasattr(boxes, "data_ptr")
         if not tensor:
             boxes = np.asarray(boxes)
-            if boxes.dtype != np.float32:
-                boxes = boxes.astype(np.float64)
         if boxes.ndim == 2:
             boxes = boxes[None]
         if boxes.ndim != 3 or tuple(boxes.shape[1:]) != (self.dim, 2):
@@ -119,54 +71,29 @@ class SSPEncoder:
             flat = boxes.as_strided((n, 2 * self.dim), (boxes.stride(0), 1))
         else:
             flat = boxes.reshape(n, 2 * self.dim)
-        return self._rows_arg(flat, 2 * self.dim, "boxes")
+        return service.rows_operand(flat, 2 * self.dim, "boxes", self.device, who="encoder")
 
-    def _rows_arg(self, x, width, what):
-        tensor = hasattr(x, "is_cuda") and hasattr(x, "data_ptr")
-        if tensor and not x.is_cuda:
-            x, tensor = x.detach().numpy(), False
-        if tensor:
-            import torch
-            if x.device.index != self.device:
-                raise ValueError(f"{what} live on {x.device}, the encoder on device {self.device}")
-            x = x.detach()
-            if x.dim() == 1:
-                x = x[None, :]
-            if x.dtype not in (torch.float32, torch.float64):
-                x = x.to(torch.float64)
-            if x.dim() != 2 or x.shape[1] != width:
-                raise ValueError(f"{what} must be (N, {width}), got {tuple(x.shape)}")
-            n = int(x.shape[0])
-            if x.stride(1) != 1 or (n > 1 and x.stride(0) < width):
-                x = x.contiguous()
-            ld = max(int(x.stride(0)), width) if n > 1 else width
-            torch.cuda.current_stream(x.device).synchronize()          # the rows are complete before the encoder's stream reads them
-            return x, n, (x.data_ptr() if n else None, 1, _lib.SSN_F32 if x.dtype == torch.float32 else _lib.SSN_F64, ld)
-        x = np.atleast_2d(np.asarray(x))
-        x = np.ascontiguousarray(x, dtype=np.float32 if x.dtype == np.float32 else np.float64)
-        if x.ndim != 2 or x.shape[1] != width:
-            raise ValueError(f"{what} must be (N, {width}), got {x.shape}")
-        n = int(x.shape[0])
-        return x, n, (x.ctypes.data if n else None, 0, _lib.SSN_F32 if x.dtype == np.float32 else _lib.SSN_F64, width)
+    def _encode(self, op, out, host_fn, device_fn, mode=(), device_mode=(), normalize=False):
+        """The tail of both encodes.  Host float64 rows to a host result are one ABI call, ``host_fn(handle, rows, n, *mode,
+        result)``; anything else goes through a device result, ``device_fn(handle, *op, *mode, *device_mode, result, leading
+        dimension)``.  ``normalize``: the rows of a host result over ``max(norm, 1e-8)`` (the call normalises a device result)."""
+        if out == "host" and not op.on_device and op.code == _lib.SSN_F64:
+            res = np.empty((op.n, self.width), dtype=np.float64)
+            self._check(host_fn(self._h, op.ptr, op.n, *mode, res.ctypes.data))
+        else:
+            res, ld = service.result(self, op.n, self.width)
+            self._check(device_fn(self._h, *op, *mode, *device_mode, res.data_ptr() if op.n else None, ld))
+            res = service.finish(res, out)
+        return unit_rows(res) if normalize and out == "host" else res
 
     def encode(self, x, out="host"):
         """SSPs of the points ``x``: array-like ``(N, dim)`` (or one point), or a torch tensor on the encoder's device (float32 /
         float64, any row stride), which is read in place.  ``out="host"``: an ``(N, d)`` float64 array.  ``out="device"``: a torch
         tensor of the encoder's dtype on its device."""
-        if self.closed:
-            raise fe.SimulationError("the encoder is closed")
-        if out not in ("host", "device"):
-            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
-        x, n, (ptr, on_device, code, ld) = self._points_arg(x)
-        if out == "host" and not on_device and code == _lib.SSN_F64:
-            res = np.empty((n, self.width), dtype=np.float64)
-            self._check(self._lib.ssn_encoder_encode(self._h, ptr, n, res.ctypes.data))
-            return res
-        import torch
-        res = torch.empty((n, self.width), dtype=torch.float32 if self.dtype == "f32" else torch.float64, device=f"cuda:{self.device}")
-        torch.cuda.current_stream(res.device).synchronize()
-        self._check(self._lib.ssn_encoder_encode_device(self._h, ptr, on_device, code, ld, n, res.data_ptr() if n else None, self.width))
-        return res if out == "device" else res.cpu().to(torch.float64).numpy()
+        self._open()
+        service.check_out(out)
+        x, _, op = service.rows_operand(x, self.dim, "points", self.device, who="encoder")
+        return self._encode(op, out, self._lib.ssn_encoder_encode, self._lib.ssn_encoder_encode_device)
 
     @property
     def region_min_scratch(self):
@@ -180,27 +107,13 @@ class SSPEncoder:
         ``encode(centre)``).  ``samples``: an int or one per axis (>= 2) - the sum of ``encode`` over that linspace mesh, both ends
         included (``get_sims_for_area`` of slam_map_new.py with 20).  ``normalize``: every row divided by ``max(norm, 1e-8)`` like
         ``SSPSpace.normalize`` (on the device for ``out="device"``).  Returns as ``encode`` does."""
-        if self.closed:
-            raise fe.SimulationError("the encoder is closed")
-        if out not in ("host", "device"):
-            raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+        self._open()
+        service.check_out(out)
         counts = region_samples(self.dim, samples, mean)
-        sp = counts.ctypes.data if counts is not None else None
-        x, n, (ptr, on_device, code, ld) = self._boxes_arg(boxes)
-        if out == "host" and not on_device and code == _lib.SSN_F64:
-            res = np.empty((n, self.width), dtype=np.float64)
-            self._check(self._lib.ssn_encoder_encode_boxes(self._h, ptr, n, sp, int(bool(mean)), res.ctypes.data))
-            return unit_rows(res) if normalize else res
-        import torch
-        res = torch.empty((n, self.width), dtype=torch.float32 if self.dtype == "f32" else torch.float64, device=f"cuda:{self.device}")
-        torch.cuda.current_stream(res.device).synchronize()
-        self._check(self._lib.ssn_encoder_encode_boxes_device(self._h, ptr, on_device, code, ld, n, sp, int(bool(mean)),
-                                                              int(bool(normalize) and out == "device"), res.data_ptr() if n else None, self.width))
-        if out == "device":
-            return res
-        res = res.cpu().to(torch.float64).numpy()
-        return unit_rows(res) if normalize else res
-
+        mode = (counts.ctypes.data if counts is not None else None, int(bool(mean)))
+        x, _, op = self._boxes(boxes)
+        return self._encode(op, out, self._lib.ssn_encoder_encode_boxes, self._lib.ssn_encoder_encode_boxes_device, mode,
+                            (int(bool(normalize) and out == "device"),), normalize)
 
 def region_samples(dim, samples, mean):
     """The per-axis mesh counts of ``encode_region`` as an int32 array (None without a mesh); ValueError for a count below 2, a

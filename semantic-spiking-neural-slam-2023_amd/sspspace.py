@@ -21,6 +21,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .service import ServiceCache
+
 __all__ = ["SPSpace", "SSPSpace", "HexagonalSSPSpace", "RandomSSPSpace", "conjsym"]
 
 
@@ -72,11 +74,7 @@ def _cached_binder(space, d, backend, device=0):
     dtype = backend_dtype(backend)
     if dtype is None:
         return None
-    cache = space.__dict__.setdefault("_binder_cache", {})
-    key = (dtype, int(device))
-    if key not in cache:
-        cache[key] = SSPBinder(int(d), dtype=dtype, device=device)
-    return cache[key]
+    return ServiceCache(space, "binder").get((dtype, int(device)), lambda: SSPBinder(int(d), dtype=dtype, device=device))
 
 
 class SPSpace:
@@ -140,9 +138,7 @@ class SPSpace:
         return np.fft.ifft(np.fft.fft(a, axis=1) * np.fft.fft(b, axis=1), axis=1).real
 
     def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop("_binder_cache", None)           # device handles stay with the object they were made for
-        return state
+        return ServiceCache.strip(dict(self.__dict__))          # device handles stay with the object they were made for
 
     def invert(self, a):
         a = np.atleast_2d(a)
@@ -320,39 +316,24 @@ class SSPSpace:
 
     # -- decoding --------------------------------------------------------------------------
     def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop("_decoder_cache", None)          # device handles stay with the object they were made for
-        state.pop("_encoder_cache", None)
-        state.pop("_binder_cache", None)
-        return state
+        return ServiceCache.strip(dict(self.__dict__))          # device handles stay with the object they were made for
 
     def _drop_decoders(self):
-        for dec in self.__dict__.pop("_decoder_cache", {}).values():
-            dec.close()
-        for enc in self.__dict__.pop("_encoder_cache", {}).values():
-            enc.close()
-        for binder in self.__dict__.pop("_binder_cache", {}).values():
-            binder.close()
+        """Close and forget every cached device service: decoders, encoders and binders."""
+        ServiceCache.drop_all(self)
 
     def _grid_decoder(self, num_samples, sampling_method, dtype, table="host"):
         """The GridDecoder of backend="hip" for this sample set, kept next to ``_grid_cache`` (one at a time: it holds the table on
         the GPU) and dropped by ``update_lengthscale``."""
         from .decoding import GridDecoder
         key = (int(num_samples), sampling_method, dtype) + (() if table == "host" else (table,))
-        if key not in self.__dict__.get("_decoder_cache", {}):
-            for dec in self.__dict__.pop("_decoder_cache", {}).values():
-                dec.close()
-            self._decoder_cache = {key: GridDecoder(self, num_samples, sampling_method, dtype=dtype, table=table)}
-        return self._decoder_cache[key]
+        return ServiceCache(self, "decoder", single=True).get(
+            key, lambda: GridDecoder(self, num_samples, sampling_method, dtype=dtype, table=table))
 
     def _ssp_encoder(self, dtype, device=0):
         """The SSPEncoder of backend="hip", one per (dtype, device), dropped by ``update_lengthscale`` like the decoder."""
         from .encoding import SSPEncoder
-        cache = self.__dict__.setdefault("_encoder_cache", {})
-        key = (dtype, int(device))
-        if key not in cache:
-            cache[key] = SSPEncoder(self, dtype=dtype, device=device)
-        return cache[key]
+        return ServiceCache(self, "encoder").get((dtype, int(device)), lambda: SSPEncoder(self, dtype=dtype, device=device))
 
     # -- sub-grid refinement ('grid-refine') ---------------------------------------------------
     def refine_tables(self):

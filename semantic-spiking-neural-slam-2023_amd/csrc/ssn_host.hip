@@ -2796,6 +2796,7 @@ struct Sim final : ssn_sim {
 
   // (diagnostic) the chain of binding hazards behind the last instance of a pipelined plan: what its period is made of
   void print_critical_chain(const RoundBuild& b, const std::vector<Inst>& all, const AccLists& accs) const {
+    if (all.empty()) return;        // (a model without a core - every operator time-batched - pipelines nothing: only the clock is stepped)
     size_t cur = 0;
     for (size_t i = 0; i < all.size(); ++i) if (all[i].round >= all[cur].round) cur = i;
     fprintf(stderr, "[ssn] critical chain (backwards from the last round):\n");

@@ -11,7 +11,7 @@
 //                              then a fixed xor butterfly - the same bits in every lane of every wave for any workgroup size.
 //                              Sa == 0 or Sb == 0: the output row is zero, exactly.  Otherwise q = ilogb(Sa / Sb),
 //                              e = floor((q + 1) / 2), s = 2^e: |a| / (s |b|) lies in [1 / sqrt 2, sqrt 2).  z = a + i s b.
-//                    forward   Z = FFT_d(z) (dft_stockham; through the chirp-z form when d is not smooth).
+//                    forward   Z = FFT_d(z) (dft_chirpz: dft_stockham, through the chirp-z form when d is not smooth).
 //                    separate  A_k = (Z_k + conj Z_{d-k}) / 2, s B_k = (Z_k - conj Z_{d-k}) / 2i, conj(A_k s B_k) for all d bins
 //                              into the other array; bin 0, and bin d / 2 of an even d, are Re Z * Im Z: real.
 //                    back      FFT_d of that: its real part is d s c_j.  Times 1 / d, then 2^-e (exact).
@@ -25,6 +25,8 @@
 // Scratch (fixed at creation, default 64 MB): per row of a chunk d doubles for each staged operand and d doubles of host output.
 // An entry never depends on the chunk its row is in, and there are no atomics, so the bits are the same for any scratch size, for
 // host and device operands of the same values and from run to run.
+// The route of a width - direct, or out-of-place Bluestein -, its tables, its workgroup and its LDS bytes are the planner's
+// (ssn_fft_plan.hpp: plan_stockham with in-place forbidden), shared with k_dft.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
@@ -33,14 +35,17 @@
 #include <vector>
 #include "../../include/ssn.h"
 #include "ssn_launch.hpp"
-#include "ssn_kernels.hpp"      // dft_stockham, cmulf
+#include "ssn_fft_plan.hpp"
+#include "ssn_kernels.hpp"      // dft_chirpz, cmulf
 #include "ssn_service.hpp"
 
 using namespace ssn::svc;      // fail, SVC_HIP, DevGuard, Lane, elapsed, stage_rows, check_rows
 
 namespace {
 
-constexpr int BIND_MAX_L = 6400;           // points of the longest transform: 153.6 KB of LDS (the planner's ceiling, plan_dft)
+namespace fft = ssn::fft;
+static_assert(sizeof(fft::cfloat) == sizeof(float2), "the planner's tables are uploaded as float2");
+constexpr int BIND_MAX_L = fft::MAX_POINTS;      // points of the longest transform: 153.6 KB of LDS
 constexpr int BIND_MAX_D64 = 10000;        // f64: 16 B of LDS per point
 enum { BIND_INVERT_A = 1, BIND_INVERT_B = 2, BIND_NORMALIZE = 4 };
 
@@ -52,7 +57,7 @@ struct BindArgs {
   long long row0;                          // output row of workgroup 0; `out` points at it
   int a64, b64, out64;                     // element types: 1 double, 0 float
   int d, L, M, nr;
-  int radix[12];
+  int radix[fft::MAX_RADICES];
   int flags;
   double norm_floor;
   const float2* tw;                        // exp(-2 pi i k / L)
@@ -72,28 +77,6 @@ __device__ __forceinline__ const void* operand_row(const void* base, int is64, l
 __device__ __forceinline__ double wave_sum(double s) {
   for (int w = 32; w >= 1; w >>= 1) s += __shfl_xor(s, w, 64);
   return s;
-}
-
-// FFT_d of what x holds (chirp-loaded and zero-padded to M for the chirp-z form); x then points at the result, y at the other array
-__device__ __forceinline__ void bind_fft(float2*& x, float2*& y, const float2* tw, const BindArgs& g, int tid, int nthr) {
-  const int L = g.L, d = g.d;
-  float2* r = ssn::dft_stockham(x, y, tw, L, g.radix, g.nr, tid, nthr);
-  if (r != x) { y = x; x = r; }
-  if (g.M > 0) {
-    // X_k = w_k (x w (*) conj w)_k: multiply the spectra, transform back (conj . FFT . conj; 1 / M folded into fb)
-    for (int i = tid; i < L; i += nthr) {
-      const float2 v = x[i], f = g.fb[i];
-      x[i] = make_float2(v.x * f.x - v.y * f.y, -(v.x * f.y + v.y * f.x));
-    }
-    __syncthreads();
-    r = ssn::dft_stockham(x, y, tw, L, g.radix, g.nr, tid, nthr);
-    if (r != x) { y = x; x = r; }
-    for (int i = tid; i < d; i += nthr) {
-      const float2 v = make_float2(x[i].x, -x[i].y), c = g.chirp[i];
-      x[i] = make_float2(v.x * c.x - v.y * c.y, v.x * c.y + v.y * c.x);
-    }
-    __syncthreads();
-  }
 }
 
 __global__ __launch_bounds__(1024) void k_bind_rows(const BindArgs g) {
@@ -142,7 +125,7 @@ __global__ __launch_bounds__(1024) void k_bind_rows(const BindArgs g) {
     x[i] = v;
   }
   __syncthreads();
-  bind_fft(x, y, tw, g, tid, nthr);
+  ssn::dft_chirpz(x, y, tw, L, g, d, tid, nthr);
   for (int k = tid; k < L; k += nthr) {
     float2 c = make_float2(0.0f, 0.0f);
     if (k < d) {
@@ -160,7 +143,7 @@ __global__ __launch_bounds__(1024) void k_bind_rows(const BindArgs g) {
   }
   __syncthreads();
   { float2* t2 = x; x = y; y = t2; }
-  bind_fft(x, y, tw, g, tid, nthr);
+  ssn::dft_chirpz(x, y, tw, L, g, d, tid, nthr);
   const float inv_d = 1.0f / (float)d;
   if (!(g.flags & BIND_NORMALIZE)) {
     for (int j = tid; j < d; j += nthr) {
@@ -242,90 +225,6 @@ __global__ __launch_bounds__(1024) void k_bind_direct(const BindArgs g) {
   }
 }
 
-// ---- the planner: the direct and out-of-place Bluestein routes of plan_dft (ssn_host.hip), restated ----
-std::vector<int> smooth_radices(int L) {
-  std::vector<int> primes;
-  int rest = L, twos = 0;
-  while (rest % 2 == 0) { ++twos; rest /= 2; }
-  for (int p = 3; p <= 32 && rest > 1; ++p)
-    while (rest % p == 0) { primes.push_back(p); rest /= p; }
-  if (rest != 1) return {};
-  std::vector<int> rad;
-  while (twos >= 3 && twos != 4) { rad.push_back(8); twos -= 3; }
-  while (twos >= 2) { rad.push_back(4); twos -= 2; }
-  if (twos) rad.push_back(2);
-  for (size_t i = 0; i < primes.size();) {
-    int r = primes[i++];
-    while (i < primes.size() && r * primes[i] <= 16) r *= primes[i++];
-    rad.push_back(r);
-  }
-  std::sort(rad.rbegin(), rad.rend());
-  return rad;
-}
-double stockham_cost(int L) {
-  const std::vector<int> rad = smooth_radices(L);
-  if (rad.empty() || rad.size() > 12) return -1.0;
-  double c = 0.0;
-  for (int r : rad) c += (r == 8 || r == 4 || r == 2) ? 1.0 : 0.25 * r + 0.5;
-  return c * L;
-}
-// -> false when no route fits in LDS
-bool plan_bind(int64_t d, int* M_out, std::vector<int>* rad_out) {
-  *M_out = 0;
-  rad_out->clear();
-  if (d < 2 || d > BIND_MAX_L) return false;
-  std::vector<int> rad = smooth_radices((int)d);
-  int M = 0;
-  if (rad.empty()) {
-    double best = -1.0;
-    for (int c = 2 * (int)d - 1; c <= BIND_MAX_L && c <= 2 * (2 * (int)d - 1); ++c) {
-      const double cost = stockham_cost(c);
-      if (cost > 0.0 && (best < 0.0 || cost < best)) { best = cost; M = c; }
-    }
-    if (best < 0.0) return false;
-    rad = smooth_radices(M);
-  }
-  if (rad.empty() || rad.size() > 12) return false;
-  *M_out = M;
-  *rad_out = rad;
-  return true;
-}
-
-std::vector<float2> twiddles(int L) {
-  std::vector<float2> h((size_t)L);
-  for (int k = 0; k < L; ++k) {
-    const double ang = -2.0 * M_PI * (double)k / (double)L;
-    h[(size_t)k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-  }
-  return h;
-}
-// chirp w_n = exp(-i pi n^2 / d), the phase reduced exactly (n^2 mod 2d), and the spectrum of its wrapped conjugate over M
-void chirp_tables(int d, int M, std::vector<float2>* w, std::vector<float2>* fb) {
-  w->assign((size_t)d, make_float2(0.0f, 0.0f));
-  fb->assign((size_t)M, make_float2(0.0f, 0.0f));
-  std::vector<double> br((size_t)M, 0.0), bi((size_t)M, 0.0), cs((size_t)M), sn((size_t)M);
-  std::vector<int> nz;
-  for (int n = 0; n < d; ++n) {
-    const long long q = ((long long)n * n) % (2LL * d);
-    const double ang = -M_PI * (double)q / (double)d;
-    (*w)[(size_t)n] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    br[(size_t)n] = std::cos(ang); bi[(size_t)n] = -std::sin(ang);
-    nz.push_back(n);
-    if (n) { br[(size_t)(M - n)] = std::cos(ang); bi[(size_t)(M - n)] = -std::sin(ang); nz.push_back(M - n); }
-  }
-  std::sort(nz.begin(), nz.end());
-  for (int k = 0; k < M; ++k) { cs[(size_t)k] = std::cos(-2.0 * M_PI * k / M); sn[(size_t)k] = std::sin(-2.0 * M_PI * k / M); }
-  for (int k = 0; k < M; ++k) {      // plain O(M d) float64 DFT, once per binder
-    double sr = 0.0, si = 0.0;
-    for (int n : nz) {
-      const size_t q = (size_t)(((long long)k * n) % M);
-      sr += br[(size_t)n] * cs[q] - bi[(size_t)n] * sn[q];
-      si += br[(size_t)n] * sn[q] + bi[(size_t)n] * cs[q];
-    }
-    (*fb)[(size_t)k] = make_float2((float)(sr / M), (float)(si / M));
-  }
-}
-
 }  // namespace
 
 struct ssn_binder : Lane {
@@ -351,7 +250,7 @@ struct ssn_binder : Lane {
 
 namespace {
 
-int upload(float2** dst, const std::vector<float2>& h) {
+int upload(float2** dst, const std::vector<fft::cfloat>& h) {
   SVC_HIP(hipMalloc((void**)dst, h.size() * sizeof(float2)));
   SVC_HIP(hipMemcpy(*dst, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
   return SSN_OK;
@@ -360,7 +259,7 @@ int upload(float2** dst, const std::vector<float2>& h) {
 hipError_t launch_bind(ssn_binder* bd, const BindArgs& g, int rows) {
   static std::atomic<uint64_t> configured32{0};
   if (bd->dtype == SSN_F32) {
-    if (hipError_t e = ssn::set_max_dynamic_lds_once(reinterpret_cast<const void*>(&k_bind_rows), BIND_MAX_L * 3 * (int)sizeof(float2), configured32); e != hipSuccess) return e;
+    if (hipError_t e = ssn::set_max_dynamic_lds_once(reinterpret_cast<const void*>(&k_bind_rows), fft::MAX_LDS_BYTES, configured32); e != hipSuccess) return e;
     hipLaunchKernelGGL(k_bind_rows, dim3((unsigned)rows), dim3((unsigned)bd->threads), (size_t)bd->lds_bytes, bd->stream, g);
   } else {
     switch ((int)((bd->d + bd->threads - 1) / bd->threads)) {
@@ -457,13 +356,14 @@ int ssn_binder_create(int32_t dtype, int32_t device, int64_t d, int64_t scratch_
   b->dtype = dtype;
   b->d = d;
   if (dtype == SSN_F32) {
-    if (!plan_bind(d, &b->M, &b->radix))
+    const fft::Route route = d <= BIND_MAX_L ? fft::plan_stockham((int)d, false) : fft::Route{};
+    if (!route)
       return fail(SSN_EUNSUPPORTED, "ssn_binder_create: SSN_EUNSUPPORTED: no f32 route for d %lld: a smooth d (prime factors <= 32) up to %d is transformed directly, "
                   "any other through a smooth M >= 2 d - 1 = %lld, and M <= %d points fit in LDS (the f64 binder takes d <= %d)", (long long)d, BIND_MAX_L,
                   (long long)(2 * d - 1), BIND_MAX_L, BIND_MAX_D64);
-    b->L = b->M > 0 ? b->M : (int)d;
-    b->threads = std::min(1024, std::max(64, ((b->L + 3) / 4 + 63) / 64 * 64));      // four points per thread (dft_stockham), as launch_dft
-    b->lds_bytes = (int64_t)b->L * 3 * (int64_t)sizeof(float2);
+    b->M = route.M; b->L = route.L; b->radix = route.radix;
+    b->threads = fft::threads(route);
+    b->lds_bytes = (int64_t)fft::lds_bytes(route);
   } else {
     if (d > BIND_MAX_D64)
       return fail(SSN_EUNSUPPORTED, "ssn_binder_create: SSN_EUNSUPPORTED: d %lld above %d, what the f64 binder holds in LDS (16 B per point)", (long long)d, BIND_MAX_D64);
@@ -474,12 +374,10 @@ int ssn_binder_create(int32_t dtype, int32_t device, int64_t d, int64_t scratch_
   if (const int rc = b->open("ssn_binder_create", device, scratch_bytes, b->min_scratch(), "row of d %lld", (long long)d)) return rc;
   DevGuard g(device);
   if (dtype == SSN_F32) {
-    if (const int rc = upload(&b->tw, twiddles(b->L))) return rc;
+    if (const int rc = upload(&b->tw, fft::twiddles(b->L))) return rc;
     if (b->M > 0) {
-      std::vector<float2> w, fb;
-      chirp_tables((int)d, b->M, &w, &fb);
-      if (const int rc = upload(&b->chirp, w)) return rc;
-      if (const int rc = upload(&b->fb, fb)) return rc;
+      if (const int rc = upload(&b->chirp, fft::chirp((int)d))) return rc;
+      if (const int rc = upload(&b->fb, fft::chirp_spectrum((int)d, b->M))) return rc;
     }
   }
   *out = b.release();

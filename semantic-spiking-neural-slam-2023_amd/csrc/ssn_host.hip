@@ -27,6 +27,7 @@
 
 #include "../../include/ssn.h"
 #include "ssn_launch.hpp"
+#include "ssn_fft_plan.hpp"
 #include "ssn_recall.hpp"
 
 namespace {
@@ -1019,178 +1020,48 @@ struct Sim final : ssn_sim {
     ens_chunking(a);
   }
 
-  // FFT plan of a DFT-structured matvec: radices (<= 32 each; runs of small primes are merged into radices <= 16, one
-  // stage and one workgroup barrier each) and the twiddle table.  A length with a prime factor > 32 (97, 1801,
-  // 2049 = 3 * 683) is planned as Bluestein's convolution of smooth length M >= 2d - 1.  N = 0 when no plan fits
-  // (LDS: 24 B per point of the longest transform, 32-bit index products) - the matrix is used then.
-  static std::vector<int> smooth_radices(int L) {
-    std::vector<int> primes;
-    int rest = L, twos = 0;
-    while (rest % 2 == 0) { ++twos; rest /= 2; }
-    for (int p = 3; p <= 32 && rest > 1; ++p)
-      while (rest % p == 0) { primes.push_back(p); rest /= p; }
-    if (rest != 1) return {};
-    std::sort(primes.begin(), primes.end());
-    std::vector<int> rad;
-    // factors of two: radix 8 / 4 / 2 passes run as in-register FFT butterflies (dft_pass_small) - eights, with a remainder
-    // of 2^1 as one radix-2 pass and of 2^4 as two fours
-    while (twos >= 3 && twos != 4) { rad.push_back(8); twos -= 3; }
-    while (twos >= 2) { rad.push_back(4); twos -= 2; }
-    if (twos) rad.push_back(2);
-    for (size_t i = 0; i < primes.size();) {           // greedy merge of ascending odd primes while the product stays <= 16
-      int r = primes[i++];
-      while (i < primes.size() && r * primes[i] <= 16) r *= primes[i++];
-      rad.push_back(r);
-    }
-    std::sort(rad.rbegin(), rad.rend());
-    return rad;
-  }
-  // relative cost of the Stockham passes of a length: a generic radix-r pass does r complex multiply-adds per point out of
-  // LDS, an in-register one (2, 4, 8) reads and writes each point once
-  static double stockham_cost(int L) {
-    const std::vector<int> rad = smooth_radices(L);
-    if (rad.empty() || rad.size() > 12) return -1.0;
-    double c = 0.0;
-    for (int r : rad) c += (r == 8 || r == 4 || r == 2) ? 1.0 : 0.25 * r + 0.5;
-    return c * L;
-  }
-
+  // FFT plan of a DFT-structured matvec: route and tables come from ssn_fft_plan.hpp; the simulator's own part is the cache of
+  // uploaded tables, the kernel's arguments and the SSN_DEBUG_PLAN listing.  N = 0 when no route fits - the matrix is used then.
   // Injective key of a table: what it is (kind) and every size its contents depend on - a network with circular convolutions
   // of two different lengths must never be handed the other length's table.
   enum { DK_TWIDDLE = 1, DK_CHIRP = 2, DK_CHIRP_SPECTRUM = 3, DK_CHIRP_SPECTRUM_INPLACE = 4, DK_DFT4_G1 = 5, DK_DFT4_G2 = 6 };
   static int64_t dft_key(int kind, int a, int b = 0) { return ((int64_t)kind << 56) | ((int64_t)(uint32_t)a << 28) | (int64_t)(uint32_t)b; }
-  int dft_table(int64_t key, const std::vector<float2>& h, float2** out) {
-    for (auto& t : dft_tables) if (t.first == key) { *out = t.second; return SSN_OK; }
-    float2* d = nullptr;
-    CHK(dupload(&d, h));
-    dft_tables.push_back({key, d});
+  // the table behind a key, made (make() -> host vector) and uploaded the first time it is asked for
+  template <typename P, typename Make>
+  int dft_table(int64_t key, Make make, const P** out) {
+    for (auto& t : dft_tables) if (t.first == key) { *out = (const P*)t.second; return SSN_OK; }
+    const auto h = make();
+    static_assert(sizeof(h[0]) == sizeof(P), "a table is uploaded as it lies on the host");
+    P* d = nullptr;
+    CHK(dupload(&d, (const P*)h.data(), (int64_t)h.size()));
+    dft_tables.push_back({key, (float2*)d});
     *out = d;
     return SSN_OK;
   }
-
-  static std::vector<float2> twiddles(int L) {
-    std::vector<float2> h((size_t)L);
-    for (int k = 0; k < L; ++k) {
-      const double ang = -2.0 * M_PI * (double)k / (double)L;
-      h[(size_t)k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-    }
-    return h;
-  }
-
-  // ---- four-step transform on the matrix cores (dft4_fft): the split L = N1 * N2 and the two DFT matrices in MFMA lane order ----
-  // cost of a split in MFMA instructions (16 x 16 x 4, two per k step: real and imaginary rows / columns)
-  static long long dft4_cost(int N1, int N2, bool complex_in) {
-    const long long P1 = (N1 + 15) / 16, C1 = (N2 + 15) / 16, N1p = (N1 + 3) / 4 * 4, N2p = (N2 + 3) / 4 * 4;
-    return P1 * C1 * ((complex_in ? 2 : 1) * N1p / 4) * 2 + P1 * C1 * (2 * N2p / 4) * 2;
-  }
-  // best (N1, N2) with N1 * N2 = L, N2 <= 192 (the step-3 matrix is (2 N2)^2 floats); {0, 0} if L has no such divisor pair
-  static std::pair<int, int> dft4_split(int L, bool complex_in) {
-    std::pair<int, int> best{0, 0};
-    long long bc = -1;
-    for (int n1 = 1; n1 <= L; ++n1) {
-      if (L % n1) continue;
-      const int n2 = L / n1;
-      if (n2 > 192 || n1 > 192) continue;
-      const long long c = dft4_cost(n1, n2, complex_in);
-      if (bc < 0 || c < bc) { bc = c; best = {n1, n2}; }
-    }
-    return best;
-  }
-  int dft4_tables(int N1, int N2, const float** g1_out, const float** g2_out) {
-    const int64_t key1 = dft_key(DK_DFT4_G1, N1, N2), key2 = dft_key(DK_DFT4_G2, N1, N2);
-    for (auto& t : dft_tables) if (t.first == key1) *g1_out = (const float*)t.second;
-    for (auto& t : dft_tables) if (t.first == key2) *g2_out = (const float*)t.second;
-    if (*g1_out && *g2_out) return SSN_OK;
-    const int P1 = (N1 + 15) / 16, Q2 = (N2 + 15) / 16, N1p = (N1 + 3) / 4 * 4, N2p = (N2 + 3) / 4 * 4;
-    const int KS1 = 2 * N1p / 4, KS3 = 2 * N2p / 4;
-    std::vector<float> g1((size_t)P1 * 2 * KS1 * 64, 0.0f), g2((size_t)Q2 * 2 * KS3 * 64, 0.0f);
-    for (int p = 0; p < P1; ++p)
-      for (int part = 0; part < 2; ++part)
-        for (int ks = 0; ks < KS1; ++ks)
-          for (int l = 0; l < 64; ++l) {
-            const int k1 = 16 * p + (l & 15), k = 4 * ks + (l >> 4);
-            const int n1 = k < N1p ? k : k - N1p;
-            if (k1 >= N1 || n1 >= N1) continue;
-            const double th = 2.0 * M_PI * (double)(((long long)k1 * n1) % N1) / (double)N1;
-            // F = cos - i sin: re out = cos xr + sin xi, im out = -sin xr + cos xi
-            const double v = part == 0 ? (k < N1p ? std::cos(th) : std::sin(th)) : (k < N1p ? -std::sin(th) : std::cos(th));
-            g1[(((size_t)p * 2 + part) * KS1 + ks) * 64 + l] = (float)v;
-          }
-    for (int q = 0; q < Q2; ++q)
-      for (int part = 0; part < 2; ++part)
-        for (int ks = 0; ks < KS3; ++ks)
-          for (int l = 0; l < 64; ++l) {
-            const int k2 = 16 * q + (l & 15), k = 4 * ks + (l >> 4);
-            const int n2 = k < N2p ? k : k - N2p;
-            if (k2 >= N2 || n2 >= N2) continue;
-            const double ph = 2.0 * M_PI * (double)(((long long)k2 * n2) % N2) / (double)N2;
-            // Xr = Br cos + Bi sin, Xi = -Br sin + Bi cos
-            const double v = part == 0 ? (k < N2p ? std::cos(ph) : std::sin(ph)) : (k < N2p ? -std::sin(ph) : std::cos(ph));
-            g2[(((size_t)q * 2 + part) * KS3 + ks) * 64 + l] = (float)v;
-          }
-    float* d1 = nullptr; float* d2 = nullptr;
-    CHK(dupload(&d1, g1));
-    CHK(dupload(&d2, g2));
-    dft_tables.push_back({key1, (float2*)d1}); dft_tables.push_back({key2, (float2*)d2});
-    *g1_out = d1; *g2_out = d2;
-    return SSN_OK;
-  }
-
   int plan_dft(const ssn_op_desc& o, ssn::DftArgs* a) {
+    namespace fft = ssn::fft;
     const int kind = (int)o.i[6];
     const int d = kind == 5 ? (int)o.i[2] : (int)o.i[3];
     *a = ssn::DftArgs{};
-    if (d < 8 || d > 6400) return SSN_OK;
-    if (opt.has(SSN_PLAN_FOUR_STEP_FFT)) {
-      // opt-in (round 3, measured slower than the Stockham passes as built - DESIGN.md): the four-step transform on the matrix
-      // cores; a length without a usable divisor pair (a prime above 192, or 2 x such a prime ...) goes through Bluestein's
-      // convolution of the cheapest length M in [2d - 1, 2d - 1 + 12 %]
-      std::pair<int, int> sp = dft4_split(d, kind == 5);
-      int M = 0;
-      if (!sp.first) {
-        long long bc = -1;
-        for (int c = 2 * d - 1; c <= 6400 && c <= (2 * d - 1) + (2 * d - 1) / 8; ++c) {
-          const std::pair<int, int> s2 = dft4_split(c, true);
-          if (!s2.first) continue;
-          const long long cost = dft4_cost(s2.first, s2.second, true);
-          if (bc < 0 || cost < bc) { bc = cost; M = c; sp = s2; }
-        }
-      }
-      if (sp.first) {
-        const int L = M > 0 ? M : d;
-        float2* tw = nullptr;
-        CHK(dft_table(dft_key(DK_TWIDDLE, L), twiddles(L), &tw));
-        if (M > 0) CHK(bluestein_tables(d, M, a));
-        const float* g1 = nullptr; const float* g2 = nullptr;
-        CHK(dft4_tables(sp.first, sp.second, &g1, &g2));
-        a->src = (const float*)(sig + o.i[1]); a->dst = (float*)(sig + o.i[0]); a->tw = tw; a->N = d; a->kind = kind;
-        a->set = (int)o.i[5]; a->nr = 0; a->N1 = sp.first; a->N2 = sp.second; a->g1 = g1; a->g2 = g2;
-        list_dft(*a);
-        return SSN_OK;
-      }
+    if (d < 8) return SSN_OK;
+    fft::Route r;
+    // opt-in (round 3, measured slower than the Stockham passes as built - DESIGN.md): the four-step transform on the matrix cores
+    if (opt.has(SSN_PLAN_FOUR_STEP_FFT)) r = fft::plan_four_step(d, kind == 5);
+    if (!r) r = fft::plan_stockham(d, !opt.dft_no_inplace);
+    if (!r) return SSN_OK;
+    CHK(dft_table(dft_key(DK_TWIDDLE, r.L), [&] { return fft::twiddles(r.L); }, &a->tw));
+    if (r.M > 0) {      // (the spectrum depends on d, M and the engine)
+      CHK(dft_table(dft_key(DK_CHIRP, d), [&] { return fft::chirp(d); }, &a->chirp));
+      CHK(dft_table(dft_key(r.inplace ? DK_CHIRP_SPECTRUM_INPLACE : DK_CHIRP_SPECTRUM, d, r.M),
+                    [&] { return fft::chirp_spectrum(d, r.M, r.inplace ? &r.radix : nullptr); }, &a->fb));
     }
-    std::vector<int> rad = smooth_radices(d);
-    int L = d, M = 0;
-    if (rad.empty()) {
-      // the cheapest smooth length in [2d - 1, 2 (2d - 1)] (a power of two where one fits: four radix-8 passes at 4096)
-      double best = -1.0;
-      for (int c = 2 * d - 1; c <= 6400 && c <= 2 * (2 * d - 1); ++c) {
-        const double cost = stockham_cost(c);
-        if (cost > 0.0 && (best < 0.0 || cost < best)) { best = cost; M = c; }
-      }
-      if (best < 0.0) return SSN_OK;
-      rad = smooth_radices(M);
-      L = M;
+    if (r.N1 > 0) {
+      CHK(dft_table(dft_key(DK_DFT4_G1, r.N1, r.N2), [&] { return fft::dft4_matrix(r.N1); }, &a->g1));
+      CHK(dft_table(dft_key(DK_DFT4_G2, r.N1, r.N2), [&] { return fft::dft4_matrix(r.N2); }, &a->g2));
     }
-    if (rad.empty() || rad.size() > 12) return SSN_OK;
-    float2* tw = nullptr;
-    CHK(dft_table(dft_key(DK_TWIDDLE, L), twiddles(L), &tw));
-    bool small_only = M > 0 && !opt.dft_no_inplace;          // every pass an in-register one: both transforms in place
-    for (int r : rad) small_only = small_only && (r == 8 || r == 4 || r == 2);
-    if (M > 0) CHK(bluestein_tables(d, M, a, small_only ? &rad : nullptr));
-    a->src = (const float*)(sig + o.i[1]); a->dst = (float*)(sig + o.i[0]); a->tw = tw; a->N = d; a->kind = kind;
-    a->set = (int)o.i[5]; a->nr = (int)rad.size();
-    for (size_t i = 0; i < rad.size(); ++i) a->radix[i] = rad[i];
+    a->src = (const float*)(sig + o.i[1]); a->dst = (float*)(sig + o.i[0]); a->N = d; a->kind = kind; a->set = (int)o.i[5];
+    a->M = r.M; a->inplace = r.inplace; a->N1 = r.N1; a->N2 = r.N2; a->nr = (int)r.radix.size();
+    for (size_t i = 0; i < r.radix.size(); ++i) a->radix[i] = r.radix[i];
     list_dft(*a);
     return SSN_OK;
   }
@@ -1200,51 +1071,6 @@ struct Sim final : ssn_sim {
     fprintf(stderr, "[ssn] dft kind %d N %d M %d inplace %d split %dx%d radices", a.kind, a.N, a.M, a.inplace, a.N1, a.N2);
     for (int i = 0; i < a.nr; ++i) fprintf(stderr, " %d", a.radix[i]);
     fprintf(stderr, "\n");
-  }
-
-  // position of frequency k after the in-place decimation-in-frequency passes with radices rad[0], rad[1], ...
-  static int dif_position(int k, int M, const std::vector<int>& rad) {
-    int pos = 0, len = M;
-    for (int r : rad) { len /= r; pos += (k % r) * len; k /= r; }
-    return pos;
-  }
-  int bluestein_tables(int d, int M, ssn::DftArgs* a, const std::vector<int>* inplace_radices = nullptr) {
-    {
-      // chirp w_n = exp(-i pi n^2 / d) with the phase reduced exactly (n^2 mod 2d), and the spectrum of its wrapped conjugate
-      std::vector<float2> w((size_t)d);
-      std::vector<double> br((size_t)M, 0.0), bi((size_t)M, 0.0);
-      for (int n = 0; n < d; ++n) {
-        const long long q = ((long long)n * n) % (2LL * d);
-        const double ang = -M_PI * (double)q / (double)d;
-        w[(size_t)n] = make_float2((float)std::cos(ang), (float)std::sin(ang));
-        br[(size_t)n] = std::cos(ang); bi[(size_t)n] = -std::sin(ang);
-        if (n) { br[(size_t)(M - n)] = std::cos(ang); bi[(size_t)(M - n)] = -std::sin(ang); }
-      }
-      std::vector<float2> fb((size_t)M);
-      std::vector<double> cs((size_t)M), sn((size_t)M);
-      for (int k = 0; k < M; ++k) { cs[(size_t)k] = std::cos(-2.0 * M_PI * k / M); sn[(size_t)k] = std::sin(-2.0 * M_PI * k / M); }
-      std::vector<int> nzn;
-      for (int n = 0; n < M; ++n) if (br[(size_t)n] != 0.0 || bi[(size_t)n] != 0.0) nzn.push_back(n);
-      for (int k = 0; k < M; ++k) {                     // plain O(M d) double DFT, once per length at build time (M <= 6400)
-        double sr = 0.0, si = 0.0;
-        for (int n : nzn) {
-          const size_t q = (size_t)(((long long)k * n) % M);
-          sr += br[(size_t)n] * cs[q] - bi[(size_t)n] * sn[q];
-          si += br[(size_t)n] * sn[q] + bi[(size_t)n] * cs[q];
-        }
-        fb[(size_t)k] = make_float2((float)(sr / M), (float)(si / M));
-      }
-      float2* dw = nullptr; float2* dfb = nullptr;
-      CHK(dft_table(dft_key(DK_CHIRP, d), w, &dw));
-      if (inplace_radices) {                             // the in-place engine multiplies in digit-reversed order
-        std::vector<float2> fp((size_t)M);
-        for (int k = 0; k < M; ++k) fp[(size_t)dif_position(k, M, *inplace_radices)] = fb[(size_t)k];
-        fb.swap(fp);
-      }
-      CHK(dft_table(dft_key(inplace_radices ? DK_CHIRP_SPECTRUM_INPLACE : DK_CHIRP_SPECTRUM, d, M), fb, &dfb));     // (the spectrum depends on d, M and the engine)
-      a->M = M; a->chirp = dw; a->fb = dfb; a->inplace = inplace_radices ? 1 : 0;
-    }
-    return SSN_OK;
   }
 
   // Neuron order for the whole-block kernel (f32).  k_ens_block leaves out the spike-time arithmetic and the decode of a
@@ -2410,13 +2236,7 @@ struct Sim final : ssn_sim {
   // longest glue operator a single workgroup takes (default 2048 elements).
   // LDS bytes of a transform as a round body
   static size_t dft_lds(const Item& it) {
-    size_t lds = (size_t)(it.dft.M > 0 ? it.dft.M : it.dft.N) * (it.dft.N1 > 0 ? 4 * sizeof(float) : 3 * sizeof(float2));
-    if (it.dft.inplace) {                         // in place: M + M / 8 points + M / (smallest radix) twiddles
-      int rmin = 8;
-      for (int q = 0; q < it.dft.nr; ++q) rmin = std::min(rmin, it.dft.radix[q]);
-      lds = (size_t)(it.dft.M + it.dft.M / 8 + it.dft.M / rmin) * sizeof(float2);
-    }
-    return lds;
+    return ssn::fft::lds_bytes(it.dft.M > 0 ? it.dft.M : it.dft.N, it.dft.inplace != 0, it.dft.N1, it.dft.radix, it.dft.nr);
   }
   double solo_lat(const Unit& u) const {        // estimated serial time of the unit on one workgroup; < 0: not eligible
     const bool solo_on = !(phased && !opt.phased_solo) && !opt.has(SSN_PLAN_NO_CHAINS) && opt.solo_chains;

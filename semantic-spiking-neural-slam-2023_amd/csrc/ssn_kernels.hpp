@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "ssn_launch.hpp"
+#include "ssn_fft_plan.hpp"
 #include "ssn_micro.hpp"
 
 namespace ssn {
@@ -707,7 +708,7 @@ __device__ inline float2* dft_stockham(float2* x, float2* y, const float2* tw, i
       continue;
     }
     for (int o0 = tid; o0 < L; o0 += nthr * U) {
-      // (all products below stay under 2^32: p j fn < L * 32, L <= 6400, see plan_dft)
+      // (all products below stay under 2^32: p j fn < L * 32, L <= fft::MAX_POINTS)
       int idx[U], stp[U];
       const float2* xi[U];
       float2 acc[U];
@@ -895,6 +896,31 @@ __device__ __forceinline__ void dft4_body(const DftArgs& a, unsigned char* ssn_d
   }
 }
 
+// FFT_d of what x holds, one of the two LDS arrays x and y (L points each; tw: the L twiddles): on return x points at the result
+// and y at the other array.  M = 0: the Stockham passes of a smooth d = L.  M > 0 (L = M): the chirp-z form - x holds x_n w_n,
+// zero-padded to M, and X_k = w_k (x w (*) conj w)_k for the first n_out bins: the spectra multiplied (fb, 1 / M folded in),
+// transformed back as conj . FFT . conj, times the chirp.  k_bind_rows runs it twice per row.  dft_body keeps its own copy of these
+// lines: through this function k_dft came out one SGPR larger (70 for 69, all else equal), and the step path is to pay nothing.
+template <typename A>      // (A: BindArgs, DftArgs - radix, nr, M, fb, chirp; read where they are used, as the radix list is)
+__device__ __forceinline__ void dft_chirpz(float2*& x, float2*& y, const float2* tw, int L, const A& a, int n_out, int tid, int nthr) {
+  float2* r = dft_stockham(x, y, tw, L, a.radix, a.nr, tid, nthr);
+  if (r != x) { y = x; x = r; }
+  if (a.M > 0) {
+    for (int i = tid; i < L; i += nthr) {
+      const float2 v = x[i], f = a.fb[i];
+      x[i] = make_float2(v.x * f.x - v.y * f.y, -(v.x * f.y + v.y * f.x));
+    }
+    __syncthreads();
+    r = dft_stockham(x, y, tw, L, a.radix, a.nr, tid, nthr);
+    if (r != x) { y = x; x = r; }
+    for (int i = tid; i < n_out; i += nthr) {
+      const float2 v = make_float2(x[i].x, -x[i].y), c = a.chirp[i];
+      x[i] = make_float2(v.x * c.x - v.y * c.y, v.x * c.y + v.y * c.x);
+    }
+    __syncthreads();
+  }
+}
+
 // (ROUND = true: the body inside k_round never runs the four-step engine - its MFMA accumulators would add 8 AGPRs to the
 //  round kernel and take every body of every round from 7 to 6 waves per SIMD; such transforms are launched on their own)
 // Bluestein's convolution with both transforms in place (DftArgs::inplace): one LDS array of M points.
@@ -1035,15 +1061,11 @@ template <typename T>
 hipError_t launch_dft(hipStream_t s, const DftBatch& b, int count) {
   int N = 0;
   for (int i = 0; i < count; ++i) N = std::max(N, b.a[i].M > 0 ? b.a[i].M : b.a[i].N);
-  int threads = std::min(1024, std::max(64, ((N + 3) / 4 + 63) / 64 * 64));      // four output points per thread (dft_stockham)
-  if (b.a[0].inplace) threads = std::min(1024, std::max(64, (N / 8 + 63) / 64 * 64));                // one radix-8 group per thread and pass
-  if (b.a[0].N1 > 0) {                // four-step: one wave per tile task of the larger step (at most 16 waves)
-    const int tasks = ((b.a[0].N1 + 15) / 16) * ((b.a[0].N2 + 15) / 16);
-    threads = std::min(1024, std::max(256, tasks * 64));
-  }
+  const int threads = fft::threads(N, b.a[0].inplace != 0, b.a[0].N1, b.a[0].N2);
   static std::atomic<uint64_t> configured{0};
-  if (hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(&k_dft<0>), 6400 * 3 * (int)sizeof(float2), configured); e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_dft<0>), dim3(count), dim3(threads), (size_t)N * 3 * sizeof(float2), s, b);
+  if (hipError_t e = set_max_dynamic_lds_once(reinterpret_cast<const void*>(&k_dft<0>), fft::MAX_LDS_BYTES, configured); e != hipSuccess) return e;
+  // (every engine is given the Stockham engine's bytes, the largest of the three)
+  hipLaunchKernelGGL((k_dft<0>), dim3(count), dim3(threads), (size_t)N * fft::STOCKHAM_POINT_BYTES, s, b);
   return hipGetLastError();
 }
 

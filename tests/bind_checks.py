@@ -28,7 +28,8 @@ What the stand-in showed about balancing: without it (``no-balance``) a pair wit
 separation ``(Z_k - conj Z_{d-k}) / 2i`` subtracts numbers of size ``|A_k|`` to get ``|B_k|``; with ``s = 2^e`` from the two sums of
 squares every pair of ``pairs(d)`` - ratios 2^+-20 included - stays at the ratio dense pairs have.  The packed form is kept.
 
-``plan`` restates the binder's planner (``plan_bind`` of csrc/ssn_bind.hip); wrong binders (``MUTANTS``) are switches of the stand-in.
+``plan`` restates the binder's planner (``plan_stockham`` of csrc/ssn_fft_plan.hpp with the in-place engine forbidden, from d = 2, as
+``ssn_binder_create`` of csrc/ssn_bind.hip calls it); wrong binders (``MUTANTS``) are switches of the stand-in.
 """
 import functools
 

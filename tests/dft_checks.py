@@ -29,7 +29,8 @@ the chirp spectrum, whose 1-norm can reach sqrt(d) times ||x||_1 although its re
 multiply-adds - and the twiddle product: ``2 N1 + 2 N2 + 7``.  Measured, the stand-in's worst case stays a factor of 7 (direct) to 160
 (four-step Bluestein) below these at the length where it occurs: rounding errors do not align.
 
-``plan`` restates the planner (``smooth_radices``, ``dft4_split``, ``plan_dft`` of csrc/ssn_host.hip); the GPU tests hold it to
+``plan`` restates the planner (``smooth_radices``, ``dft4_split``, ``plan_stockham``, ``plan_four_step`` of csrc/ssn_fft_plan.hpp and
+the bounds of ``plan_dft`` in csrc/ssn_host.hip); tests/test_fft_plan.py holds the planner to it on a CPU, the GPU tests hold it to
 the planner's own listing under SSN_DEBUG_PLAN for every swept length, and the stand-in is driven by it.
 
 Wrong devices (``MUTANTS``) that each have to fail the bar on the CPU are switches of the stand-in.

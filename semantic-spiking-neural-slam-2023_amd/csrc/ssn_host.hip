@@ -95,49 +95,8 @@ enum ItemType { IT_PROGRAM = 0, IT_ENS, IT_MATVEC, IT_NEURONS, IT_PES, IT_VOJA, 
                 IT_MATVEC_NEURONS,  // (round plan) a dense population's encoder product with the neuron update in its epilogue
                 IT_NONE };          // (round plan) an operator that was folded into another one
 
-// What the planner asks about a micro-operator kind (ssn::MicroKind): one row per kind, one flag per question.  What a kind
-// reads and writes is Sim::micro_access; every "is it one of these kinds" is a lookup here.
-enum MicroKindFlag {
-  MK_SAME_THREAD = 1,   // element-wise in a program, element p of a range on thread (p - origin) mod 1024: follows an operator it depends on
-                        // without a barrier when their origins agree (push_micro); a glue member of a serial chain (solo_lat)
-  MK_VECOPS = 2,        // may move into the grid-wide head of the item plan (k_vecops)
-  MK_CUT = 4,           // cut at the range endpoints of the other operators (split_micro)
-  MK_CHAIN = 8,         // may join a chain of element-aligned operators (chainable)
-  MK_GLUE_ROW = 16,     // a glue block takes GLUE_ROWS rows of it, not GLUE_CHUNK elements (emit)
-  MK_BATCH_EW = 32,     // time-batched stage: element-wise, shares a launch with its neighbours (batch_hazard, run_batch)
-  MK_BATCH_R = 64,      // time-batched stage: reads src
-  MK_BATCH_W = 128,     // time-batched stage: writes dst
-  MK_BATCH_PRODUCT = 256 // time-batched stage: a matrix product - reads `cols` elements of src, not `len` (batch_read_len, run_batch)
-};
-// A kind appended to ssn::MicroKind takes: the enum (ssn_launch.hpp), one `case` in ssn_micro.hpp (what it computes - every
-// kernel that runs micro-operators calls that one definition), its row below (without one it would read as "no flags") and its
-// row in Sim::micro_access (what it reads and writes).
-static_assert(ssn::M_LINCOMB == 17, "MICRO_KINDS has a row for every MicroKind up to M_LINCOMB: add the new kind's");
-struct MicroKindTable {
-  unsigned short f[ssn::M_LINCOMB + 1] = {};
-  constexpr MicroKindTable() {
-    f[ssn::M_FILL] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN | MK_BATCH_EW | MK_BATCH_W;
-    f[ssn::M_AXPY_INC] = f[ssn::M_AXPY_SET] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN | MK_BATCH_EW | MK_BATCH_R | MK_BATCH_W;
-    f[ssn::M_LOWPASS] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN | MK_BATCH_R | MK_BATCH_W;
-    f[ssn::M_TABLE] = MK_SAME_THREAD | MK_VECOPS | MK_CHAIN | MK_BATCH_EW | MK_BATCH_W;
-    f[ssn::M_ROW_IN] = MK_SAME_THREAD | MK_VECOPS | MK_CUT | MK_CHAIN;
-    f[ssn::M_ROW_OUT] = MK_SAME_THREAD | MK_CUT | MK_CHAIN;
-    f[ssn::M_PROBE] = MK_SAME_THREAD | MK_CHAIN | MK_BATCH_EW | MK_BATCH_R;
-    f[ssn::M_LINCOMB] = MK_CUT | MK_CHAIN;
-    f[ssn::M_REDUCE_SET] = f[ssn::M_REDUCE_INC] = MK_CHAIN | MK_GLUE_ROW;
-    f[ssn::M_MATVEC_INC] = f[ssn::M_MATVEC_SET] = MK_GLUE_ROW | MK_BATCH_R | MK_BATCH_W | MK_BATCH_PRODUCT;
-    f[ssn::M_ENS_FINISH] = MK_GLUE_ROW;
-    // M_GATE, M_ARGMAX_GATHER, M_STEP_END: none
-  }
-};
-constexpr MicroKindTable MICRO_KINDS;
-constexpr bool kind_is(int kind, int flag) { return kind > 0 && kind <= ssn::M_LINCOMB && (MICRO_KINDS.f[kind] & flag) != 0; }
-// (the round kernel chunks an operator by ssn::micro_row_kind, the planner counts its blocks by MK_GLUE_ROW)
-constexpr bool glue_rows_agree() {
-  for (int k = 0; k <= ssn::M_LINCOMB + 1; ++k) if (kind_is(k, MK_GLUE_ROW) != ssn::micro_row_kind(k)) return false;
-  return true;
-}
-static_assert(glue_rows_agree(), "MK_GLUE_ROW and ssn::micro_row_kind name different kinds");
+// What the planner asks about a micro-operator kind - ssn::kind_is(kind, ssn::MK_*) - is one table in ssn_micro_kinds.hpp.
+using ssn::kind_is;
 
 // Plan options: ssn_model_desc.flags and the environment knobs, read once at ssn_create and constant for the simulator's
 // life.  PlanOptions::read is the only caller of getenv in the library.  One row per knob: how the variable is read, the
@@ -368,7 +327,8 @@ struct Sim final : ssn_sim {
   std::vector<int64_t> seg_spikes;                                       // spike signals whose list is segmented
   std::vector<std::pair<int64_t, float2*>> dft_tables;                  // dft_key(kind, sizes) -> table (twiddles, chirps, spectra, DFT matrices)
   std::vector<ssn::BatchOp<T>> pre_ops, post_ops;
-  int batch_skipped = 0;                      // products of the batched stages whose whole input was zero over a block (run_batch)
+  std::vector<ssn::stage::Launch> pre_launches, post_launches;      // the launches over them (optimise_batch)
+  int batch_skipped = 0;                     // products of the batched stages whose whole input was zero over a block (run_batch)
   std::vector<ssn_range> pre_to_core, core_to_post;
   std::vector<unsigned char> batched_mask;    // signals owned by a batched stage (for ssn_read_signal)
   std::vector<MOp> mops;                     // [head][middle programs...][tail][head copy]
@@ -403,11 +363,10 @@ struct Sim final : ssn_sim {
 
   ssn::StepCtx* d_ctx = nullptr;
   std::vector<ssn::TableSlot> tables;
-  // host copy of every table's row index per step, and where each table's rows land in the signal vector: a time-batched
-  // product whose whole input is a table that is zero for the whole block (the init-SSP input of the path integrator after
-  // its first 50 ms, reference run_pathint.py:136) is not multiplied out - its result rows are zero-filled instead
+  // host copy of every table's row index per step: a time-batched product whose whole input is a table that is zero for the
+  // whole block (the init-SSP input of the path integrator after its first 50 ms, reference run_pathint.py:136) is not
+  // multiplied out - its result rows are zero-filled instead
   std::vector<std::vector<int32_t>> table_idx_host;
-  std::vector<std::pair<long long, long long>> table_dst;      // (signal offset, width) per table id; width 0: unknown
   ssn::TableSlot* d_tables = nullptr;
   std::vector<DevBuf> table_rows, table_idx;
   // staged tables (ssn_stage_table / ssn_commit_tables): the NEXT chunk's inputs arrive in a second set of buffers by DMA on the
@@ -1415,11 +1374,11 @@ struct Sim final : ssn_sim {
     // shared element to the same thread (equal range starts modulo 1024): program order inside the thread suffices.
     // (Here and for the grid-wide head below, an empty range that lies inside another one counts as touching it: keep_empty.)
     auto level_change_needs_barrier = [&](const MOp& op) -> bool {
-      if (!kind_is(op.kind, MK_SAME_THREAD)) return true;
+      if (!kind_is(op.kind, ssn::MK_SAME_THREAD)) return true;
       std::vector<Rng> mine, theirs;
       micro_access(mine, op, false, true);
       for (size_t q = cur.size(); q-- > 0;) {             // operators since the last barrier
-        if (!kind_is(cur[q].kind, MK_SAME_THREAD)) return true;
+        if (!kind_is(cur[q].kind, ssn::MK_SAME_THREAD)) return true;
         theirs.clear();
         micro_access(theirs, cur[q], false, true);
         for (const Rng& x : mine)
@@ -1486,10 +1445,7 @@ struct Sim final : ssn_sim {
         switch (o.kind) {
           case SSN_OP_FILL: b.kind = ssn::M_FILL; b.dst = o.i[0]; b.len = o.i[1]; b.a = (T)o.f[0]; wlo = o.i[0]; wlen = o.i[1]; break;
           case SSN_OP_TABLE: b.kind = ssn::M_TABLE; b.dst = o.i[0]; b.len = o.i[1]; b.p0 = d_tables + o.i[2];
-            tables[o.i[2]].width = o.i[1]; wlo = o.i[0]; wlen = o.i[1];
-            if (table_dst.size() < tables.size()) table_dst.resize(tables.size(), {0, 0});
-            table_dst[(size_t)o.i[2]] = {o.i[0], o.i[1]};
-            break;
+            tables[o.i[2]].width = o.i[1]; wlo = o.i[0]; wlen = o.i[1]; break;
           case SSN_OP_AXPY: b.kind = o.i[3] ? ssn::M_AXPY_SET : ssn::M_AXPY_INC; b.dst = o.i[0]; b.src = o.i[1]; b.len = o.i[2];
             b.a = (T)o.f[0]; wlo = o.i[0]; wlen = o.i[2]; break;
           case SSN_OP_LOWPASS: b.kind = ssn::M_LOWPASS; b.dst = o.i[0]; b.src = o.i[1]; b.len = o.i[2];
@@ -1747,8 +1703,8 @@ struct Sim final : ssn_sim {
       push_micro(op, -2, first_probe);
       first_probe = false;
     }
-    optimise_batch(pre_ops);
-    optimise_batch(post_ops);
+    optimise_batch(pre_ops, pre_launches);
+    optimise_batch(post_ops, post_launches);
     if (!fused) {
       MOp end{};
       end.kind = ssn::M_STEP_END;
@@ -1818,7 +1774,7 @@ struct Sim final : ssn_sim {
       std::vector<Rng> moved, mine;                    // what the prefix so far reads and writes
       for (; lv < head.size() && (lv == 0 || !head[lv].barrier); ++lv) {
         const MOp& q = head[lv];
-        if (!kind_is(q.kind, MK_VECOPS)) break;
+        if (!kind_is(q.kind, ssn::MK_VECOPS)) break;
         mine.clear();
         micro_access(mine, q, false, true);
         if (hazard(mine, moved)) break;
@@ -2145,7 +2101,7 @@ struct Sim final : ssn_sim {
     return cuts;
   }
   int split_micro(const MOp& op, const std::vector<int64_t>& cuts, std::vector<MOp>& out) {
-    if (!kind_is(op.kind, MK_CUT) || op.len <= 1 || opt.has(SSN_PLAN_NO_CUTS)) { out.push_back(op); return SSN_OK; }
+    if (!kind_is(op.kind, ssn::MK_CUT) || op.len <= 1 || opt.has(SSN_PLAN_NO_CUTS)) { out.push_back(op); return SSN_OK; }
     std::vector<Rng> operands;                        // (their origins in signal space: every one is op.len long)
     micro_access(operands, op);
     const std::vector<ssn::LinTerm<T>>* terms = nullptr;
@@ -2215,7 +2171,7 @@ struct Sim final : ssn_sim {
   // behind that update) joins their round - one block then runs the chain's operators back to back on 256 elements, the
   // same thread on the same index in program order, with no barrier and no launch between them.
   bool chainable(const Unit& u) const {
-    return u.mop >= 0 && !opt.has(SSN_PLAN_NO_CHAINS) && kind_is(mops[(size_t)u.mop].kind, MK_CHAIN);
+    return u.mop >= 0 && !opt.has(SSN_PLAN_NO_CHAINS) && kind_is(mops[(size_t)u.mop].kind, ssn::MK_CHAIN);
   }
   // Serial chains (round 4, second half).  The long loop of a SLAM timestep - clean-up -> binding -> memory -> unbinding -> gate ->
   // oscillator input, one synapse delay per hop - is partly made of operators that ONE workgroup executes: glue over 1 - 2
@@ -2245,7 +2201,7 @@ struct Sim final : ssn_sim {
       const MOp& op = mops[(size_t)u.mop];
       // (measured on the chains of SLAM config 3: ~2 us per glue member - one trip for its data, one for the store to land
       //  before the barrier - with its descriptor already in LDS; a transform ~9.5 us)
-      if (kind_is(op.kind, MK_SAME_THREAD))
+      if (kind_is(op.kind, ssn::MK_SAME_THREAD))
         return op.len <= opt.solo_max_len ? 1.7 + 0.5 * (double)((op.len + ssn::GLUE_CHUNK - 1) / ssn::GLUE_CHUNK) : -1.0;
       switch (op.kind) {
         case ssn::M_GATE: case ssn::M_ARGMAX_GATHER: return 3.5;
@@ -2552,7 +2508,7 @@ struct Sim final : ssn_sim {
           for (int c = 0; c < blocks; ++c) b.glue_map.push_back(ssn::GlueBlock{-(ofs + 1), c});
           continue;
         }
-        const long long per = kind_is(op.kind, MK_GLUE_ROW) ? ssn::GLUE_ROWS : ssn::GLUE_CHUNK;
+        const long long per = kind_is(op.kind, ssn::MK_GLUE_ROW) ? ssn::GLUE_ROWS : ssn::GLUE_CHUNK;
         const int chunks = (int)std::max<long long>(1, (op.len + per - 1) / per);
         for (int c = 0; c < chunks; ++c) b.glue_map.push_back(ssn::GlueBlock{u.mop, c | (in->sub << 24)});
       }
@@ -3025,158 +2981,56 @@ struct Sim final : ssn_sim {
     return SSN_OK;
   }
 
-  // Element-wise operators of a time-batched stage: what they write / read (column ranges; rows are handled alike).
-  static bool batch_elementwise(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_EW); }
-  static bool batch_writes(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_W); }
-  static bool batch_reads(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_R); }
-  static long long batch_read_len(const ssn::BatchOp<T>& o) { return kind_is(o.kind, MK_BATCH_PRODUCT) ? o.cols : o.len; }
-  // Hazard between two operators of a stage, `a` the earlier one.  0: none; 1: only on elements that both touch at the SAME
-  // index of the same row (equal range origins, no previous-row read of what the other writes) - two element-wise operators
-  // may then share a launch, the same thread runs them in order (kb_elementwise_multi); 2: anything else.
-  static int batch_hazard(const ssn::BatchOp<T>& a, const ssn::BatchOp<T>& b) {
-    auto ov = [](long long x, long long xl, long long y, long long yl) { return x < y + yl && y < x + xl; };
-    int kind = 0;
-    auto pair = [&](long long x, long long xl, long long y, long long yl, bool prev) {
-      if (!ov(x, xl, y, yl)) return;
-      kind = std::max(kind, (x == y && !prev) ? 1 : 2);
-    };
-    if (batch_writes(a) && batch_writes(b)) pair(a.dst, a.len, b.dst, b.len, false);
-    if (batch_writes(a) && batch_reads(b)) pair(a.dst, a.len, b.src, batch_read_len(b), b.src_prev != 0);
-    if (batch_reads(a) && batch_writes(b)) pair(a.src, batch_read_len(a), b.dst, b.len, a.src_prev != 0);
-    if (kind == 1 && !(batch_elementwise(a) && batch_elementwise(b))) kind = 2;
-    return kind;
+  // Order and launches of a time-batched stage (ssn_stage_plan.hpp), once at plan(): neither depends on the block.
+  void optimise_batch(std::vector<ssn::BatchOp<T>>& ops, std::vector<ssn::stage::Launch>& launches) {
+    if (ops.size() >= 2 && !opt.no_batch_reorder) {
+      std::vector<ssn::BatchOp<T>> out = ssn::stage::optimise(ops);
+      if (opt.debug_plan) {
+        fprintf(stderr, "[ssn] time-batched stage: %zu operators -> %zu\n", ops.size(), out.size());
+        for (const ssn::BatchOp<T>& o : out) fprintf(stderr, "[ssn]   batch op kind %d dst %lld src %lld len %lld cols %d prev %d\n", o.kind, (long long)o.dst, (long long)o.src, (long long)o.len, o.cols, o.src_prev);
+      }
+      ops.swap(out);
+    }
+    launches = ssn::stage::pack(ops, !opt.has(SSN_PLAN_NO_STAGE_BATCH));
   }
 
-  // Order of a time-batched stage: the builder hands its operators over in one valid order (stages.py `border`), in which
-  // independent operators of different kinds alternate (a scan, the sum that reads it, the next scan ...) and every one is
-  // a launch.  Here: resets and sums are cut at the range endpoints of the other operators (the reset of all accumulators
-  // of a network then lines up with each consumer), every operator takes the earliest dependency level its hazards allow,
-  // operators are sorted by level and kind, and neighbouring scans with equal coefficients over adjacent ranges are joined
-  // again.  run_batch then packs consecutive element-wise operators - also dependent ones, see batch_hazard - into launches.
-  void optimise_batch(std::vector<ssn::BatchOp<T>>& ops) {
-    if (ops.size() < 2 || opt.no_batch_reorder) return;
-    typedef ssn::BatchOp<T> Op;
-    std::vector<long long> cuts;
-    for (const Op& o : ops) {
-      if (batch_writes(o)) { cuts.push_back(o.dst); cuts.push_back(o.dst + o.len); }
-      if (batch_reads(o)) { cuts.push_back(o.src); cuts.push_back(o.src + batch_read_len(o)); }
-    }
-    std::sort(cuts.begin(), cuts.end());
-    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-    std::vector<Op> cut;
-    for (const Op& o : ops) {
-      const bool axpy = o.kind == ssn::M_AXPY_INC || o.kind == ssn::M_AXPY_SET;
-      if (!(axpy || o.kind == ssn::M_FILL) || o.len <= 1) { cut.push_back(o); continue; }
-      std::vector<long long> offs{0, o.len};
-      for (long long base : {o.dst, axpy ? o.src : o.dst}) {
-        auto lo = std::upper_bound(cuts.begin(), cuts.end(), base), hi = std::lower_bound(cuts.begin(), cuts.end(), base + o.len);
-        for (auto it = lo; it < hi; ++it) offs.push_back(*it - base);
-      }
-      std::sort(offs.begin(), offs.end());
-      offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-      if (offs.size() > 32) { cut.push_back(o); continue; }
-      for (size_t q = 0; q + 1 < offs.size(); ++q) {
-        Op pc = o;
-        pc.dst = o.dst + offs[q]; pc.len = offs[q + 1] - offs[q];
-        if (axpy) pc.src = o.src + offs[q];
-        cut.push_back(pc);
-      }
-    }
-    const size_t n = cut.size();
-    std::vector<int> level(n, 0);
-    for (size_t j = 0; j < n; ++j)
-      for (size_t i = 0; i < j; ++i)
-        if (batch_hazard(cut[i], cut[j])) level[j] = std::max(level[j], level[i] + 1);
-    auto cls = [](const Op& o) { return batch_elementwise(o) ? 0 : o.kind == ssn::M_LOWPASS ? 1 : 2; };
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) {
-      if (level[x] != level[y]) return level[x] < level[y];
-      if (cls(cut[x]) != cls(cut[y])) return cls(cut[x]) < cls(cut[y]);
-      return cut[x].kind == ssn::M_LOWPASS && cut[y].kind == ssn::M_LOWPASS && cut[x].dst < cut[y].dst;
-    });
-    std::vector<Op> out;
-    int last_level = -1;
-    for (size_t k : order) {
-      const Op& o = cut[k];
-      if (!out.empty() && level[k] == last_level && o.kind == ssn::M_LOWPASS && out.back().kind == ssn::M_LOWPASS && out.back().a == o.a && out.back().b == o.b &&
-          out.back().src_prev == o.src_prev && out.back().dst + out.back().len == o.dst && out.back().src + out.back().len == o.src) {
-        out.back().len += o.len;
-        continue;
-      }
-      out.push_back(o);
-      last_level = level[k];
-    }
-    if (opt.debug_plan) {
-      fprintf(stderr, "[ssn] time-batched stage: %zu operators -> %zu\n", ops.size(), out.size());
-      for (const Op& o : out) fprintf(stderr, "[ssn]   batch op kind %d dst %lld src %lld len %lld cols %d prev %d\n", o.kind, (long long)o.dst, (long long)o.src, (long long)o.len, o.cols, o.src_prev);
-    }
-    ops.swap(out);
-  }
-
-  hipError_t run_batch(std::vector<ssn::BatchOp<T>>& ops, int B, int64_t step0) {
-    auto elementwise = [](const ssn::BatchOp<T>& o) { return batch_elementwise(o); };
-    // Signal elements known to be ZERO in every row of this block: a table without an entry for any timestep of the block
-    // (the init-SSP input of the path integrator after its first 50 ms, reference run_pathint.py:136), and what fills /
-    // copies / products make of zeros.  A product whose whole input is zero is not multiplied out (PathIntegration config 2:
-    // the 1000 x 1015 x 1524 to_Fourier GEMM of every block but the first - 47 of a block's 3480 us).
-    std::vector<char> zero((size_t)n_sig, 0);
-    const bool track = !opt.no_zero_skip;
-    auto all_zero = [&](long long lo, long long n) { for (long long q = lo; q < lo + n; ++q) if (!zero[(size_t)q]) return false; return n > 0; };
-    auto set_zero = [&](long long lo, long long n, bool v) { for (long long q = lo; q < lo + n; ++q) zero[(size_t)q] = v ? 1 : 0; };
+  // One block of a stage: its launches in order, products of nothing but zeros left out (stage::ZeroMap).
+  hipError_t run_batch(std::vector<ssn::BatchOp<T>>& ops, const std::vector<ssn::stage::Launch>& launches, int B, int64_t step0) {
+    ssn::stage::ZeroMap<T> zeros(n_sig, !opt.no_zero_skip);
     auto note = [&](const ssn::BatchOp<T>& o) {              // effect of an operator that IS executed on the zero map
-      if (!track) return;
-      switch (o.kind) {
-        case ssn::M_TABLE: {
-          bool z = false;
-          for (size_t id = 0; id < table_dst.size() && id < table_idx_host.size(); ++id)
-            if (table_dst[id].second > 0 && table_dst[id].first == o.dst && table_dst[id].second == o.len) z = table_is_zero((int)id, B, step0);
-          set_zero(o.dst, o.len, z); break;
-        }
-        case ssn::M_FILL: set_zero(o.dst, o.len, o.a == T(0)); break;
-        case ssn::M_AXPY_SET: set_zero(o.dst, o.len, !o.src_prev && all_zero(o.src, o.len)); break;
-        case ssn::M_AXPY_INC: if (o.src_prev || !all_zero(o.src, o.len)) set_zero(o.dst, o.len, false); break;
-        case ssn::M_PROBE: break;
-        default: set_zero(o.dst, o.len, false); break;          // products, filters: not known
+      bool z = false;
+      if (o.kind == ssn::M_TABLE && !opt.no_zero_skip) {
+        // the table's id from its slot: plan() makes p0 = d_tables + id and the (dst, len) that used to be searched for from the
+        // same o.i[2], and every table operator has a signal range of its own - so the slot names the table the search found
+        const size_t id = (size_t)((const ssn::TableSlot*)o.p0 - d_tables);
+        z = id < table_idx_host.size() && table_is_zero((int)id, B, step0);
       }
+      zeros.note(o, z);
     };
-    for (size_t i = 0; i < ops.size();) {
-      ops[i].B = B; ops[i].step0 = step0;
-      if (elementwise(ops[i]) && !opt.has(SSN_PLAN_NO_STAGE_BATCH)) {
-        // consecutive element-wise operators share one launch unless a hazard between them crosses threads (batch_hazard)
-        ssn::BatchOpList<T> l{};
-        l.op[0] = ops[i];
-        l.count = 1;
-        size_t j = i + 1;
-        for (; j < ops.size() && l.count < ssn::MAX_BATCH_OPS && elementwise(ops[j]); ++j) {
-          ops[j].B = B; ops[j].step0 = step0;
-          bool clash = false;
-          for (int q = 0; q < l.count; ++q) clash = clash || batch_hazard(l.op[q], ops[j]) == 2;
-          if (clash) break;
-          l.op[l.count++] = ops[j];
-        }
-        if (l.count > 1) {
-          hipError_t e = ssn::launch_batch_elementwise<T>(stream, l);
-          if (e != hipSuccess) return e;
-          for (int q = 0; q < l.count; ++q) note(l.op[q]);      // (list order = program order of every thread)
-          i = j;
-          continue;
-        }
-      }
-      if (track && kind_is(ops[i].kind, MK_BATCH_PRODUCT) && !ops[i].src_prev && all_zero(ops[i].src, ops[i].cols)) {
-        ++batch_skipped;
-        if (ops[i].kind == ssn::M_MATVEC_SET) {        // W @ 0: the result rows of the block are zero (an increment adds nothing)
-          hipError_t e = hipMemset2DAsync(bsig + n_sig + ops[i].dst, (size_t)n_sig * sizeof(T), 0, (size_t)ops[i].len * sizeof(T), (size_t)B, stream);
-          if (e != hipSuccess) return e;
-          set_zero(ops[i].dst, ops[i].len, true);
-        }
-        ++i;
+    for (const ssn::stage::Launch& l : launches) {
+      for (int q = 0; q < l.count; ++q) { ops[(size_t)(l.first + q)].B = B; ops[(size_t)(l.first + q)].step0 = step0; }
+      const ssn::BatchOp<T>& o = ops[(size_t)l.first];
+      if (l.count > 1) {
+        ssn::BatchOpList<T> list{};
+        std::copy_n(&o, l.count, list.op);
+        list.count = l.count;
+        hipError_t e = ssn::launch_batch_elementwise<T>(stream, list);
+        if (e != hipSuccess) return e;
+        for (int q = 0; q < l.count; ++q) note(list.op[q]);      // (list order = program order of every thread)
         continue;
       }
-      hipError_t e = ssn::launch_batch_op<T>(stream, ops[i]);
+      if (zeros.skippable(o)) {
+        ++batch_skipped;
+        if (o.kind == ssn::M_MATVEC_SET) {        // W @ 0: the result rows of the block are zero (an increment adds nothing)
+          hipError_t e = hipMemset2DAsync(bsig + n_sig + o.dst, (size_t)n_sig * sizeof(T), 0, (size_t)o.len * sizeof(T), (size_t)B, stream);
+          if (e != hipSuccess) return e;
+        }
+        zeros.note_skipped(o);
+        continue;
+      }
+      hipError_t e = ssn::launch_batch_op<T>(stream, o);
       if (e != hipSuccess) return e;
-      note(ops[i]);
-      ++i;
+      note(o);
     }
     return hipSuccess;
   }
@@ -3551,7 +3405,7 @@ struct Sim final : ssn_sim {
       if (bsig) {
         hipLaunchKernelGGL(k_set_block, dim3(1), dim3(1), 0, stream, d_ctx, (long long)step0);
         HIPCHK(hipGetLastError());
-        HIPCHK(run_batch(pre_ops, (int)B, step0));
+        HIPCHK(run_batch(pre_ops, pre_launches, (int)B, step0));
       }
       if (fused_defer) HIPCHK(ssn::launch_ens_finish<T>(stream, fin_begin));
       if (fused_block) {
@@ -3587,7 +3441,7 @@ struct Sim final : ssn_sim {
       }
       if (fused_defer) HIPCHK(ssn::launch_ens_finish<T>(stream, fin_flush));
       if (bsig) {
-        HIPCHK(run_batch(post_ops, (int)B, step0));
+        HIPCHK(run_batch(post_ops, post_launches, (int)B, step0));
         HIPCHK(hipMemcpyAsync(bsig, bsig + (size_t)B * n_sig, (size_t)n_sig * sizeof(T), hipMemcpyDeviceToDevice, stream));
       }
       done += B;

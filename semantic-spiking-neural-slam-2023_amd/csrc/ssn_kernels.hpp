@@ -1174,7 +1174,7 @@ __global__ __launch_bounds__(1024) void k_program(const MicroOp<T>* __restrict__
 
 // k_vecops: the first level of a timestep's head program when it is long (SLAM config 3: ~100 k elements of resets
 // and hand-offs from the pre stage) - independent element-wise operators, executed grid-wide instead of by the
-// program's single workgroup.  (The planner moves no probe here: MK_VECOPS, ssn_host.hip.)
+// program's single workgroup.  (The planner moves no probe here: MK_VECOPS, ssn_micro_kinds.hpp.)
 template <typename T>
 struct GridWalk {
   long long gtid, gsz, now;
@@ -1777,7 +1777,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void kb_elementwise(BatchOp<T> o) { kb_elementwise_body<T>(o); }
 // Several element-wise operators of a time-batched stage in one launch (a launch costs ~5 us + the gap behind it).  Thread
 // (t, i) runs element i of row t of EVERY operator of the list, in list order: operators may depend on each other where
-// both touch a signal element at the same index i of the same row (ssn_host.hip run_batch checks: equal range origins, no
+// both touch a signal element at the same index i of the same row (stage::pack, ssn_stage_plan.hpp, checks: equal range origins, no
 // previous-row read in between) - a reset, the sums into it and the hand-off of the result are one launch.
 constexpr int KB_MULTI_ROWS = 8;      // rows per workgroup of kb_elementwise_multi (independent iterations: eight accesses in flight per thread)
 template <typename T>
@@ -2135,24 +2135,28 @@ hipError_t launch_gemm_nt(hipStream_t s, const T* A, int lda, const T* Wm, int l
 
 template <typename T>
 hipError_t launch_batch_op(hipStream_t s, const BatchOp<T>& o) {
-  if (o.B <= 0 || o.len <= 0) return hipSuccess;
-  if (o.kind == M_LOWPASS) {
-    if constexpr (sizeof(T) == 4) {
-      if (o.B >= 256) {
+  switch (stage::kernel_for(o.kind, o.len, o.cols, o.B, sizeof(T) == 4)) {
+    case stage::KB_NOTHING: return hipSuccess;
+    case stage::KB_LOWPASS_CHUNKED:
+      if constexpr (sizeof(T) == 4)
         hipLaunchKernelGGL((kb_lowpass_chunked<32, 32>), dim3((unsigned)((o.len + 31) / 32)), dim3(1024), 0, s, o);
-        return hipGetLastError();
-      }
+      break;
+    case stage::KB_LOWPASS:
+      hipLaunchKernelGGL((kb_lowpass<T>), dim3((unsigned)((o.len + 63) / 64)), dim3(64), 0, s, o);
+      break;
+    case stage::KB_GEMM_MFMA_F32:
+      if constexpr (sizeof(T) == 4)
+        hipLaunchKernelGGL((kb_gemm_mfma_f32<32>), dim3((unsigned)((o.len + 63) / 64), (unsigned)((o.B + 63) / 64)), dim3(1024), 0, s, o);
+      break;
+    case stage::KB_GEMM:
+      hipLaunchKernelGGL((kb_gemm<T>), dim3((unsigned)((o.len + 31) / 32), (unsigned)((o.B + 31) / 32)), dim3(256), 0, s, o);
+      break;
+    case stage::KB_ELEMENTWISE: {
+      const long long total = (long long)o.B * o.len;
+      const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+      hipLaunchKernelGGL((kb_elementwise<T>), dim3(grid), dim3(256), 0, s, o);
+      break;
     }
-    hipLaunchKernelGGL((kb_lowpass<T>), dim3((unsigned)((o.len + 63) / 64)), dim3(64), 0, s, o);
-  } else if ((o.kind == M_MATVEC_INC || o.kind == M_MATVEC_SET) && sizeof(T) == 4 && o.cols >= 64 && o.len >= 32 && o.B >= 32) {
-    if constexpr (sizeof(T) == 4)
-      hipLaunchKernelGGL((kb_gemm_mfma_f32<32>), dim3((unsigned)((o.len + 63) / 64), (unsigned)((o.B + 63) / 64)), dim3(1024), 0, s, o);
-  } else if (o.kind == M_MATVEC_INC || o.kind == M_MATVEC_SET) {
-    hipLaunchKernelGGL((kb_gemm<T>), dim3((unsigned)((o.len + 31) / 32), (unsigned)((o.B + 31) / 32)), dim3(256), 0, s, o);
-  } else {
-    const long long total = (long long)o.B * o.len;
-    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL((kb_elementwise<T>), dim3(grid), dim3(256), 0, s, o);
   }
   return hipGetLastError();
 }

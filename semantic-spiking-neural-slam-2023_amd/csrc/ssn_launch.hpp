@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include "ssn_stage_plan.hpp"      // MicroKind (ssn_micro_kinds.hpp), BatchOp, BatchOpList
 
 namespace ssn {
 
@@ -200,17 +201,7 @@ template <typename T> struct SpmvBatch { SpmvArgs<T> a[MAX_BATCH]; };
 constexpr int MAX_ENS_BATCH = 2;
 template <typename T> struct EnsBatch { EnsArgs<T> a[MAX_ENS_BATCH]; };
 
-enum MicroKind {
-  M_FILL = 1, M_AXPY_INC, M_AXPY_SET, M_LOWPASS, M_TABLE, M_MATVEC_INC, M_MATVEC_SET, M_ENS_FINISH,
-  M_GATE, M_ARGMAX_GATHER, M_PROBE, M_STEP_END, M_ROW_IN, M_ROW_OUT, M_REDUCE_SET, M_REDUCE_INC,
-  M_LINCOMB            // dst = a * dst + b * (c + sum_k alpha_k * sig[src_k + i]); p0 = LinTerm[i0]
-};
-template <typename T> struct LinTerm { long long src; T alpha; };
-// Row kinds: one thread computes one output row (micro_row, ssn_micro.hpp), so a block of the round kernel takes GLUE_ROWS rows
-// of them where it takes GLUE_CHUNK elements of an element-wise kind.  Kernels and planner (MK_GLUE_ROW) both ask here.
-constexpr bool micro_row_kind(int kind) {
-  return kind == M_MATVEC_INC || kind == M_MATVEC_SET || kind == M_ENS_FINISH || kind == M_REDUCE_SET || kind == M_REDUCE_INC;
-}
+template <typename T> struct LinTerm { long long src; T alpha; };      // (M_LINCOMB, ssn_micro_kinds.hpp)
 
 template <typename T>
 struct MicroOp {
@@ -243,22 +234,6 @@ struct StepCtx {
   int pad;
   long long block_start; // step number at which the current time-batched block began
   long long finished;    // deferred-finish cores: last step whose finish has been applied
-};
-
-// One operator of a time-batched stage, executed for rows t = 0..B-1 of the block.  Row r of the block
-// buffer `bsig` ([B+1][n_sig]) holds the signals after step (block_start + r); row 0 is the carry-in.
-template <typename T>
-struct BatchOp {
-  T* bsig;
-  long long n_sig;       // row stride
-  int B;
-  int kind;              // MicroKind (M_FILL, M_AXPY_*, M_LOWPASS, M_TABLE, M_MATVEC_*, M_PROBE)
-  long long dst, src, len;   // len = rows for matvec
-  int cols, ld;
-  int src_prev;          // 1: read row t (value before this step's update) instead of row t+1
-  T a, b;
-  const void* p0;        // W | TableSlot* | ProbeSlot*
-  long long step0;       // = block_start
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -327,8 +302,6 @@ template <typename T> hipError_t launch_round(hipStream_t, const RoundArgs<T>&, 
 constexpr int GLUE_CHUNK = 1024;
 constexpr int GLUE_ROWS = 256;
 
-constexpr int MAX_BATCH_OPS = 24;
-template <typename T> struct BatchOpList { BatchOp<T> op[MAX_BATCH_OPS]; int count; };
 template <typename T> hipError_t launch_batch_elementwise(hipStream_t, const BatchOpList<T>&);   // independent element-wise ops, one launch
 
 template <typename T> hipError_t launch_ensarray(hipStream_t, const EnsArgs<T>&);

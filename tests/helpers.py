@@ -1,8 +1,41 @@
-"""Test helpers: an oracle-backed stand-in with the Simulator's Python surface (tests only)."""
+"""Test helpers: an oracle-backed stand-in with the Simulator's Python surface, and the host compiler for the planners' dump
+programs (tests only)."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
+import pytest
 
 import sspslam_amd.frontend as nengo
 from oracle import OracleSimulator
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "semantic-spiking-neural-slam-2023_amd", "csrc")
+
+
+def _compiler():
+    for name in ("c++", "g++", "clang++"):
+        if shutil.which(name):
+            return shutil.which(name)
+    for root in (os.environ.get("ROCM_PATH"), "/opt/rocm"):
+        for rel in ("llvm/bin/clang++", "lib/llvm/bin/clang++", "bin/amdclang++"):
+            if root and os.path.exists(os.path.join(root, rel)):
+                return os.path.join(root, rel)
+    return None
+
+
+def compiled_dump(tmp_path_factory, name):
+    """The body of a session fixture: csrc/<name>.cpp (a planner header's stand-alone dump program) compiled once with the host
+    compiler -> ``run(*args, stdin=None)``, its stdout.  Skips without a compiler."""
+    cxx = _compiler()
+    if cxx is None:
+        pytest.skip("no C++ compiler on PATH or under the ROCm install")
+    exe = str(tmp_path_factory.mktemp(name) / name)
+    subprocess.run([cxx, "-std=c++17", "-O2", os.path.join(CSRC, name + ".cpp"), "-o", exe], check=True)
+
+    def run(*args, stdin=None):
+        return subprocess.run([exe] + [str(a) for a in args], check=True, capture_output=True, text=True, input=stdin).stdout
+    return run
 
 
 class OracleBackedSimulator:

@@ -1,9 +1,10 @@
 """The instrument of the time-batched stage tests (tests only; neither a test module nor a conftest).
 
 The feed-forward half of every model runs a block of B timesteps at a time through a runtime of its own: ``stages.py`` marks the
-operators, ``optimise_batch`` / ``run_batch`` (csrc/ssn_host.hip) order, pack and zero-skip them, ``launch_batch_op``
-(csrc/ssn_kernels.hpp) picks ``kb_gemm`` / ``kb_gemm_mfma_f32`` and ``kb_lowpass`` / ``kb_lowpass_chunked``, row B of the block buffer
-becomes row 0 of the next block.  Here every operator of such a stage, at every step, is held to a float64 evaluation of the same
+operators, ``stage::optimise`` / ``stage::pack`` / ``stage::ZeroMap`` (csrc/ssn_stage_plan.hpp; ``Sim::run_batch`` of
+csrc/ssn_host.hip walks what they planned) order, pack and zero-skip them, ``stage::kernel_for`` picks ``kb_gemm`` /
+``kb_gemm_mfma_f32`` and ``kb_lowpass`` / ``kb_lowpass_chunked`` for ``launch_batch_op`` (csrc/ssn_kernels.hpp), row B of the block
+buffer becomes row 0 of the next block.  Here every operator of such a stage, at every step, is held to a float64 evaluation of the same
 operator list under a first-order bound, on models without neurons (every operator has ``stage == 2`` and the device reports
 ``launches_per_step == 0``: all it computes runs time-batched).
 
@@ -38,14 +39,15 @@ The chunked scan's own term
     cuts=)`` applies this per block of 256 steps or more; the sequential kernels and f64 keep the plain recursion.
 
 The stand-in (``StandIn``)
-    NumPy float32 restatement of what the kernels do: the stage's operators cut, levelled, sorted and re-joined as ``optimise_batch``
+    NumPy float32 restatement of what the kernels do: the stage's operators cut, levelled, sorted and re-joined as ``stage::optimise``
     does (``optimise``; the GPU tests hold it to the library's own listing under SSN_DEBUG_PLAN), packed into lists of at most 24 as
-    ``run_batch`` does, with its zero map; a k-sequential fused-multiply-add chain per output element for both GEMMs; the sequential
-    scan and the 32-chunk scan with its ``pw`` products; one persistent block buffer whose row B is copied to row 0; ``src_prev``.  It
+    ``stage::pack`` does (``pack``), with the zero map of ``stage::ZeroMap`` (``zero_walk``) - tests/test_stage_plan.py holds the
+    header itself to these three, ``hazard`` and ``dispatch`` on a CPU; a k-sequential fused-multiply-add chain per output element for
+    both GEMMs; the sequential scan and the 32-chunk scan with its ``pw`` products; one persistent block buffer whose row B is copied to row 0; ``src_prev``.  It
     proves that the bars hold and are not slack (tests/test_stages.py: error <= half a bar everywhere, median bound / error <= 64 per
     operator kind), and its switches are the wrong devices (``MUTANTS``) that each have to fail a case of the GPU module's list.
 
-``dispatch`` restates ``launch_batch_op``'s choice of kernel; ``parse_listing`` reads the ``[ssn]   batch op kind ...`` lines.
+``dispatch`` restates the choice of kernel (``stage::kernel_for``); ``parse_listing`` reads the ``[ssn]   batch op kind ...`` lines.
 ``expected_skips`` derives ``batch_products_skipped`` from input windows and block cuts alone.
 """
 import contextlib
@@ -159,7 +161,7 @@ def _read_len(o):
 
 
 def hazard(a, b):
-    """``batch_hazard``: 0 none; 1 only on elements both touch at the same index of the same row (two element-wise operators may then
+    """``stage::hazard``: 0 none; 1 only on elements both touch at the same index of the same row (two element-wise operators may then
     share a launch); 2 anything else."""
     kind = 0
 
@@ -180,7 +182,7 @@ def hazard(a, b):
 
 
 def optimise(ops, real=np.float32):
-    """``optimise_batch``: resets and sums cut at the range endpoints of the other operators (kept whole beyond 32 pieces), every
+    """``stage::optimise``: resets and sums cut at the range endpoints of the other operators (kept whole beyond 32 pieces), every
     operator at the earliest level its hazards allow, sorted by level and class, neighbouring scans with equal coefficients joined."""
     if len(ops) < 2:
         return [dict(o) for o in ops]
@@ -227,7 +229,7 @@ def optimise(ops, real=np.float32):
 
 
 def pack(ops, stage_batch=True, drop_overflow=False):
-    """``run_batch``'s launches: [('list', [operators])] for consecutive element-wise operators without a cross-thread hazard, at most
+    """The launches of ``stage::pack``: [('list', [operators])] for consecutive element-wise operators without a cross-thread hazard, at most
     24 to a list, [('op', operator)] for everything else (a list of one is an ordinary launch).  ``drop_overflow``: the wrong device
     that loses the operator a full list has no slot for."""
     out, i = [], 0
@@ -251,6 +253,41 @@ def pack(ops, stage_batch=True, drop_overflow=False):
     return out
 
 
+def zero_walk(ops, table_zero_per_block, zero_skip=True, skip_prev=False, inc_as_set=False):
+    """The zero map of ``run_batch`` (``stage::ZeroMap``) over the operators a block executes, in order: which signal elements are zero
+    in every row of the block, and the products that are therefore not multiplied out.  ``table_zero_per_block``: per block {table
+    id: the table has no stored row in the block}.  -> per block {index of a skipped product: its rows are marked zero (a ``set``)}.
+    ``skip_prev`` / ``inc_as_set``: the wrong devices that skip a previous-row product / clear the rows of a skipped increment."""
+    n = max([0] + [o["dst"] + o["len"] for o in ops] + [o["src"] + _read_len(o) for o in ops])
+    out = []
+    for table_zero in table_zero_per_block:
+        zero = np.zeros(n, dtype=bool)
+        all_zero = lambda lo, k: k > 0 and bool(zero[lo:lo + k].all())
+        skipped = {}
+        for i, o in enumerate(ops):
+            k, d = o["kind"], slice(o["dst"], o["dst"] + o["len"])
+            if not zero_skip:
+                continue
+            if k in PRODUCTS and (not o["prev"] or skip_prev) and all_zero(o["src"], o["cols"]):
+                skipped[i] = k == K_MATVEC_SET or inc_as_set
+                if skipped[i]:
+                    zero[d] = True
+                continue
+            if k == K_TABLE:
+                zero[d] = bool(table_zero[o["table"]])
+            elif k == K_FILL:
+                zero[d] = o["a"] == 0
+            elif k == K_AXPY_SET:
+                zero[d] = (not o["prev"]) and all_zero(o["src"], o["len"])
+            elif k == K_AXPY_INC:
+                if o["prev"] or not all_zero(o["src"], o["len"]):
+                    zero[d] = False
+            elif k != K_PROBE:
+                zero[d] = False
+        out.append(skipped)
+    return out
+
+
 def plan_key(ops):
     """What a listing line carries, for every operator but the probe samples' pointers: (kind, dst, src, len, cols, prev)."""
     return [(o["kind"], o["dst"], o["src"], o["len"], o["cols"], o["prev"]) for o in ops]
@@ -263,7 +300,7 @@ def parse_listing(err):
 
 
 def dispatch(kind, length, cols, B, f32=True):
-    """``launch_batch_op``: the kernel one operator of a block of B steps goes to (None: nothing is launched)."""
+    """``stage::kernel_for``: the kernel one operator of a block of B steps goes to (None: nothing is launched)."""
     if B <= 0 or length <= 0:
         return None
     if kind == K_LOWPASS:
@@ -496,38 +533,24 @@ class StandIn:
         return not fn.stored(range(step0 + 1, step0 + B + 1)).any()
 
     def _block(self, B, step0):
-        zero = np.zeros(self.model.sig_size, dtype=bool)
         prev = lambda o: o["prev"] and self.mutant != "no-src-prev"
-
-        def note(o):
-            if not self.zero_skip:
-                return
-            k, d = o["kind"], slice(o["dst"], o["dst"] + o["len"])
-            if k == K_TABLE:
-                zero[d] = self._table_zero(o, B, step0)
-            elif k == K_FILL:
-                zero[d] = o["a"] == 0
-            elif k == K_AXPY_SET:
-                zero[d] = (not o["prev"]) and bool(zero[o["src"]:o["src"] + o["len"]].all())
-            elif k == K_AXPY_INC:
-                if o["prev"] or not zero[o["src"]:o["src"] + o["len"]].all():
-                    zero[d] = False
-            elif k != K_PROBE:
-                zero[d] = False
-        for what, item in pack(self.ops, self.stage_batch, self.mutant == "op-25"):
+        launches = pack(self.ops, self.stage_batch, self.mutant == "op-25")
+        executed = [o for what, item in launches for o in (item if what == "list" else [item])]
+        tables = {o["table"]: self._table_zero(o, B, step0) for o in executed if o["kind"] == K_TABLE} if self.zero_skip else {}
+        skipped = zero_walk(executed, [tables], self.zero_skip, self.mutant == "prev-product-skipped", self.mutant == "inc-skipped-as-set")[0]
+        at = 0                                                      # index into `executed`
+        for what, item in launches:
             if what == "list":
                 for o in item:
                     self._elementwise(o, B, step0, prev(o), B - B % MULTI_ROWS if self.mutant == "multi-tail" else B)
-                    note(o)
+                at += len(item)
                 continue
-            o = item
-            if o["kind"] in PRODUCTS and self.zero_skip and (not o["prev"] or self.mutant == "prev-product-skipped") \
-                    and zero[o["src"]:o["src"] + o["cols"]].all():
+            o, at = item, at + 1
+            if at - 1 in skipped:
                 self.skipped += 1
-                if o["kind"] == K_MATVEC_SET or self.mutant == "inc-skipped-as-set":
+                if skipped[at - 1]:
                     wide = 1 if self.mutant == "memset-wide" else 0
                     self.R[1:B + 1, o["dst"]:o["dst"] + o["len"] + wide] = 0
-                    zero[o["dst"]:o["dst"] + o["len"]] = True
                 continue
             if o["kind"] in PRODUCTS:
                 self._product(o, B, prev(o))
@@ -535,7 +558,6 @@ class StandIn:
                 self._scan(o, B, prev(o))
             else:
                 self._elementwise(o, B, step0, prev(o), B)
-            note(o)
 
     def _elementwise(self, o, B, step0, prev, rows):
         """Rows 1 .. rows of one element-wise operator (rows < B: the wrong device that drops the tail of the 8-row walk)."""

@@ -1,45 +1,22 @@
 """The FFT planner (csrc/ssn_fft_plan.hpp) on a CPU: csrc/fft_plan_dump.cpp, compiled once with the host compiler, prints the routes
 and tables that k_dft and the binder are planned with.  Routes are held to the two independent restatements in Python
 (``dft_checks.plan``, ``bind_checks.plan``), tables to float64 NumPy."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import bind_checks as B
 import dft_checks as D
+from helpers import compiled_dump
 
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "semantic-spiking-neural-slam-2023_amd", "csrc")
 ROUTES = ("stockham-inplace", "stockham-outofplace", "fourstep-real", "fourstep-complex")
 LENGTHS = sorted(set(range(2, 513)) | {e[0] for e in D.LONG} | set(B.LENGTHS) | {3199, 3200, 3201, 6400, 6401})
 CHIRP_LENGTHS = (74, 97, 151, 239, 1801, 3199)
 ULP = 2.0 ** -23          # both sides round a double that is right to well under a float32 ulp: one ulp of a value <= 1 apart at most
 
 
-def _compiler():
-    for name in ("c++", "g++", "clang++"):
-        if shutil.which(name):
-            return shutil.which(name)
-    for root in (os.environ.get("ROCM_PATH"), "/opt/rocm"):
-        for rel in ("llvm/bin/clang++", "lib/llvm/bin/clang++", "bin/amdclang++"):
-            if root and os.path.exists(os.path.join(root, rel)):
-                return os.path.join(root, rel)
-    return None
-
-
 @pytest.fixture(scope="session")
 def dump(tmp_path_factory):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no C++ compiler on PATH or under the ROCm install")
-    exe = str(tmp_path_factory.mktemp("fft_plan") / "fft_plan_dump")
-    subprocess.run([cxx, "-std=c++17", "-O2", os.path.join(CSRC, "fft_plan_dump.cpp"), "-o", exe], check=True)
-
-    def run(*args):
-        return subprocess.run([exe] + [str(a) for a in args], check=True, capture_output=True, text=True).stdout
-    return run
+    return compiled_dump(tmp_path_factory, "fft_plan_dump")
 
 
 def _parse_route(line):
